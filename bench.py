@@ -16,6 +16,10 @@ Either way the ranks meet through libslamhip's RCCL communicator (slam_comm_*, n
 both sides of the timed region, MAX over ranks of the time, and the job's ONE collective -- the
 final min-all-reduce of the best-loss vector over xGMI.
 
+A plain run sets up, warms up, times exactly --steps steps once and prints the headline line; --dump-outputs DIR also writes
+what the timed path returned for its last step.  --full adds 3 repetitions of the timed region, the per-span roofline pass,
+the CPU baseline + parity sample and the secondary measurements.
+
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement".
 """
 from __future__ import annotations

@@ -138,14 +138,19 @@ def run_workload(args, workload, rank, world, local_rank, comm, steps, warmup, n
             # misses the threshold at its size goes on to the next) -- round 4 built the lists on the host, one call per size.
             # Local targets come back as (0, 0), targets beyond the whole template's reach as (+inf, -1).
             c.decompose_predicted(seq_coords, 3, gate_seqs, prm, threshold, first, n_per_step, carry=True, tol=5e-4)
-            best_loss, best_x, best_cycles = c.fetch_results_range(3, first, n_per_step)
-            return best_loss, best_cycles
+            return c.fetch_results_range(3, first, n_per_step)
         if sweep:
             c.set_gates(np.stack([sweep_gate(basis_of(s))]))
-            best_loss, best_x, best_cycles = c.decompose_range(0, n_per_step, 1, 3, gate_seqs, prm, threshold)
-        else:
-            best_loss, best_x, best_cycles = c.decompose_range(s * n_per_step, n_per_step, 1, 3, gate_seqs, prm, threshold)
-        return best_loss, best_cycles
+            return c.decompose_range(0, n_per_step, 1, 3, gate_seqs, prm, threshold)
+        return c.decompose_range(s * n_per_step, n_per_step, 1, 3, gate_seqs, prm, threshold)
+
+    last_step = total_steps - 1
+
+    def keep(results, s, bl, x, bc):
+        # a step's losses and template sizes are counted below; the parameters are kept for the last step only (--dump-outputs)
+        results[s] = (bl, bc)
+        if s == last_step:
+            results["last_x"] = x
 
     def sync():
         # barrier + device synchronisation on both sides of the timed region (all streams of this rank drained,
@@ -175,17 +180,17 @@ def run_workload(args, workload, rank, world, local_rank, comm, steps, warmup, n
                             ctx_basis[id(c)] = basis_of(s)
                     _ffi.decompose_multi(sub, 0, n_per_step, 1, 3, gate_seqs, prm, threshold)
                     for s, c in zip(g, sub):
-                        bl, _, bc = c.fetch_results_range(3, 0, n_per_step)
-                        results[s] = (bl, bc)
+                        keep(results, s, *c.fetch_results_range(3, 0, n_per_step))
                     continue
                 if len(g) == 1 or g != list(range(g[0], g[0] + len(g))):
                     for s in g:
-                        results[s] = one_step(s, ctxs[w])
+                        keep(results, s, *one_step(s, ctxs[w]))
                     continue
                 # one library call for the whole group of consecutive steps, results handed back per step
-                bl, _, bc = ctxs[w].decompose_range(g[0] * n_per_step, len(g) * n_per_step, 1, 3, gate_seqs, prm, threshold)
+                bl, bx, bc = ctxs[w].decompose_range(g[0] * n_per_step, len(g) * n_per_step, 1, 3, gate_seqs, prm, threshold)
                 for i, s in enumerate(g):
-                    results[s] = (bl[i * n_per_step : (i + 1) * n_per_step], bc[i * n_per_step : (i + 1) * n_per_step])
+                    win = slice(i * n_per_step, (i + 1) * n_per_step)
+                    keep(results, s, bl[win], bx[win], bc[win])
 
         if n_streams == 1:
             worker(0)
@@ -399,7 +404,27 @@ def run_workload(args, workload, rank, world, local_rank, comm, steps, warmup, n
         "rejected": rejected, "flops_accepted": flops_accepted, "flops_strict": flops_strict, "per_span": per_span,
         "resident_merge": resident_merge, "rep_ms": rep_ms, "strong": strong, "group": group, "gpu_sample": gpu_sample,
         "rank_diag": rank_diag, "mq": mq,
+        # what a caller of the timed path receives for its last step (median repetition)
+        "last_outputs": {"best_loss": res[last_step][0], "best_x": res["last_x"], "best_cycles": res[last_step][1]},
     }
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    """--dump-outputs: every array of `outputs` as path/<name>.npy in float64.  Above DUMP_MAX_BYTES in all, the same fixed,
+    seeded sample of rows is taken from every array, and the sampled row indices are written beside them (row_index.npy)."""
+    arrs = {k: np.asarray(v, dtype=np.float64) for k, v in outputs.items()}
+    n = len(next(iter(arrs.values())))
+    row_bytes = sum(a[:1].nbytes for a in arrs.values()) + 8
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["row_index"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -429,20 +454,35 @@ def main():
     ap.add_argument("--fast-exit", action="store_true",
                     help="drop SLAM_FLAG_ORDERED: the first restart to FINISH below stop_loss wins (timing-dependent winner) instead of "
                          "the lowest-index successful restart (the reference's sequential semantics, bitwise reproducible; default)")
-    ap.add_argument("--repeats", type=int, default=3,
-                    help="repetitions of the timed region (each exactly --steps steps between barriers); the line reports the median one and min / max")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: 3 repetitions of the timed region, the per-span roofline pass, the CPU baseline "
+                         "+ parity sample and the secondary measurements (a plain run sets up, warms up, times --steps steps once and reports)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last step (best_loss, best_x, best_cycles) "
+                         "as DIR/<name>.npy in float64")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the timed region (each exactly --steps steps between barriers); the line reports the median one and "
+                         "min / max (default 1; 3 with --full)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): every GPU gets its own full-size batches; strong: one GPU's batch per step is split over the --gpus ranks")
     ap.add_argument("--no-multi", action="store_true", help="cfg5: one library call per basis, 16 in flight (round 3) instead of slam_decompose_multi")
     ap.add_argument("--staged", action="store_true", help="one call in flight: never ask for the spans side by side (SLAM_FLAG_OVERLAP is asked for where the batch's coverage says it pays)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity sample")
     ap.add_argument("--cpu-sample", type=int, default=0, help="targets of the CPU baseline sample (default 4 x host cores)")
-    ap.add_argument("--per-span-steps", type=int, default=5, help="steps of the single-stream per-span roofline pass after the timed region (0 = skip)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary cfg2 / v2 measurements")
+    ap.add_argument("--per-span-steps", type=int, default=None,
+                    help="steps of the single-stream per-span roofline pass after the timed region (0 = skip; default 0, 5 with --full)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary cfg2 / v2 measurements")
     ap.add_argument("--v2-only", action="store_true", help="dev: run only the secondary.v2 measurement (CircuitTemplateV2) and print it")
     ap.add_argument("--long-only", action="store_true", help="dev: run only the secondary.long measurement (templates of 6..16 gates) and print it")
     ap.add_argument("--api-only", action="store_true", help="dev: run only the secondary.api measurement (TemplateOptimizer.approximate_from_distribution) and print it")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.per_span_steps is None:
+        args.per_span_steps = 5 if args.full else 0
+    if not args.full:
+        # a plain run measures the headline figure only
+        args.no_cpu_baseline = args.no_secondary = True
 
     stub = os.environ.get("SLAM_BENCH_TEST_STUB")
     if stub:
@@ -492,6 +532,8 @@ def main():
 
     comm = make_comm(rank, world, local_rank)
     m = run_workload(args, args.workload, rank, world, local_rank, comm, steps, warmup, args.streams, main=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["last_outputs"])
     secondary = None
     if not args.no_secondary and args.workload == "cfg3" and not args.span_rules and not args.targets and not args.restarts:
         # BASELINE configs[1] (1024 x 16 CNOT, the latency-bound small-batch regime) beside the headline

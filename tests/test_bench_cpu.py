@@ -16,7 +16,7 @@ def _run(extra, env_extra, timeout=180):
     env = dict(os.environ, SLAM_BENCH_TEST_STUB=os.path.join(ROOT, "tests", "bench_stub.py"), **env_extra)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary", "--per-span-steps", "0"] + extra,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary", "--per-span-steps", "0"] + extra,
                        env=env, capture_output=True, text=True, timeout=timeout)
     return p
 
@@ -122,9 +122,67 @@ def test_two_ranks_under_torch_distributed_run():
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--targets", "256",
-                        "--restarts", "4", "--no-cpu-baseline", "--no-secondary", "--per-span-steps", "0"], env=env, capture_output=True, text=True, timeout=300)
+                        "--restarts", "4", "--full", "--no-cpu-baseline", "--no-secondary", "--per-span-steps", "0"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["comm"] == "FileComm" and len(out["rank_devices"]) == 2 and out["steps"] == 3
+
+
+def test_plain_run_times_only_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full): ONE repetition of exactly --steps timed steps, no per-span pass, no CPU baseline, no secondary
+    measurements; --dump-outputs writes what the timed path returned for its last step (here the stub's fake results of targets
+    (steps + warmup - 1) * n .. (steps + warmup) * n - 1), float64, the same on every run."""
+    env = dict(os.environ, SLAM_BENCH_TEST_STUB=os.path.join(ROOT, "tests", "bench_stub.py"))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SLAM_BENCH_FORCE_LAUNCH"):
+        env.pop(k, None)
+    steps, warmup, n = 5, 2, 256
+    outs = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--targets", str(n), "--restarts", "4", "--dump-outputs", str(tmp_path / d)],
+                           env=env, capture_output=True, text=True, timeout=180)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == steps and out["warmup"] == warmup and out["repetitions"] == 1 and len(out["ms_per_step_all"]) == 1
+    assert "secondary" not in out and "cpu_baseline" not in out and "parity_sample" not in out and "per_span" not in out["roofline"]
+    # the stub counts 40 evaluations per item and span: exactly `steps` steps were timed
+    assert out["roofline"]["evals_per_span"] == {str(k): 40 * steps * n * 4 for k in (1, 2, 3)}
+    import numpy as np
+
+    idx = 20260000 + (steps + warmup - 1) * n + np.arange(n)
+    want = {"best_loss": np.where(idx % 7 == 0, 1e-3, 1e-12 * (1 + idx % 5)), "best_cycles": np.where(idx % 7 == 0, 3, 2), "best_x": np.zeros((n, 24))}
+    for name, w in want.items():
+        a, b = (np.load(tmp_path / d / f"{name}.npy") for d in ("a", "b"))
+        assert a.dtype == np.float64 and a.shape == w.shape and np.array_equal(a, w) and np.array_equal(a, b), name
+    assert sorted(os.listdir(tmp_path / "a")) == ["best_cycles.npy", "best_loss.npy", "best_x.npy"]
+
+
+def test_dump_outputs_samples_rows_above_64_mb(tmp_path):
+    """Outputs above 64 MB in all: the same fixed, seeded rows of every array, their indices beside them."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    from benchlib.run import DUMP_MAX_BYTES, dump_outputs
+
+    n = 400_000
+    x = np.arange(n * 24, dtype=np.float64).reshape(n, 24)
+    outputs = {"best_loss": np.arange(n, dtype=np.float64), "best_x": x, "best_cycles": np.arange(n, dtype=np.int32) % 4}
+    for d in ("a", "b"):
+        dump_outputs(str(tmp_path / d), outputs)
+    total = sum(np.load(tmp_path / "a" / f).nbytes for f in os.listdir(tmp_path / "a"))
+    assert total <= DUMP_MAX_BYTES
+    rows = np.load(tmp_path / "a" / "row_index.npy")
+    assert rows.dtype == np.float64 and len(rows) > n // 2 and np.all(np.diff(rows) > 0)
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "best_loss.npy"), r)
+    assert np.array_equal(np.load(tmp_path / "a" / "best_x.npy"), x[r])
+    assert np.array_equal(np.load(tmp_path / "a" / "best_cycles.npy"), (r % 4).astype(np.float64))
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

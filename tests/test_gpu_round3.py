@@ -21,7 +21,7 @@ def _bench(extra, env_extra):
     env = dict(os.environ, **env_extra)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SLAM_BENCH_TEST_STUB"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary", "--per-span-steps", "0"] + extra,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary", "--per-span-steps", "0"] + extra,
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 ENVS=""
 if [ "$1" = "-e" ]; then ENVS="$2"; shift 2; fi
 for args in "$@"; do
-  env $ENVS python3 bench.py --no-cpu-baseline --no-secondary $args > /tmp/bs.json 2> /tmp/bs.err || { echo "FAILED: $args"; tail -3 /tmp/bs.err; exit 1; }
+  env $ENVS python3 bench.py --full --no-cpu-baseline --no-secondary $args > /tmp/bs.json 2> /tmp/bs.err || { echo "FAILED: $args"; tail -3 /tmp/bs.err; exit 1; }
   python3 - "$args" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/bs.json").read().strip().splitlines()[-1])

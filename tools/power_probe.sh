@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: sample clocks / power with rocm-smi while the cfg3 workload runs (is the fp64 loop power-limited?)
-python bench.py --workload cfg3 --no-cpu-baseline --steps 150 --warmup 3 > /tmp/pp.json 2>/dev/null &
+python bench.py --full --workload cfg3 --no-cpu-baseline --steps 150 --warmup 3 > /tmp/pp.json 2>/dev/null &
 BP=$!
 sleep 2.5
 for i in 1 2 3 4; do

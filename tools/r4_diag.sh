@@ -12,7 +12,7 @@ python3 tools/r4_solo_probe.py sqiswap 65536 32 6 > $OUT/solo_probe.txt 2>&1 || 
 cat $OUT/solo_probe.txt
 COMMON="--no-cpu-baseline --no-secondary"
 probe() {  # $1 = tag, rest = bench args: clocks / power sampled while the bench runs
-  python3 bench.py $COMMON --steps 150 --warmup 3 --repeats 1 --per-span-steps 0 "${@:2}" > $OUT/pp_$1.json 2> $OUT/pp_$1.err &
+  python3 bench.py --full $COMMON --steps 150 --warmup 3 --repeats 1 --per-span-steps 0 "${@:2}" > $OUT/pp_$1.json 2> $OUT/pp_$1.err &
   BP=$!
   sleep 6
   for i in 1 2 3 4 5; do
@@ -29,7 +29,7 @@ print('$1', '%.4g dec/s' % d['value'], '%.3f ms/step' % d['ms_per_step'], 'frac 
 probe s1 --streams 1
 probe s2 --streams 2
 probe s5 --streams 5
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_headline -- python3 bench.py --steps 20 --warmup 5 $COMMON --per-span-steps 0 > $OUT/headline_bench_under_trace.json 2> $OUT/trace_headline.err || { tail -5 $OUT/trace_headline.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_headline -- python3 bench.py --full --steps 20 --warmup 5 $COMMON --per-span-steps 0 > $OUT/headline_bench_under_trace.json 2> $OUT/trace_headline.err || { tail -5 $OUT/trace_headline.err; exit 1; }
 KT=$(ls $OUT/trace_headline/*/*_kernel_trace.csv | head -1)
 python3 tools/trace_concurrency.py $KT > $OUT/headline_concurrency.txt
 cat $OUT/headline_concurrency.txt

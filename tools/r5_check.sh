@@ -14,7 +14,7 @@ if [ "$1" != "none" ]; then
   if [ $rc -ne 0 ]; then grep -n "Error\|assert\|FAILED" $OUT/pytest.txt | tail -30; exit 1; fi
 fi
 [ "$2" = "nobench" ] && exit 0
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; rc=$?
+timeout -k 10 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; rc=$?
 if [ $rc -ne 0 ]; then tail -20 $OUT/bench_default.err; exit 1; fi
 python3 - <<'PY'
 import json

@@ -7,7 +7,7 @@ import json,sys; d=json.loads(open('$1').read().strip().splitlines()[-1]); r=d['
 for rep in 1 2; do for keep in 0 1; do
   if [ $keep = 1 ]; then export MALLOC_MMAP_THRESHOLD_=33554432 MALLOC_TRIM_THRESHOLD_=17179869184 MALLOC_TOP_PAD_=268435456; else unset MALLOC_MMAP_THRESHOLD_ MALLOC_TRIM_THRESHOLD_ MALLOC_TOP_PAD_; fi
   for w in cfg3 cfg4 cfg2 cfg5; do
-    python3 bench.py --workload $w --no-cpu-baseline --no-secondary --per-span-steps 0 > $O/${w}_$keep.json 2>> $O/err.txt; show $O/${w}_$keep.json "keep $keep $w"
+    python3 bench.py --full --workload $w --no-cpu-baseline --no-secondary --per-span-steps 0 > $O/${w}_$keep.json 2>> $O/err.txt; show $O/${w}_$keep.json "keep $keep $w"
   done
   python3 bench.py --api-only 2>> $O/err.txt | python3 -c "
 import json,sys
