@@ -348,10 +348,18 @@ int slam_minimize_stage_trace(slam_ctx* ctx, int k, const int32_t* gate_seq, con
  * (UnitaryCostFunction subclasses, src/slam/cost_function.py):
  *   SLAM_COST_BASIC   BasicCost   1 - |Tr(T^+ U)| / d                       (cost_function.py:140-145), default
  *   SLAM_COST_SQUARE  SquareCost  1 - (|Tr(T^+ U)|^2 + d) / (d (d + 1))     (cost_function.py:169-173)
+ *   SLAM_COST_MAKHLIN MakhlinFunctionalCost  sum_i (g_i(U) - g_i(T))^2       (cost_function.py:219-221, weylchamber J_T_LI)
+ *                     with g = (Re G1, Im G1, Re G2) the Makhlin local invariants: the distance up to single-qubit gates.  Unrounded
+ *                     (the reference's invariants are rounded to 8 digits).  Honoured by slam_eval_loss_grad, slam_eval_unitary,
+ *                     slam_minimize_stage(_trace), slam_decompose, slam_decompose_range(_fetch), slam_decompose_list /
+ *                     _resident and slam_decompose_predicted -- always through the per-span launches (as SLAM_FLAG_STAGED |
+ *                     SLAM_FLAG_NO_OVERLAP), whatever the flags say.  slam_decompose_multi and the slam_v2_* family return
+ *                     SLAM_ERR_UNSUPPORTED under it.
  * Anything else fails like the reference's objective_func: "Unrecognized Cost Function" (optimizer.py:211).
  */
 #define SLAM_COST_BASIC 0
 #define SLAM_COST_SQUARE 1
+#define SLAM_COST_MAKHLIN 2
 int slam_set_cost(slam_ctx* ctx, int cost);
 
 /* Block until all work queued on the context's stream has finished. */

@@ -32,7 +32,7 @@ MAX_MAXITER = 4000
 V2_MAX_SPAN = 5
 OP_SUM, OP_MAX, OP_MIN = 0, 2, 3
 COMM_ID_BYTES = 128
-COST_BASIC, COST_SQUARE = 0, 1
+COST_BASIC, COST_SQUARE, COST_MAKHLIN = 0, 1, 2
 
 # every symbol include/slam_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -780,7 +780,7 @@ class Context:
         return out
 
     def set_cost(self, kind: int) -> None:
-        """0 = BasicCost (default), 1 = SquareCost."""
+        """0 = BasicCost (default), 1 = SquareCost, 2 = MakhlinFunctionalCost (per-span launches; not for decompose_multi / V2)."""
         _check(self._lib.slam_set_cost(self._h, int(kind)))
 
     def synchronize(self) -> None:

@@ -642,6 +642,185 @@ __device__ __forceinline__ int theta_slot_bits(int q) {
 }
 
 // ---------------------------------------------------------------------------------
+// MakhlinFunctionalCost (cost_function.py:219-221, weylchamber's J_T_LI, unrounded): J(W; T) = |g(W) - g(T)|^2 with the local
+// invariants g = (Re G1, Im G1, Re G2) of Makhlin in the form without a basis change:
+//   Y = sigma_y (x) sigma_y,  M = W^T Y W Y,  d = det W,  G1 = tr(M)^2 / (16 d),  G2 = (tr(M)^2 - tr(M^2)) / (4 d).
+// Y is real and antidiagonal, Y[r][3 - r] = y_r with y = (-1, 1, 1, -1).  A = W^T Y W is symmetric and M = A Y.
+// Lane q of a quad holds column q of the 4x4 matrix (as everywhere in the quad kernels); the quad exchanges columns with DPP
+// quad_perm moves only (no LDS: the exchange area is full of the trig table at this point).  Every quantity below comes out
+// bit-identical in the four lanes (quad sums are symmetric, the determinant is formed from the same operands in every lane).
+// ---------------------------------------------------------------------------------
+__host__ __device__ constexpr double mk_y(int r) { return (r == 0 || r == 3) ? -1.0 : 1.0; }
+
+// quad_perm [P, P, P, P]: lane P's value in all four lanes
+template <int P>
+__device__ __forceinline__ void mk_bcast_col(const double (&wr)[4], const double (&wi)[4], double (&cr)[4], double (&ci)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        cr[r] = dpp_f64<P * 0x55>(wr[r]);
+        ci[r] = dpp_f64<P * 0x55>(wi[r]);
+    }
+}
+
+struct MkInv {
+    double tr, ti;    // tr M
+    double t2r, t2i;  // tr M^2
+    double dr, di;    // det W
+    double ar[4], ai[4];  // row q of A
+    double br[4], bi[4];  // row 3 - q of A
+};
+
+__device__ __forceinline__ void mk_invariants(const double (&wr)[4], const double (&wi)[4], int q, MkInv& v) {
+    const double yq = ((q + 1) & 2) ? 1.0 : -1.0;
+    // A[q][j] = sum_r u[r] W[r][j],  u[r] = y_r W[3 - r][q]
+    double ur[4], ui[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { ur[r] = mk_y(r) * wr[3 - r]; ui[r] = mk_y(r) * wi[3 - r]; }
+    auto arow = [&](int j, const double (&cr)[4], const double (&ci)[4]) {
+        double sr = 0.0, si = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            sr = fma(ur[r], cr[r], fma(-ui[r], ci[r], sr));
+            si = fma(ur[r], ci[r], fma(ui[r], cr[r], si));
+        }
+        v.ar[j] = sr; v.ai[j] = si;
+    };
+    { double cr[4], ci[4]; mk_bcast_col<0>(wr, wi, cr, ci); arow(0, cr, ci); }
+    { double cr[4], ci[4]; mk_bcast_col<1>(wr, wi, cr, ci); arow(1, cr, ci); }
+    { double cr[4], ci[4]; mk_bcast_col<2>(wr, wi, cr, ci); arow(2, cr, ci); }
+    { double cr[4], ci[4]; mk_bcast_col<3>(wr, wi, cr, ci); arow(3, cr, ci); }
+    // row 3 - q of A: quad_perm [3, 2, 1, 0]
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v.br[k] = dpp_f64<0x1B>(v.ar[k]); v.bi[k] = dpp_f64<0x1B>(v.ai[k]); }
+    // tr M = sum_q y_q A[q][3 - q];  tr M^2 = sum_q y_q sum_j y_j A[q][3 - j] A[3 - q][j]
+    const double a3r = q == 0 ? v.ar[3] : (q == 1 ? v.ar[2] : (q == 2 ? v.ar[1] : v.ar[0]));
+    const double a3i = q == 0 ? v.ai[3] : (q == 1 ? v.ai[2] : (q == 2 ? v.ai[1] : v.ai[0]));
+    double tr = yq * a3r, ti = yq * a3i;
+    double t2r = 0.0, t2i = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double pr = v.ar[3 - j] * v.br[j] - v.ai[3 - j] * v.bi[j];
+        const double pi = v.ar[3 - j] * v.bi[j] + v.ai[3 - j] * v.br[j];
+        t2r = fma(mk_y(j), pr, t2r);
+        t2i = fma(mk_y(j), pi, t2i);
+    }
+    t2r *= yq; t2i *= yq;
+    quad_sum2(tr, ti);
+    quad_sum2(t2r, t2i);
+    v.tr = tr; v.ti = ti; v.t2r = t2r; v.t2i = t2i;
+    // det W by Laplace expansion along the column pairs (0, 1) | (2, 3): the 2x2 minors of the lane's pair (q & ~1, q | 1), then
+    // the other pair's minors from lane q ^ 2
+    double pr_[4], pi_[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { pr_[r] = dpp_f64<0xB1>(wr[r]); pi_[r] = dpp_f64<0xB1>(wi[r]); }
+    const bool odd = q & 1;
+    double xr[4], xi[4], zr[4], zi[4];  // columns 2 (q >> 1) and 2 (q >> 1) + 1
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        xr[r] = odd ? pr_[r] : wr[r]; xi[r] = odd ? pi_[r] : wi[r];
+        zr[r] = odd ? wr[r] : pr_[r]; zi[r] = odd ? wi[r] : pi_[r];
+    }
+    constexpr int R1[6] = {0, 0, 0, 1, 1, 2}, R2[6] = {1, 2, 3, 2, 3, 3};
+    double mr[6], mi[6], orr[6], oi[6];
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+        const int a = R1[p], b = R2[p];
+        mr[p] = (xr[a] * zr[b] - xi[a] * zi[b]) - (xr[b] * zr[a] - xi[b] * zi[a]);
+        mi[p] = (xr[a] * zi[b] + xi[a] * zr[b]) - (xr[b] * zi[a] + xi[b] * zr[a]);
+    }
+#pragma unroll
+    for (int p = 0; p < 6; ++p) { orr[p] = dpp_f64<0x4E>(mr[p]); oi[p] = dpp_f64<0x4E>(mi[p]); }
+    const bool hi = q & 2;
+    double dr = 0.0, di = 0.0;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+        // minors of columns (0, 1) on rows p times minors of columns (2, 3) on the complementary rows (pair 5 - p)
+        const double Pr = hi ? orr[p] : mr[p], Pi = hi ? oi[p] : mi[p];
+        const double Qr = hi ? mr[5 - p] : orr[5 - p], Qi = hi ? mi[5 - p] : oi[5 - p];
+        const double s = (p == 1 || p == 4) ? -1.0 : 1.0;
+        dr = fma(s, Pr * Qr - Pi * Qi, dr);
+        di = fma(s, Pr * Qi + Pi * Qr, di);
+    }
+    v.dr = dr; v.di = di;
+}
+
+// g = (Re G1, Im G1, Re G2) from the invariants; also returns 1 / d and G1, G2 (complex)
+__device__ __forceinline__ void mk_g(const MkInv& v, double (&g)[3], double& idr, double& idi, double& G1r, double& G1i, double& G2r,
+                                     double& G2i) {
+    const double rd = fast_rcp(v.dr * v.dr + v.di * v.di);
+    idr = v.dr * rd; idi = -v.di * rd;
+    const double sr = v.tr * v.tr - v.ti * v.ti, si = 2.0 * v.tr * v.ti;  // tr(M)^2
+    G1r = 0.0625 * (sr * idr - si * idi); G1i = 0.0625 * (sr * idi + si * idr);
+    const double er = sr - v.t2r, ei = si - v.t2i;
+    G2r = 0.25 * (er * idr - ei * idi); G2i = 0.25 * (er * idi + ei * idr);
+    g[0] = G1r; g[1] = G1i; g[2] = G2r;
+}
+
+// the three target invariants of the quad's target, column q of T at tcol (row-major (re, im), as eval_quad reads it)
+__device__ __forceinline__ void mk_target_g(const double* tcol, int q, double (&g)[3]) {
+    double tr[4], ti[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const double2 t = *reinterpret_cast<const double2*>(tcol + 8 * r);
+        tr[r] = t.x; ti[r] = t.y;
+    }
+    MkInv v;
+    mk_invariants(tr, ti, q, v);
+    double a, b, c, d, e, f;
+    mk_g(v, g, a, b, c, d, e, f);
+}
+
+// J and row q of the adjoint seed S (dJ = Re Tr(S dW)), W given by columns (lane q: column q):
+//   S_tr = 2 Y W^T Y,  S_tr2 = 2 (M^T Y W^T Y + Y M W^T Y) = 2 M^T S_tr  (M^T = Y M Y = Y A),
+//   S = (2 D1 - 2i D2) (2 tr(M) S_tr / (16 d) - G1 W^+) + 2 D3 ((2 tr(M) S_tr - S_tr2) / (4 d) - G2 W^+),  D = g(W) - g(T)
+// (d det W = det W tr(W^-1 dW), W^-1 = W^+ for a unitary W).  Row q of S_tr is 2 y_q y_c W[3 - c][3 - q] (column 3 - q, one quad_perm
+// away); row q of S_tr2 is 4 y_q y_c sum_m A[3 - q][3 - m] y_m W[3 - c][m] (the four columns broadcast once more).
+__device__ __forceinline__ void mk_loss_seed(const double (&wr)[4], const double (&wi)[4], int q, const double (&gT)[3], double& fout,
+                                             double (&Ur)[4], double (&Ui)[4]) {
+    MkInv v;
+    mk_invariants(wr, wi, q, v);
+    double g[3], idr, idi, G1r, G1i, G2r, G2i;
+    mk_g(v, g, idr, idi, G1r, G1i, G2r, G2i);
+    const double D1 = g[0] - gT[0], D2 = g[1] - gT[1], D3 = g[2] - gT[2];
+    fout = fma(D1, D1, fma(D2, D2, D3 * D3));
+    const double a1r = 2.0 * D1, a1i = -2.0 * D2, a3 = 2.0 * D3;
+    // alpha = tr(M) / d (a1 / 8 + a3 / 2),  beta = -a3 / (4 d),  gamma = -(a1 G1 + a3 G2)
+    const double tdr = v.tr * idr - v.ti * idi, tdi = v.tr * idi + v.ti * idr;
+    const double cr = fma(0.125, a1r, 0.5 * a3), ci = 0.125 * a1i;
+    const double alr = tdr * cr - tdi * ci, ali = tdr * ci + tdi * cr;
+    const double ber = -0.25 * a3 * idr, bei = -0.25 * a3 * idi;
+    const double gar = -((a1r * G1r - a1i * G1i) + a3 * G2r), gai = -((a1r * G1i + a1i * G1r) + a3 * G2i);
+    // acc[r] = sum_m A[3 - q][3 - m] y_m W[r][m]
+    double accr[4] = {0.0, 0.0, 0.0, 0.0}, acci[4] = {0.0, 0.0, 0.0, 0.0};
+    auto accum = [&](int m, const double (&cr_)[4], const double (&ci_)[4]) {
+        const double kr = mk_y(m) * v.br[3 - m], ki = mk_y(m) * v.bi[3 - m];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            accr[r] = fma(kr, cr_[r], fma(-ki, ci_[r], accr[r]));
+            acci[r] = fma(kr, ci_[r], fma(ki, cr_[r], acci[r]));
+        }
+    };
+    { double c0r[4], c0i[4]; mk_bcast_col<0>(wr, wi, c0r, c0i); accum(0, c0r, c0i); }
+    { double c1r[4], c1i[4]; mk_bcast_col<1>(wr, wi, c1r, c1i); accum(1, c1r, c1i); }
+    { double c2r[4], c2i[4]; mk_bcast_col<2>(wr, wi, c2r, c2i); accum(2, c2r, c2i); }
+    { double c3r[4], c3i[4]; mk_bcast_col<3>(wr, wi, c3r, c3i); accum(3, c3r, c3i); }
+    // column 3 - q of W
+    double wbr[4], wbi[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { wbr[r] = dpp_f64<0x1B>(wr[r]); wbi[r] = dpp_f64<0x1B>(wi[r]); }
+    const double yq = ((q + 1) & 2) ? 1.0 : -1.0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double s = yq * mk_y(c);
+        // S[q][c] = s (2 alpha W[3 - c][3 - q] + 4 beta acc[3 - c]) + gamma conj(W[c][q])
+        const double xr = 2.0 * (alr * wbr[3 - c] - ali * wbi[3 - c]) + 4.0 * (ber * accr[3 - c] - bei * acci[3 - c]);
+        const double xi = 2.0 * (alr * wbi[3 - c] + ali * wbr[3 - c]) + 4.0 * (ber * acci[3 - c] + bei * accr[3 - c]);
+        Ur[c] = fma(s, xr, gar * wr[c] + gai * wi[c]);
+        Ui[c] = fma(s, xi, gai * wr[c] - gar * wi[c]);
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // Fused forward chain + BasicCost + analytic gradient for the quad's item.
 //   xd    this lane's parameter slots: xd[a] = x[4a + q]
 //   tcol  global pointer to T[0][q] of the item's target (row-major (re, im): T[r][q] is 8 r doubles on);
@@ -656,11 +835,12 @@ __device__ __forceinline__ int theta_slot_bits(int q) {
 // HUGE_ARGS: also handle |x| >= 2e9 (out-of-line ocml path).  The optimizer kernel keeps |x| far
 // below that (x0 in [0, 2 pi) or validated by the host, steps <= 2 rad) and instantiates false, so no
 // function call -- and none of the register save/restore traffic a call site drags in -- sits in its loop.
-template <int K, bool HUGE_ARGS, int GC>
+// MK: MakhlinFunctionalCost instead (cost_kind is ignored, the target column is not read): mkt = the target's invariants g(T)
+template <int K, bool HUGE_ARGS, int GC, bool MK = false>
 __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const double* tcol,
                                           const double* gates, double* xq, double2* fh, const double2* tbl,
                                           int q, int theta_bits, int cost_kind, double& fout, double (&gd)[Cfg<K>::NA],
-                                          double (&Wr)[4], double (&Wi)[4]) {
+                                          double (&Wr)[4], double (&Wi)[4], const double* mkt = nullptr) {
     constexpr bool LEAN = lean_layout<K, GC>();
     constexpr bool PSQ = psq_layout<K, GC>();
     using C = Cfg<K, PSQ>;
@@ -670,11 +850,13 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
     auto HS = [](int j) constexpr { return LEAN ? j : 2 * j + 1; };  // fh slot of the layer output h_j
     // the target column is requested first and consumed after the forward pass
     double tre[4], tim[4];
+    if constexpr (!MK) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const double2 t = *reinterpret_cast<const double2*>(tcol + 8 * r);
-        tre[r] = t.x;
-        tim[r] = t.y;
+        for (int r = 0; r < 4; ++r) {
+            const double2 t = *reinterpret_cast<const double2*>(tcol + 8 * r);
+            tre[r] = t.x;
+            tim[r] = t.y;
+        }
     }
     // ---- 1. trig table: each lane handles its own parameter slots
     {
@@ -791,38 +973,45 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
 #pragma unroll
     for (int r = 0; r < 4; ++r) { Wr[r] = Fr[r]; Wi[r] = Fi[r]; }
 
-    // ---- 3. t = Tr(T^+ W), loss, z = -conj(t) / (4|t|)
-    double pr = 0.0, pi = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        pr = fma(tre[r], Fr[r], fma(tim[r], Fi[r], pr));
-        pi = fma(tre[r], Fi[r], fma(-tim[r], Fr[r], pi));
-    }
-    quad_sum2(pr, pi);
-    const double at2 = pr * pr + pi * pi;
-    const double rat = (at2 > 1e-300) ? fast_rsqrt(at2) : 0.0;  // 1 / |t|
-    const double at = at2 * rat;
-    const double basic = 1.0 - 0.25 * at;  // BasicCost, cost_function.py:140-145
-    // SquareCost (cost_function.py:169-173): 1 - (|t|^2 + d) / (d (d + 1)), d = 4, is the monotone map
-    // 0.8 (2 L - L^2) of BasicCost L, so its gradient is 1.6 (1 - L) times BasicCost's (wave-uniform select)
-    // written as L (c0 + c1 L) and its derivative factor d0 + d1 L with wave-uniform coefficients ((1, 0), (1, 0) for
-    // BasicCost -- exact --, (1.6, -0.8), (1.6, -1.6) for SquareCost): scalar selects instead of vector ones
-    // (opaque: hoisted out of the optimizer loop the three coefficients were spilled into VGPR lanes and came back through six
-    // v_readlane -- vector-ALU slots -- per evaluation; re-selected here they are three s_cselect_b64)
-    asm volatile("" : "+s"(cost_kind));
-    const bool sq = (cost_kind == 1);
-    const double c0 = sq ? 1.6 : 1.0, c1 = sq ? -0.8 : 0.0, d1 = sq ? -1.6 : 0.0;
-    fout = basic * fma(c1, basic, c0);
-    const double inv = (0.25 * rat) * fma(d1, basic, c0);
-    const double zr = -pr * inv, zi = pi * inv;
-
-    // ---- 4. backward: u = row q of (z T^+)(suffix); accumulate this column's partials
     double Ur[4], Ui[4];
+    if constexpr (MK) {
+        // ---- 3-4. MakhlinFunctionalCost: loss and row q of the adjoint seed S (in place of z T^+)
+        const double gT[3] = {mkt[0], mkt[1], mkt[2]};
+        mk_loss_seed(Fr, Fi, q, gT, fout, Ur, Ui);
+    } else {
+        // ---- 3. t = Tr(T^+ W), loss, z = -conj(t) / (4|t|)
+        double pr = 0.0, pi = 0.0;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        Ur[r] = zr * tre[r] + zi * tim[r];
-        Ui[r] = zi * tre[r] - zr * tim[r];
+        for (int r = 0; r < 4; ++r) {
+            pr = fma(tre[r], Fr[r], fma(tim[r], Fi[r], pr));
+            pi = fma(tre[r], Fi[r], fma(-tim[r], Fr[r], pi));
+        }
+        quad_sum2(pr, pi);
+        const double at2 = pr * pr + pi * pi;
+        const double rat = (at2 > 1e-300) ? fast_rsqrt(at2) : 0.0;  // 1 / |t|
+        const double at = at2 * rat;
+        const double basic = 1.0 - 0.25 * at;  // BasicCost, cost_function.py:140-145
+        // SquareCost (cost_function.py:169-173): 1 - (|t|^2 + d) / (d (d + 1)), d = 4, is the monotone map
+        // 0.8 (2 L - L^2) of BasicCost L, so its gradient is 1.6 (1 - L) times BasicCost's (wave-uniform select)
+        // written as L (c0 + c1 L) and its derivative factor d0 + d1 L with wave-uniform coefficients ((1, 0), (1, 0) for
+        // BasicCost -- exact --, (1.6, -0.8), (1.6, -1.6) for SquareCost): scalar selects instead of vector ones
+        // (opaque: hoisted out of the optimizer loop the three coefficients were spilled into VGPR lanes and came back through six
+        // v_readlane -- vector-ALU slots -- per evaluation; re-selected here they are three s_cselect_b64)
+        asm volatile("" : "+s"(cost_kind));
+        const bool sq = (cost_kind == 1);
+        const double c0 = sq ? 1.6 : 1.0, c1 = sq ? -0.8 : 0.0, d1 = sq ? -1.6 : 0.0;
+        fout = basic * fma(c1, basic, c0);
+        const double inv = (0.25 * rat) * fma(d1, basic, c0);
+        const double zr = -pr * inv, zi = pi * inv;
+        // row q of the seed z T^+
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            Ur[r] = zr * tre[r] + zi * tim[r];
+            Ui[r] = zi * tre[r] - zr * tim[r];
+        }
     }
+
+    // ---- 4. backward: u = row q of (seed)(suffix); accumulate this column's partials
     constexpr bool kL0Out = true;  // layer 0's partials from its output side (l0_gate_partials)
     constexpr bool kBwdTrigAhead = (K == 1);
     constexpr bool kEarlyP = (K <= 4);

@@ -137,6 +137,11 @@ struct slam_ctx {
     int64_t resident_waves_mq[SLAM_MAX_SPAN_EVAL + 1][kGateClasses] = {};
     int64_t resident_waves_long = 0;  // wavefront-per-item kernels (slam_long.hpp): resident wavefronts; 0 = not asked yet
     bool long_eval_ready = false;
+    // MakhlinFunctionalCost kernels (eval_mk_kernel / minimize_mk_kernel / the *_long_mk_kernel pair): attributes set, resident wavefronts
+    bool mk_lds_set[SLAM_MAX_SPAN_QUAD + 1][2] = {};
+    int64_t resident_waves_mk[SLAM_MAX_SPAN_QUAD + 1] = {};
+    int64_t resident_waves_long_mk = 0;
+    bool long_eval_mk_ready = false;
     int64_t resident_waves_wl[kGateClasses] = {};  // span_wave_kernel<GC>: resident wavefronts (0 = not asked yet)
     // speculative spans (span_spec_kernel): staging rows, two side streams, fork / join events
     DevBuf spec_loss, spec_x, spec_ev;
@@ -302,6 +307,31 @@ int launch_eval(slam_ctx* c, const int32_t* gate_seq, const double* d_x, const i
     return SLAM_OK;
 }
 
+// MakhlinFunctionalCost: the dense gate class whatever the gates' structure (one instantiation per span)
+template <int K>
+int launch_eval_mk(slam_ctx* c, const int32_t* gate_seq, const double* d_x, const int32_t* d_tof, int64_t M, double* d_loss, double* d_grad,
+                   double* d_unitary) {
+    const size_t lds = lds_bytes<K, GC_DENSE>();
+    if (!c->mk_lds_set[K][0]) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_mk_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        c->mk_lds_set[K][0] = true;
+    }
+    EvalArgs<K> a{};
+    a.targets = c->targets.as<double>();
+    a.x = d_x;
+    a.target_of = d_tof;
+    a.n_items = M;
+    a.loss = d_loss;
+    a.grad = d_grad;
+    a.unitary = d_unitary;
+    a.cost_kind = c->cost_kind;
+    { int rc = stage_gates(c, K, gate_seq, &a.gates); if (rc) return rc; }
+    const int64_t blocks = (M + kQuadsPerWave - 1) / kQuadsPerWave;
+    hipLaunchKernelGGL((eval_mk_kernel<K>), dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    return SLAM_OK;
+}
+
 struct StageLaunch {
     double exit_loss;               // a finished restart below this pre-empts its siblings
     const int32_t* gate_seq;
@@ -390,13 +420,45 @@ int launch_minimize(slam_ctx* c, const StageLaunch& sl) {
     return SLAM_OK;
 }
 
+// MakhlinFunctionalCost, spans 1..SLAM_MAX_SPAN_QUAD: the per-span optimizer launch of the dense gate class
+template <int K>
+int launch_minimize_mk(slam_ctx* c, const StageLaunch& sl) {
+    const size_t lds = lds_bytes<K, GC_DENSE>();
+    if (!c->mk_lds_set[K][1]) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&minimize_mk_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&minimize_mk_kernel<K>), kWave, lds));
+        if (per_cu < 1) per_cu = 1;
+        c->resident_waves_mk[K] = (int64_t)per_cu * c->compute_units;
+        c->mk_lds_set[K][1] = true;
+    }
+    const slam_opt_params* prm = sl.prm;
+    MinimizeArgs<K> a;
+    { int rc = build_minimize_args<K>(c, sl, a); if (rc) return rc; }
+    int64_t blocks = (sl.n_items_max + kQuadsPerWave - 1) / kQuadsPerWave;
+    if (prm->items_per_quad > 1) {
+        blocks = (sl.n_items_max + (int64_t)kQuadsPerWave * prm->items_per_quad - 1) / ((int64_t)kQuadsPerWave * prm->items_per_quad);
+        if (blocks < 1) blocks = 1;
+    }
+    const int64_t cap = c->resident_waves_mk[K] - c->reserve_waves > 0 ? c->resident_waves_mk[K] - c->reserve_waves : 1;
+    if (blocks > cap) blocks = cap;
+    HIP_TRY(hipEventRecord(c->ev_a[K], c->stream));
+    hipLaunchKernelGGL((minimize_mk_kernel<K>), dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_b[K], c->stream));
+    return SLAM_OK;
+}
+
 // templates of SLAM_MAX_SPAN_QUAD + 1 .. SLAM_MAX_SPAN_MINIMIZE gates: one wavefront per item (slam_long.hpp)
 int launch_minimize_long(slam_ctx* c, const StageLaunch& sl, int k) {
-    if (c->resident_waves_long == 0) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&minimize_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes));
+    const bool mk = c->cost_kind == SLAM_COST_MAKHLIN;
+    const void* kern = mk ? reinterpret_cast<const void*>(&minimize_long_mk_kernel) : reinterpret_cast<const void*>(&minimize_long_kernel);
+    int64_t& resident = mk ? c->resident_waves_long_mk : c->resident_waves_long;
+    if (resident == 0) {
+        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes));
         int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&minimize_long_kernel), kWave, kLongLdsBytes));
-        c->resident_waves_long = (int64_t)(per_cu < 1 ? 1 : per_cu) * c->compute_units;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, kLongLdsBytes));
+        resident = (int64_t)(per_cu < 1 ? 1 : per_cu) * c->compute_units;
     }
     const slam_opt_params* prm = sl.prm;
     LongArgs a{};
@@ -426,13 +488,14 @@ int launch_minimize_long(slam_ctx* c, const StageLaunch& sl, int k) {
     a.trace_x = c->trace_cap > 0 ? c->trace_x.as<double>() : nullptr;
     { int rc = stage_gates(c, k, sl.gate_seq, &a.gates); if (rc) return rc; }
     int64_t blocks = sl.n_items_max;  // one item per wavefront at a time
-    if (blocks > c->resident_waves_long) blocks = c->resident_waves_long;
+    if (blocks > resident) blocks = resident;
     if (blocks < 1) blocks = 1;
     // (sized for the whole grid and the longest template once: growing it between two stages of a chain would free it under the stage in flight)
-    HIP_TRY(c->long_hmem.reserve((size_t)c->resident_waves_long * (size_t)(6 * (SLAM_MAX_SPAN_MINIMIZE + 1)) * kLongHStride * sizeof(float)));
+    HIP_TRY(c->long_hmem.reserve((size_t)resident * (size_t)(6 * (SLAM_MAX_SPAN_MINIMIZE + 1)) * kLongHStride * sizeof(float)));
     a.hmem = c->long_hmem.as<float>();
     HIP_TRY(hipEventRecord(c->ev_a[k], c->stream));
-    hipLaunchKernelGGL(minimize_long_kernel, dim3((unsigned)blocks), dim3(kWave), kLongLdsBytes, c->stream, a);
+    if (mk) hipLaunchKernelGGL(minimize_long_mk_kernel, dim3((unsigned)blocks), dim3(kWave), kLongLdsBytes, c->stream, a);
+    else hipLaunchKernelGGL(minimize_long_kernel, dim3((unsigned)blocks), dim3(kWave), kLongLdsBytes, c->stream, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev_b[k], c->stream));
     return SLAM_OK;
@@ -440,9 +503,12 @@ int launch_minimize_long(slam_ctx* c, const StageLaunch& sl, int k) {
 
 int launch_eval_long(slam_ctx* c, int k, const int32_t* gate_seq, const double* d_x, const int32_t* d_tof, int64_t M, double* d_loss, double* d_grad,
                      double* d_unitary) {
-    if (!c->long_eval_ready) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes));
-        c->long_eval_ready = true;
+    const bool mk = c->cost_kind == SLAM_COST_MAKHLIN;
+    bool& ready = mk ? c->long_eval_mk_ready : c->long_eval_ready;
+    if (!ready) {
+        HIP_TRY(hipFuncSetAttribute(mk ? reinterpret_cast<const void*>(&eval_long_mk_kernel) : reinterpret_cast<const void*>(&eval_long_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes));
+        ready = true;
     }
     LongEvalArgs a{};
     a.targets = c->targets.as<double>();
@@ -458,7 +524,8 @@ int launch_eval_long(slam_ctx* c, int k, const int32_t* gate_seq, const double* 
     int64_t blocks = M;
     const int64_t cap = (int64_t)8 * c->compute_units;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(eval_long_kernel, dim3((unsigned)blocks), dim3(kWave), kLongLdsBytes, c->stream, a);
+    if (mk) hipLaunchKernelGGL(eval_long_mk_kernel, dim3((unsigned)blocks), dim3(kWave), kLongLdsBytes, c->stream, a);
+    else hipLaunchKernelGGL(eval_long_kernel, dim3((unsigned)blocks), dim3(kWave), kLongLdsBytes, c->stream, a);
     HIP_TRY(hipGetLastError());
     return SLAM_OK;
 }
@@ -573,7 +640,8 @@ int enqueue_stage(slam_ctx* c, int k, const int32_t* gate_seq, const int32_t* d_
     const int gc = classify_gates(c, k, gate_seq);
 #define SLAM_MIN_CASE(KK)                                                   \
     case KK:                                                                \
-        if (gc == GC_CX) rc = launch_minimize<KK, GC_CX>(c, sl);            \
+        if (c->cost_kind == SLAM_COST_MAKHLIN) rc = launch_minimize_mk<KK>(c, sl); \
+        else if (gc == GC_CX) rc = launch_minimize<KK, GC_CX>(c, sl);       \
         else if (gc == GC_XRI1) rc = launch_minimize<KK, GC_XRI1>(c, sl);   \
         else if (gc == GC_XRI) rc = launch_minimize<KK, GC_XRI>(c, sl);     \
         else if (gc == GC_XGEN) rc = launch_minimize<KK, GC_XGEN>(c, sl);   \
@@ -758,6 +826,7 @@ bool overlap_eligible(const slam_ctx* c, int64_t count, int k_min, int k_max, co
     static const bool env_staged = std::getenv("SLAM_STAGED") != nullptr;
     static const bool env_off = []{ const char* e = std::getenv("SLAM_OVERLAP"); return e && e[0] == '0'; }();
     if ((prm->flags & SLAM_FLAG_STAGED) || env_staged || env_off) return false;
+    if (c->cost_kind == SLAM_COST_MAKHLIN) return false;  // (per-span launches only: no MakhlinFunctionalCost instantiation of the side-by-side spans)
     if (!(prm->flags & SLAM_FLAG_EARLY_EXIT) || !(prm->flags & SLAM_FLAG_ORDERED)) return false;
     if (k_max <= k_min || k_max > 3 || c->trace_cap > 0) return false;
     if (prm->flags & SLAM_FLAG_OVERLAP) return true;
@@ -769,6 +838,7 @@ int decompose_wave_loop(slam_ctx* c, int64_t first, int64_t count, int k_min, in
                         double success_threshold, FetchReq* fetch, bool* taken) {
     *taken = false;
     if (prm->flags & SLAM_FLAG_STAGED) return SLAM_OK;
+    if (c->cost_kind == SLAM_COST_MAKHLIN) return SLAM_OK;  // (no wave-loop instantiation for MakhlinFunctionalCost: the per-span launches)
     static const bool env_staged = std::getenv("SLAM_STAGED") != nullptr;  // (test runs: the whole suite through the per-span launches)
     static const bool env_no_wave = []{ const char* e = std::getenv("SLAM_WAVE_LOOP"); return e && e[0] == '0'; }();  // (A/B runs)
     if (env_staged || env_no_wave) return SLAM_OK;
@@ -1227,6 +1297,8 @@ int decompose_multi_body(slam_ctx** cs, int n, int64_t first, int64_t count, int
             return fail(SLAM_ERR_INVALID, "ctxs[%d]: target window [%lld, %lld) outside [0, %lld)", i, (long long)first, (long long)(first + count), (long long)cs[i]->n_targets);
         if (cs[i]->cost_kind != lead->cost_kind) return fail(SLAM_ERR_INVALID, "ctxs[%d]: another cost function than ctxs[0]", i);
     }
+    if (lead->cost_kind == SLAM_COST_MAKHLIN)
+        return fail(SLAM_ERR_UNSUPPORTED, "slam_decompose_multi does not run MakhlinFunctionalCost (SLAM_COST_MAKHLIN): call slam_decompose_range per context");
     HIP_TRY(hipSetDevice(lead->device));
     if (k_min < 1 || k_max < k_min) return fail(SLAM_ERR_INVALID, "bad span range [%d, %d]", k_min, k_max);
     if (k_max > 3) return fail(SLAM_ERR_UNSUPPORTED, "slam_decompose_multi runs spans 1..3 (got k_max = %d)", k_max);
@@ -1537,7 +1609,8 @@ static int eval_body(slam_ctx* ctx, int k, const int32_t* gate_seq, const double
     const int gc = classify_gates(ctx, k, gate_seq);
 #define SLAM_EVAL_CASE(KK)                                                                                  \
     case KK:                                                                                                \
-        if (gc == GC_CX) rc = launch_eval<KK, GC_CX>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);   \
+        if (ctx->cost_kind == SLAM_COST_MAKHLIN) rc = launch_eval_mk<KK>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); \
+        else if (gc == GC_CX) rc = launch_eval<KK, GC_CX>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);   \
         else if (gc == GC_XRI1) rc = launch_eval<KK, GC_XRI1>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); \
         else if (gc == GC_XRI) rc = launch_eval<KK, GC_XRI>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); \
         else if (gc == GC_XGEN) rc = launch_eval<KK, GC_XGEN>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); \
@@ -1550,7 +1623,8 @@ static int eval_body(slam_ctx* ctx, int k, const int32_t* gate_seq, const double
         SLAM_EVAL_CASE(4)
         default:
             if (k > SLAM_MAX_SPAN_QUAD) { rc = launch_eval_long(ctx, k, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break; }
-            if (gc == GC_CX) rc = launch_eval<5, GC_CX>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
+            if (ctx->cost_kind == SLAM_COST_MAKHLIN) rc = launch_eval_mk<5>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
+            else if (gc == GC_CX) rc = launch_eval<5, GC_CX>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
             else if (gc == GC_XRI1) rc = launch_eval<5, GC_XRI1>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
             else if (gc == GC_XRI) rc = launch_eval<5, GC_XRI>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
             else if (gc == GC_XGEN) rc = launch_eval<5, GC_XGEN>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
@@ -1971,7 +2045,7 @@ int slam_minimize_stage_trace(slam_ctx* ctx, int k, const int32_t* gate_seq, con
 
 int slam_set_cost(slam_ctx* ctx, int cost) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (cost != SLAM_COST_BASIC && cost != SLAM_COST_SQUARE)
+    if (cost != SLAM_COST_BASIC && cost != SLAM_COST_SQUARE && cost != SLAM_COST_MAKHLIN)
         return fail(SLAM_ERR_INVALID, "Unrecognized Cost Function (%d)", cost);
     ctx->cost_kind = cost;
     return SLAM_OK;
@@ -2193,6 +2267,8 @@ int v2_launch_minimize(slam_ctx* c, const V2Stage& sgt) {
 int v2_eval_body(slam_ctx* c, int k, const int32_t* gate_seq, const double* x, const int32_t* target_of, int64_t M, double* loss,
                  double* grad, double* unitary) {
     if (!c) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (c->cost_kind == SLAM_COST_MAKHLIN)
+        return fail(SLAM_ERR_UNSUPPORTED, "parametrised-gate templates do not run MakhlinFunctionalCost (SLAM_COST_MAKHLIN)");
     HIP_TRY(hipSetDevice(c->device));
     if (c->n_targets <= 0) return fail(SLAM_ERR_STATE, "no targets: call slam_set_targets first");
     if (k < 1 || k > SLAM_V2_MAX_SPAN) return fail(SLAM_ERR_UNSUPPORTED, "parametrised-gate templates support spans 1..%d (got %d)", SLAM_V2_MAX_SPAN, k);
@@ -2228,6 +2304,8 @@ int v2_minimize_body(slam_ctx* c, int k, const int32_t* gate_seq, const int32_t*
                      const slam_opt_params* prm, double exit_loss, double* best_loss, double* best_x, int32_t* best_restart,
                      double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals) {
     if (!c) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (c->cost_kind == SLAM_COST_MAKHLIN)
+        return fail(SLAM_ERR_UNSUPPORTED, "parametrised-gate templates do not run MakhlinFunctionalCost (SLAM_COST_MAKHLIN)");
     HIP_TRY(hipSetDevice(c->device));
     if (c->n_targets <= 0) return fail(SLAM_ERR_STATE, "no targets: call slam_set_targets first");
     if (k < 1 || k > SLAM_V2_MAX_SPAN) return fail(SLAM_ERR_UNSUPPORTED, "parametrised-gate templates support spans 1..%d (got %d)", SLAM_V2_MAX_SPAN, k);
@@ -2324,6 +2402,8 @@ int v2_decompose_body(slam_ctx* c, int64_t first, int64_t count, int k_min, int 
                       const double* init_hi, const double* bound_lo, const double* bound_hi, const slam_opt_params* prm,
                       double success_threshold, FetchReq* fetch) {
     if (!c) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (c->cost_kind == SLAM_COST_MAKHLIN)
+        return fail(SLAM_ERR_UNSUPPORTED, "parametrised-gate templates do not run MakhlinFunctionalCost (SLAM_COST_MAKHLIN)");
     HIP_TRY(hipSetDevice(c->device));
     if (c->n_targets <= 0) return fail(SLAM_ERR_STATE, "no targets: call slam_set_targets first");
     if (c->v2_gates_host.empty()) return fail(SLAM_ERR_STATE, "no parametrised gates: call slam_v2_set_gates first");

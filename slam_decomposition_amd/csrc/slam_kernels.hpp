@@ -128,8 +128,8 @@ struct EvalArgs {
 // ---------------------------------------------------------------------------------
 // loss + gradient (+ template unitary) for explicit parameter vectors
 // ---------------------------------------------------------------------------------
-template <int K, int GC>
-__global__ void __launch_bounds__(kWave) eval_kernel(EvalArgs<K> args) {
+template <int K, int GC, bool MK>
+__device__ __forceinline__ void eval_body(const EvalArgs<K>& args) {
     using C = Cfg<K, psq_layout<K, GC>()>;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* xchg = lds;
@@ -152,7 +152,14 @@ __global__ void __launch_bounds__(kWave) eval_kernel(EvalArgs<K> args) {
         xd[a] = (i < C::N) ? args.x[it * C::N + i] : 0.0;
     }
     double f, Wr[4], Wi[4];
-    eval_quad<K, true, GC>(xd, tcol, args.gates, xchg + quad * C::XSTRIDE, fhbase + lane, tbl, q, theta_slot_bits<K>(q), args.cost_kind, f, gd, Wr, Wi);
+    if constexpr (MK) {
+        double gT[3];
+        mk_target_g(tcol, q, gT);
+        eval_quad<K, true, GC, true>(xd, tcol, args.gates, xchg + quad * C::XSTRIDE, fhbase + lane, tbl, q, theta_slot_bits<K>(q), args.cost_kind, f, gd,
+                                     Wr, Wi, gT);
+    } else {
+        eval_quad<K, true, GC>(xd, tcol, args.gates, xchg + quad * C::XSTRIDE, fhbase + lane, tbl, q, theta_slot_bits<K>(q), args.cost_kind, f, gd, Wr, Wi);
+    }
     if (live) {
         if (q == 0) args.loss[item] = f;
         if (args.unitary) {
@@ -170,6 +177,15 @@ __global__ void __launch_bounds__(kWave) eval_kernel(EvalArgs<K> args) {
             }
         }
     }
+}
+template <int K, int GC>
+__global__ void __launch_bounds__(kWave) eval_kernel(EvalArgs<K> args) {
+    eval_body<K, GC, false>(args);
+}
+// MakhlinFunctionalCost (SLAM_COST_MAKHLIN): dense gate class only
+template <int K>
+__global__ void __launch_bounds__(kWave) eval_mk_kernel(EvalArgs<K> args) {
+    eval_body<K, GC_DENSE, true>(args);
 }
 
 // Kernel arguments that are only needed when an item starts or finishes (result pointers, seeds, the work queue) are
@@ -225,9 +241,12 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
     return __hiloint2double(hi, lo);
 }
 
-template <int K, int GC, bool MQ, bool WL>
+// MK: MakhlinFunctionalCost (args.cost_kind is not looked at); the target's invariants g(T) are computed once per item, when its quad
+// takes it, and kept in registers for the item's life
+template <int K, int GC, bool MQ, bool WL, bool MK = false>
 __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const MinimizeArgs<K>* subs, int n_sub, WlStage& wl) {
     static_assert(!WL || MQ, "the wave-local stage reads its argument block from device memory");
+    static_assert(!MK || (!MQ && GC == GC_DENSE), "MakhlinFunctionalCost: per-span launches of the dense gate class only");
     using C = Cfg<K, psq_layout<K, GC>()>;
     constexpr int NA = C::NA;
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -305,6 +324,7 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
     for (int a = 0; a < NA; ++a) { x[a] = 0.0; g[a] = 0.0; p[a] = 0.0; }
     HMat<NA> H;
     h_set_identity_where<NA>(H, q, true);
+    double mkt[3] = {0.0, 0.0, 0.0};  // MK: g(T) of the quad's item
     bool exhausted = false;  // wave-uniform
     const unsigned kChunk = kChunkV;  // wave-uniform: 16 (small batches: spread over all waves) .. 64
     unsigned cur_next = 0, cur_end = WL ? n_items : 0u;  // wave-uniform (WL: the whole restart range is this wavefront's chunk)
@@ -541,6 +561,14 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
                 }
             }
             if (__any(taken)) h_set_identity_where<NA>(H, q, taken);
+            if constexpr (MK) {
+                if (__any(taken)) {  // (all lanes: the quad exchanges; tcol is a valid column for idle quads too)
+                    double g3[3];
+                    mk_target_g(tcol, q, g3);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) mkt[i] = taken ? g3[i] : mkt[i];
+                }
+            }
         }
         if (!__any(live)) {
             if constexpr (MQ && !WL) continue;  // (nothing is live, hence nothing loop-carried to copy: the next sub-problem, or out)
@@ -568,8 +596,12 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
             double xt[NA];
 #pragma unroll
             for (int a = 0; a < NA; ++a) xt[a] = fma(alpha, p[a], x[a]);
-            eval_quad<K, false, GC>(xt, tcol, MQ ? cold_args<K, MQ>(cur)->gates : args.gates, xq, fh, tbl, q, theta_bits,
-                                    WL ? __builtin_amdgcn_readfirstlane(args.cost_kind) : args.cost_kind, ft, gt, Wr, Wi);
+            if constexpr (MK) {
+                eval_quad<K, false, GC, true>(xt, tcol, args.gates, xq, fh, tbl, q, theta_bits, 0, ft, gt, Wr, Wi, mkt);
+            } else {
+                eval_quad<K, false, GC>(xt, tcol, MQ ? cold_args<K, MQ>(cur)->gates : args.gates, xq, fh, tbl, q, theta_bits,
+                                        WL ? __builtin_amdgcn_readfirstlane(args.cost_kind) : args.cost_kind, ft, gt, Wr, Wi);
+            }
         }
         const bool active = live;
         const bool finite = isfinite(ft);
@@ -801,6 +833,12 @@ template <int K, int GC, bool MQ = false>
 __global__ void __launch_bounds__(kWave, (K <= 2 ? 2 : 1)) minimize_kernel(MinimizeArgs<K> args, const MinimizeArgs<K>* subs, int n_sub) {
     WlStage none{};
     minimize_body<K, GC, MQ, false>(args, subs, n_sub, none);
+}
+// MakhlinFunctionalCost (SLAM_COST_MAKHLIN): per-span launches, dense gate class
+template <int K>
+__global__ void __launch_bounds__(kWave, (K <= 2 ? 2 : 1)) minimize_mk_kernel(MinimizeArgs<K> args) {
+    WlStage none{};
+    minimize_body<K, GC_DENSE, false, false, true>(args, nullptr, 0, none);
 }
 
 // ---------------------------------------------------------------------------------

@@ -28,7 +28,7 @@ from . import _ffi, runtime
 from .basis import CircuitTemplate
 from .basisv2 import CircuitTemplateV2
 from .basis_abc import DataDictEntry, LazyList, RowBlocks, TargetDataList, VariationalTemplate
-from .cost_function import BasicCost, SquareCost, UnitaryCostFunction
+from .cost_function import BasicCost, MakhlinFunctionalCost, SquareCost, UnitaryCostFunction
 from .sampler import SampleFunction
 
 SUCCESS_THRESHOLD = 1e-10  # optimizer.py:18
@@ -83,6 +83,11 @@ class TemplateOptimizer:
             self._cost_kind = _ffi.COST_SQUARE
         elif isinstance(self.objective, BasicCost):
             self._cost_kind = _ffi.COST_BASIC
+        elif isinstance(self.objective, MakhlinFunctionalCost):
+            self._cost_kind = _ffi.COST_MAKHLIN
+            if self._v2:
+                raise NotImplementedError("MakhlinFunctionalCost is implemented for fixed-gate templates (CircuitTemplate, "
+                                          "MixedOrderBasisCircuitTemplate), not for CircuitTemplateV2")
         else:
             # the reference raises this for objectives its objective_func does not know (optimizer.py:211)
             raise ValueError("Unrecognized Cost Function")

@@ -12,6 +12,19 @@ _YY = np.kron(_SY, _SY)
 _M = np.array([[1, 1, 0], [1, 0, 1], [0, 1, 1]])
 
 
+def g1g2g3(U):
+    """Makhlin's local invariants (g1, g2, g3) = (Re G1, Im G1, Re G2) of a two-qubit unitary, unrounded:
+    M = U^T Y U Y (Y = sigma_y (x) sigma_y), G1 = tr(M)^2 / (16 det U), G2 = (tr(M)^2 - tr(M^2)) / (4 det U) -- the
+    magic-basis form of weylchamber.g1g2g3 without the basis change (Q Q^T = -Y)."""
+    U = np.asarray(U, dtype=np.complex128)
+    M = U.T @ _YY @ U @ _YY
+    d = complex(np.linalg.det(U))
+    t = complex(np.trace(M))
+    G1 = t * t / (16 * d)
+    G2 = (t * t - complex(np.trace(M @ M))) / (4 * d)
+    return (float(G1.real), float(G1.imag), float(G2.real))
+
+
 def c1c2c3(U, ndigits: int = 8):
     """(c1, c2, c3) in units of pi, rounded to ``ndigits`` like weylchamber does."""
     U = np.asarray(U, dtype=np.complex128)
