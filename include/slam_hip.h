@@ -193,6 +193,27 @@ int slam_predict_spans(slam_ctx* ctx, int64_t first, int64_t count, int k_max, c
                        int32_t* spans_out);
 
 /*
+ * Coverage lookup on the device: for every resident target of [first, first + count) the first entry of a cost-ordered coverage set
+ * whose region contains the target -- the lookup MixedOrderBasisCircuitTemplate makes (src/slam/basis.py:321-326 ->
+ * monodromy_range_from_target, src/slam/utils/polytopes/polytope_wrap.py:39-94) for TemplateOptimizer.cost_target_U /
+ * cost_from_distribution (src/slam/optimizer.py:156-178).  No optimisation.  Several coverage sets ("tables") are looked up in one
+ * call; table t holds entries [table_offsets[t], table_offsets[t + 1]) of one concatenated entry array of E = table_offsets[n_tables]
+ * rows, in cost order:
+ *   table_offsets  int32[n_tables + 1]  table_offsets[0] = 0, non-decreasing
+ *   kinds          int32[E]             0: one gate (the target must be in its class); 1: a circuit of two or more gates
+ *   points         double[E][4]         kind 0: the gate's alcove point (|a_j - point_j| <= max(tol, 0) + 1e-12)
+ *   bounds         double[E][14]        kind 1: bounds[p] - tol <= sum of the target's alcove coordinates over the p-th subset (the
+ *                                       order of slam_predict_spans); -inf = no constraint (all -inf: every target)
+ *   tol                                 widens the regions (units of pi)
+ * counts_out  int64[E + 2 n_tables]: per table, n_entries + 2 counts -- targets whose first containing entry is entry e (e = 0 ..
+ *             n_entries - 1), then local targets, then targets no entry contains.
+ * entry_out   int32[n_tables][count] or NULL: per table and target, the same bin index (n_entries = local, n_entries + 1 = none).
+ * Integer counts: the result does not depend on the order in which the device adds them up.
+ */
+int slam_coverage_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_tables, const int32_t* table_offsets, const int32_t* kinds,
+                         const double* points, const double* bounds, double tol, int64_t* counts_out, int32_t* entry_out);
+
+/*
  * Upload the table of 2Q basis-gate matrices (CircuitTemplate(base_gates=...),
  * src/slam/basis.py:52-69; matrices from src/slam/utils/gates/custom_gates.py).
  * gates: double[n_gates][4][4][2].
@@ -517,7 +538,8 @@ const char* slam_version(void);
  *   5  round 4: slam_decompose_multi, slam_predict_spans, 32-byte item records;
  *   6  round 5: SLAM_MAX_SPAN_EVAL / SLAM_MAX_SPAN_MINIMIZE 5 -> 16 -- the per-span arrays of slam_stats and the rows of
  *      slam_fetch_span_losses grow with them --, SLAM_FLAG_NO_EXTERIOR, kernel_ms_span[0];
- *   7  round 5: slam_host_alloc / slam_host_free (new symbols only).
+ *   7  round 5: slam_host_alloc / slam_host_free (new symbols only);
+ *      later: slam_coverage_lookup (a new symbol only; no signature or structure changed).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

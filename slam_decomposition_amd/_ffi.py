@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "slam_c1c2c3",
     "slam_targets_c1c2c3",
     "slam_predict_spans",
+    "slam_coverage_lookup",
     "slam_eval_c1c2c3",
     "slam_sample_haar",
     "slam_get_targets",
@@ -180,6 +181,8 @@ def load_library() -> C.CDLL:
     lib.slam_c1c2c3.argtypes = [P, P, C.c_int64, C.c_int32, P]
     lib.slam_targets_c1c2c3.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P]
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
+    if hasattr(lib, "slam_coverage_lookup"):
+        lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
     lib.slam_eval_c1c2c3.argtypes = [P, C.c_int32, P, P, C.c_int64, C.c_int32, P]
     lib.slam_sample_haar.argtypes = [P, C.c_uint64, C.c_int64, C.c_int64]
     lib.slam_get_targets.argtypes = [P, C.c_int64, C.c_int64, P]
@@ -426,6 +429,31 @@ class Context:
         out = np.zeros(count, dtype=np.int32)
         _check(self._lib.slam_predict_spans(self._h, int(first), int(count), int(k_max), _ptr(point), _ptr(bounds), float(tol), _ptr(out)))
         return out
+
+    def coverage_lookup(self, tables, first: int = 0, count: Optional[int] = None, want_entries: bool = False, tol: float = 1e-7):
+        """First entry of each cost-ordered coverage table that contains each resident target of [first, first + count)
+        (slam_coverage_lookup; the targets and their Weyl coordinates stay on the device).  ``tables``: objects with ``kinds``
+        (int32 [n]: 0 one gate, 1 half-spaces), ``points`` ([n, 4]) and ``bounds`` ([n, 14]) -- ``basis.CoverageTable``, as
+        ``MixedOrderBasisCircuitTemplate.coverage_table`` builds them; ``tol`` is the widening ``CircuitCoverage.inside`` applies
+        (``span_rules._TOL`` + its default slack).  Returns ``(counts, entries)``: per table int64 [n + 2] (hits per entry, then local
+        targets, then targets no entry contains) and -- with ``want_entries`` -- int32 [n_tables, count] of those bin indices (else
+        None), all tables in ONE launch."""
+        tables = list(tables)
+        if not tables:
+            raise ValueError("coverage_lookup needs at least one table")
+        count = self.n_targets - first if count is None else int(count)
+        sizes = [len(np.asarray(t.kinds)) for t in tables]
+        offsets = np.zeros(len(tables) + 1, dtype=np.int32)
+        offsets[1:] = np.cumsum(sizes)
+        kinds = np.ascontiguousarray(np.concatenate([np.asarray(t.kinds, dtype=np.int32).reshape(-1) for t in tables]))
+        points = np.ascontiguousarray(np.concatenate([np.asarray(t.points, dtype=np.float64).reshape(-1, 4) for t in tables]))
+        bounds = np.ascontiguousarray(np.concatenate([np.asarray(t.bounds, dtype=np.float64).reshape(-1, 14) for t in tables]))
+        counts = np.zeros(int(offsets[-1]) + 2 * len(tables), dtype=np.int64)
+        entries = np.zeros((len(tables), max(count, 0)), dtype=np.int32) if want_entries else None
+        _check(self._lib.slam_coverage_lookup(self._h, int(first), int(count), len(tables), _ptr(offsets), _ptr(kinds), _ptr(points),
+                                              _ptr(bounds), float(tol), _ptr(counts), _ptr(entries)))
+        per_table = [counts[int(offsets[t]) + 2 * t : int(offsets[t + 1]) + 2 * (t + 1)] for t in range(len(tables))]
+        return per_table, entries
 
     def eval_c1c2c3(self, gate_seq: Sequence[int], x: np.ndarray, ndigits: int = 8) -> np.ndarray:
         """Weyl coordinates of CircuitTemplate.eval(x[m]) for ``x[M, n]`` (optimizer.py:85,103) -> float64[M, 3];

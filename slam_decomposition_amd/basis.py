@@ -253,6 +253,32 @@ class CircuitCoverage:
         return bool(self.inside(target_coords)[0][0])
 
 
+class CoverageTable:
+    """A coverage set as the device's lookup reads it (``_ffi.Context.coverage_lookup`` -> slam_coverage_lookup), one row per entry in
+    cost order: ``kinds`` int32 [n] (0: one gate, 1: two or more), ``points`` [n, 4] (kind 0: the gate's alcove point), ``bounds``
+    [n, 14] (kind 1: ``coverage.region`` of the entry's gates; all -inf where the entry reaches every target), ``costs`` [n] and the
+    ``entries`` themselves."""
+
+    def __init__(self, entries):
+        from . import coverage
+
+        self.entries = list(entries)
+        n = len(self.entries)
+        self.kinds = np.ones(n, dtype=np.int32)
+        self.points = np.zeros((n, 4))
+        self.bounds = np.full((n, len(coverage._PATTERNS)), -np.inf)
+        self.costs = np.array([float(e.cost) for e in self.entries], dtype=np.float64)
+        for j, e in enumerate(self.entries):
+            if len(e) == 1:
+                self.kinds[j] = 0
+                self.points[j] = coverage.alcove_coordinates(e.gate_coords)[0]
+            elif not span_rules._reaches_everything(e.gate_coords):
+                self.bounds[j] = coverage.region(e.gate_coords)
+
+    def __len__(self):
+        return len(self.entries)
+
+
 class MixedOrderBasisCircuitTemplate(CircuitTemplate):
     """Templates over a SET of basis gates in which every target gets the cheapest circuit that reaches it (reference:
     src/slam/basis.py:213-359 with ``monodromy_range_from_target``, src/slam/utils/polytopes/polytope_wrap.py:39-94: the coverage set
@@ -319,6 +345,14 @@ class MixedOrderBasisCircuitTemplate(CircuitTemplate):
         self.circuit_polytope = None
         self.cost = None
         self._span_exact = all(e.exact for e in entries)
+        self._coverage_table = None
+
+    def coverage_table(self) -> CoverageTable:
+        """``self.coverage`` as rows for the device lookup (built on first use and kept: the regions of a 26-gate set of three gates
+        are 3 653 dynamic programmes)."""
+        if self._coverage_table is None:
+            self._coverage_table = CoverageTable(self.coverage)
+        return self._coverage_table
 
     # ---- the bound entry ------------------------------------------------------------------------
     def set_polytope(self, circuit_polytope):

@@ -132,6 +132,7 @@ struct slam_ctx {
     int64_t resident_waves[SLAM_MAX_SPAN_EVAL + 1][kGateClasses] = {};
     // eval buffers
     DevBuf ev_x, ev_tof, ev_loss, ev_grad, ev_unitary, ev_weyl;
+    DevBuf cov_table, cov_counts, cov_entries;  // slam_coverage_lookup: offsets / kinds / points / bounds, counts, entry per target
     slam_stats stats{};
     bool max_lds_set[SLAM_MAX_SPAN_EVAL + 1][kGateClasses][3] = {};  // [.][.][0] eval kernel, [1] optimizer kernel, [2] its multi-queue form
     int64_t resident_waves_mq[SLAM_MAX_SPAN_EVAL + 1][kGateClasses] = {};
@@ -181,6 +182,9 @@ struct slam_ctx {
         spec_x.release();
         spec_ev.release();
         slot_ev.release();
+        cov_table.release();
+        cov_counts.release();
+        cov_entries.release();
         if (ov_fork) (void)hipEventDestroy(ov_fork);
         for (hipEvent_t e : ov_join) if (e) (void)hipEventDestroy(e);
         for (slam_ctx* h : helper) {
@@ -1957,6 +1961,64 @@ int slam_predict_spans(slam_ctx* ctx, int64_t first, int64_t count, int k_max, c
                        ctx->targets.as<double>() + first * 32, count, r, ctx->ev_weyl.as<int32_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(spans_out, ctx->ev_weyl.p, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+int slam_coverage_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_tables, const int32_t* table_offsets, const int32_t* kinds,
+                         const double* points, const double* bounds, double tol, int64_t* counts_out, int32_t* entry_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (n_tables < 1) return fail(SLAM_ERR_INVALID, "n_tables must be >= 1 (got %d)", n_tables);
+    if (!table_offsets) return fail(SLAM_ERR_INVALID, "table_offsets is NULL");
+    if (table_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "table_offsets[0] must be 0 (got %d)", table_offsets[0]);
+    int32_t max_bins = 0;
+    for (int32_t t = 0; t < n_tables; ++t) {
+        if (table_offsets[t + 1] < table_offsets[t])
+            return fail(SLAM_ERR_INVALID, "table_offsets must be non-decreasing (offsets[%d] = %d > offsets[%d] = %d)", t, table_offsets[t],
+                        t + 1, table_offsets[t + 1]);
+        if (table_offsets[t + 1] > 0x3fffffff) return fail(SLAM_ERR_INVALID, "too many coverage entries");
+        const int32_t nb = table_offsets[t + 1] - table_offsets[t] + 2;
+        if (nb > max_bins) max_bins = nb;
+    }
+    const int64_t E = table_offsets[n_tables];
+    if (E > 0 && (!kinds || !points || !bounds)) return fail(SLAM_ERR_INVALID, "kinds / points / bounds is NULL");
+    for (int64_t e = 0; e < E; ++e)
+        if (kinds[e] != 0 && kinds[e] != 1) return fail(SLAM_ERR_INVALID, "kinds[%lld] = %d (0 = one gate, 1 = half-spaces)", (long long)e, kinds[e]);
+    if (!counts_out) return fail(SLAM_ERR_INVALID, "counts_out is NULL");
+    const int64_t n_counts = E + 2 * (int64_t)n_tables;
+    std::memset(counts_out, 0, (size_t)n_counts * sizeof(int64_t));
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one upload: offsets, kinds (int32), then points [E][4] and bounds [E][14] (doubles, 8-byte aligned)
+    const size_t off_b = 0, kind_b = (size_t)(n_tables + 1) * sizeof(int32_t);
+    const size_t pt_b = ((kind_b + (size_t)E * sizeof(int32_t)) + 7) & ~(size_t)7;
+    const size_t bd_b = pt_b + (size_t)E * 4 * sizeof(double);
+    const size_t total_b = bd_b + (size_t)E * kSpanPatterns * sizeof(double);
+    HIP_TRY(ctx->cov_table.reserve(total_b));
+    HIP_TRY(ctx->cov_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
+    if (entry_out) HIP_TRY(ctx->cov_entries.reserve((size_t)n_tables * (size_t)count * sizeof(int32_t)));
+    char* tb = ctx->cov_table.as<char>();
+    HIP_TRY(hipMemcpyAsync(tb + off_b, table_offsets, kind_b, hipMemcpyHostToDevice, ctx->stream));
+    if (E > 0) {
+        HIP_TRY(hipMemcpyAsync(tb + kind_b, kinds, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(tb + pt_b, points, (size_t)E * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(tb + bd_b, bounds, (size_t)E * kSpanPatterns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipMemsetAsync(ctx->cov_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
+    const int32_t lds_bins = max_bins < kCoverageLdsBins ? max_bins : kCoverageLdsBins;
+    hipLaunchKernelGGL(coverage_lookup_kernel, dim3((unsigned)((count + kCoverageBlock - 1) / kCoverageBlock)), dim3(kCoverageBlock),
+                       (size_t)lds_bins * sizeof(unsigned int), ctx->stream, ctx->targets.as<double>() + first * 32, count, n_tables,
+                       reinterpret_cast<const int32_t*>(tb + off_b), reinterpret_cast<const int32_t*>(tb + kind_b),
+                       reinterpret_cast<const double*>(tb + pt_b), reinterpret_cast<const double*>(tb + bd_b), tol, lds_bins,
+                       ctx->cov_counts.as<unsigned long long>(), entry_out ? ctx->cov_entries.as<int32_t>() : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counts_out, ctx->cov_counts.p, (size_t)n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (entry_out)
+        HIP_TRY(hipMemcpyAsync(entry_out, ctx->cov_entries.p, (size_t)n_tables * (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost,
+                               ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return SLAM_OK;
 }

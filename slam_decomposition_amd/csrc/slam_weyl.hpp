@@ -218,4 +218,117 @@ __global__ void span_predict_kernel(const double* __restrict__ U, int64_t M, Spa
     spans[i] = local ? 0 : best;
 }
 
+// ---------------------------------------------------------------------------------
+// Coverage lookup (the cost side of MixedOrderBasisCircuitTemplate: monodromy_range_from_target over a coverage set sorted by cost,
+// src/slam/utils/polytopes/polytope_wrap.py:39-94, as TemplateOptimizer.cost_from_distribution asks it, src/slam/optimizer.py:156-178):
+// for every resident target, the first entry of a cost-ordered table whose region contains it.  Entries are rows of device memory:
+//   kind 0  one gate: the target's class is the gate's -- |a_j - point_j| <= max(tol, 0) + 1e-12 for one of the two alcove points
+//   kind 1  a circuit of two or more gates: bounds[p] - tol <= sum_p(gamma) for all 14 subsets (-inf: no constraint)
+// -- coverage.contains with the tolerance CircuitCoverage.inside passes.  Several tables (one per gate set) follow each other in one
+// entry array (offsets[n_tables + 1]); the Weyl coordinates and the 2 x 14 sums are computed once per target for all of them.
+// One thread per target.  The entry index is wave-uniform: every lane of the wavefront looks at the same row (scalar loads), lanes
+// that have found their entry idle, and the wavefront leaves the walk when none is still searching.  Per table the block keeps a
+// histogram in LDS (bins n_entries + 2: the entries, then local targets, then targets no entry contains) and folds its non-empty
+// bins into `counts` with one 64-bit atomic each; bins beyond the LDS histogram's size go to `counts` directly.
+// ---------------------------------------------------------------------------------
+constexpr int kCoverageBlock = 256;
+// the table is read-only for the whole launch: read through the constant address space, whose loads at a wave-uniform address the
+// compiler issues as scalar loads (a plain global pointer gets vector loads of the same row in every lane)
+template <class T>
+using const_as_ptr = const __attribute__((address_space(4))) T*;
+constexpr int kCoverageLdsBins = 8192;  // 32 KiB of LDS at most: a 26-gate set of three gates (3 653 entries) fits
+
+__global__ __launch_bounds__(kCoverageBlock) void coverage_lookup_kernel(
+    const double* __restrict__ U, int64_t M, int32_t n_tables, const int32_t* __restrict__ offsets, const int32_t* __restrict__ kinds,
+    const double* __restrict__ points, const double* __restrict__ bounds, double tol, int32_t lds_bins,
+    unsigned long long* __restrict__ counts, int32_t* __restrict__ entry_out) {
+    extern __shared__ unsigned int hist[];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < M;
+    double pt[2][4], sm[2][kSpanPatterns];
+    bool local = false;
+    if (live) {
+        double c[3];
+        weyl_c1c2c3(U + i * 32, 8, c);
+#pragma unroll
+        for (int sh = 0; sh < 2; ++sh) {
+            double a[4];
+            alcove_point(c[0], c[1], c[2], sh ? 0.5 : 0.0, a);
+            local = local || (fabs(a[0]) <= 1e-8 && fabs(a[3]) <= 1e-8);
+            const double g1 = a[3], g2 = a[2], g3 = a[1], g4 = a[0];  // same order as span_predict_kernel
+            const double s[kSpanPatterns] = {g1, g2, g3, g4, g1 + g2, g1 + g3, g1 + g4, g2 + g3, g2 + g4, g3 + g4,
+                                             g1 + g2 + g3, g1 + g2 + g4, g1 + g3 + g4, g2 + g3 + g4};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pt[sh][j] = a[j];
+#pragma unroll
+            for (int p = 0; p < kSpanPatterns; ++p) sm[sh][p] = s[p];
+        }
+    } else {
+#pragma unroll
+        for (int sh = 0; sh < 2; ++sh) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pt[sh][j] = 0.0;
+#pragma unroll
+            for (int p = 0; p < kSpanPatterns; ++p) sm[sh][p] = 0.0;
+        }
+    }
+    const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
+    const const_as_ptr<int32_t> koffsets = (const_as_ptr<int32_t>)offsets;
+    const const_as_ptr<int32_t> kkinds = (const_as_ptr<int32_t>)kinds;
+    const const_as_ptr<double> kpoints = (const_as_ptr<double>)points;
+    const const_as_ptr<double> kbounds = (const_as_ptr<double>)bounds;
+    const int32_t base0 = koffsets[0];
+    for (int32_t t = 0; t < n_tables; ++t) {
+        const int32_t e0 = koffsets[t], e1 = koffsets[t + 1];
+        const int32_t n = e1 - e0;
+        const int32_t nb = n + 2;
+        const int32_t nl = nb < lds_bins ? nb : lds_bins;
+        unsigned long long* __restrict__ cnt = counts + (int64_t)(e0 - base0) + 2 * (int64_t)t;
+        for (int b = threadIdx.x; b < nl; b += blockDim.x) hist[b] = 0u;
+        __syncthreads();
+        bool searching = live && !local;
+        int32_t found = local ? n : n + 1;
+        for (int32_t e = e0; e < e1; ++e) {
+            if (!__any(searching)) break;  // wave-uniform exit: e is the same in every lane
+            bool hit;
+            if (kkinds[e] == 0) {
+                const const_as_ptr<double> q = kpoints + (int64_t)e * 4;
+                const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+                hit = false;
+#pragma unroll
+                for (int sh = 0; sh < 2; ++sh)
+                    hit = hit || (fabs(pt[sh][0] - q0) <= t1 && fabs(pt[sh][1] - q1) <= t1 && fabs(pt[sh][2] - q2) <= t1 &&
+                                  fabs(pt[sh][3] - q3) <= t1);
+            } else {
+                const const_as_ptr<double> r = kbounds + (int64_t)e * kSpanPatterns;
+                bool ok0 = true, ok1 = true;
+#pragma unroll
+                for (int p = 0; p < kSpanPatterns; ++p) {
+                    const double lo = r[p] - tol;
+                    ok0 = ok0 && (sm[0][p] >= lo);
+                    ok1 = ok1 && (sm[1][p] >= lo);
+                }
+                hit = ok0 || ok1;
+            }
+            if (searching && hit) {
+                found = e - e0;
+                searching = false;
+            }
+        }
+        if (live) {
+            if (entry_out) entry_out[(int64_t)t * M + i] = found;
+            if (found < nl)
+                atomicAdd(&hist[found], 1u);
+            else
+                atomicAdd(&cnt[found], 1ull);
+        }
+        __syncthreads();
+        for (int b = threadIdx.x; b < nl; b += blockDim.x) {
+            const unsigned int v = hist[b];
+            if (v) atomicAdd(&cnt[b], (unsigned long long)v);
+        }
+        __syncthreads();  // the next table clears the histogram
+    }
+}
+
 }  // namespace slamdev

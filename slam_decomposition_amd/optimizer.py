@@ -891,6 +891,51 @@ class TemplateOptimizer:
             self._device_sampler = None
         return self.training_loss, self.coordinate_list, target_data
 
+    # ---- costs without optimisation (optimizer.py:156-178; pulse_cost.py) ---------------------------------------------------------
+    cost_counts = None  # after cost_from_distribution: [(CircuitCoverage, count)] in cost order
+    cost_local_count = None  # ... and the number of local targets (cost 0)
+
+    def cost_target_U(self, target) -> float:
+        """optimizer.py:156-166: the cost of the cheapest coverage entry that contains the target (``basis.unit_cost``), with that
+        entry left bound (``set_polytope``); no parameters are fitted.  A local target costs 0."""
+        from . import pulse_cost, span_rules
+        from .weyl import c1c2c3
+
+        pulse_cost._check_templates([self.basis])
+        t = np.asarray(target, dtype=np.complex128)
+        if t.shape != (4, 4):
+            raise ValueError("targets must be 4x4 unitaries")
+        if np.max(np.abs(span_rules._fold(np.array([c1c2c3(t)])))) < span_rules._TOL:
+            return 0.0
+        try:
+            k = max(self.basis.get_spanning_range(t))
+        except ValueError as e:
+            raise pulse_cost.unreachable_error(self.basis) from e
+        return self.basis.unit_cost(k)
+
+    def cost_from_distribution(self, sampler: SampleFunction) -> float:
+        """optimizer.py:168-178: the total cost of the sampler's targets, with the reference's two log lines.  The lookup runs on
+        ``devices[0]`` (slam_coverage_lookup; a device sampler's targets are generated in place and never come back); the counts per
+        entry are kept as ``cost_counts`` / ``cost_local_count``, and the template is left bound to the last target's entry."""
+        from . import pulse_cost
+
+        counts, n, ctx = pulse_cost.lookup_counts([self.basis], sampler, self.devices[0])
+        counts = counts[0]
+        total_cost = pulse_cost.total_cost(self.basis, counts)
+        entries = self.basis.coverage
+        self.cost_counts = [(e, int(c)) for e, c in zip(entries, counts[: len(entries)].tolist())]
+        self.cost_local_count = int(counts[len(entries)])
+        if n:
+            _, last = ctx.coverage_lookup([self.basis.coverage_table()], n - 1, 1, want_entries=True, tol=pulse_cost.TOL)
+            j = int(last[0, 0])
+            if j < len(entries):
+                self.basis.set_polytope(entries[j])
+                self.basis._sequence = None
+        logging.info(f"Total circuit pulse cost: {total_cost}")
+        if n:
+            logging.info(f"Average gate pulse cost: {total_cost / n}")
+        return total_cost
+
     def _approximate_batch(self, stacked, log_index: bool):
         n = len(stacked)
         # The reference logs per target (optimizer.py:77-106,183,234,297-305).  Formatting ~10 lines for each of 1e5
