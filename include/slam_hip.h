@@ -490,6 +490,48 @@ int slam_v2_minimize_stage_trace(slam_ctx* ctx, int k, const int32_t* gate_seq, 
                                  double* trace_x);
 
 /*
+ * Parallel-drive ("smush") gates -- CircuitTemplateV2(param_vec_expand=[offset, N, N]) with ConversionGainSmushGate
+ * (custom_gates.py:215-257, hamiltonian.py:114-144, basisv2.py:47-50,268-273): a conversion-gain pulse with single-qubit drives
+ * applied during it, cut into N time slices with their own drive amplitudes,
+ *     G = U_{N-1} ... U_0,  U_s = exp(-i (t / N) H_s),
+ *     H_s = gx[s] (A + A^+) + gy[s] (B + B^+) + gc (e^{i pc} A B^+ + h.c.) + gg (e^{i pg} A B + h.c.).
+ * Phases pc, pg in {0, pi} only (pi flips the sign of gc / gg: fold it into the map).  A slam_smush_gate says how the raw pulse
+ * values, in the order gc, gg, gx[0 .. N), gy[0 .. N) (raw index 2 + s for gx[s], 2 + N + s for gy[s]), follow from the gate's
+ * n_params parameters q: raw[r] = scale[r] * q[sel[r]] + offset[r] (sel[r] = -1: the constant offset[r]); t is a constant.
+ * Parameter vectors in index order: P0 .. P{6(k+1)-1}, then the n_params parameters of gate 1, gate 2, ...:
+ * n = 6 (k + 1) + n_params k <= SLAM_SMUSH_MAX_N, spans 1..SLAM_SMUSH_MAX_SPAN; beyond that SLAM_ERR_UNSUPPORTED.
+ * Cost kinds BasicCost and SquareCost; SLAM_COST_MAKHLIN returns SLAM_ERR_UNSUPPORTED.  One wavefront per (target, restart) item.
+ *   slam_smush_set_gates               the table of smush base gates (host side only)
+ *   slam_smush_eval_loss_grad          as slam_v2_eval_loss_grad (angles beyond 2e8 rad evaluate to NaN)
+ *   slam_smush_minimize_stage(_trace)  as slam_v2_minimize_stage(_trace): projected quasi-Newton over the box, Philox start points in
+ *                                      [init_lo, init_hi), restart-major queue, ordered early exit, lowest-index restart below exit_loss
+ */
+#define SLAM_SMUSH_MAX_SLICES 58
+#define SLAM_SMUSH_RAW (2 + 2 * SLAM_SMUSH_MAX_SLICES)
+#define SLAM_SMUSH_MAX_SPAN 6
+#define SLAM_SMUSH_MAX_N 128
+typedef struct slam_smush_gate {
+    int32_t n_params;
+    int32_t n_slices;
+    double t;
+    int32_t sel[SLAM_SMUSH_RAW];
+    double scale[SLAM_SMUSH_RAW];
+    double offset[SLAM_SMUSH_RAW];
+} slam_smush_gate;
+int slam_smush_set_gates(slam_ctx* ctx, const slam_smush_gate* gates, int32_t n_gates);
+int slam_smush_eval_loss_grad(slam_ctx* ctx, int k, const int32_t* gate_seq, const double* x, const int32_t* target_of, int64_t M,
+                              double* loss, double* grad, double* unitary);
+int slam_smush_minimize_stage(slam_ctx* ctx, int k, const int32_t* gate_seq, const int32_t* active, int64_t n_active, const double* x0,
+                              const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi,
+                              const slam_opt_params* params, double exit_loss, double* best_loss, double* best_x, int32_t* best_restart,
+                              double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals);
+int slam_smush_minimize_stage_trace(slam_ctx* ctx, int k, const int32_t* gate_seq, const int32_t* active, int64_t n_active, const double* x0,
+                                    const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi,
+                                    const slam_opt_params* params, double exit_loss, int32_t trace_cap, double* best_loss, double* best_x,
+                                    int32_t* best_restart, double* item_loss, int32_t* item_iters, int32_t* item_status, double* trace_loss,
+                                    double* trace_x);
+
+/*
  * Multi-GPU: one process per GPU, RCCL over xGMI, reached through this ABI (no torch, no MPI).  The path shards by
  * target, every rank keeps all restarts of its targets, so the only exchange is the FINAL min-all-reduce of the
  * best-loss vector -- the running minimum of TemplateOptimizer._run (src/slam/optimizer.py:281-284) taken over the
@@ -539,7 +581,8 @@ const char* slam_version(void);
  *   6  round 5: SLAM_MAX_SPAN_EVAL / SLAM_MAX_SPAN_MINIMIZE 5 -> 16 -- the per-span arrays of slam_stats and the rows of
  *      slam_fetch_span_losses grow with them --, SLAM_FLAG_NO_EXTERIOR, kernel_ms_span[0];
  *   7  round 5: slam_host_alloc / slam_host_free (new symbols only);
- *      later: slam_coverage_lookup (a new symbol only; no signature or structure changed).
+ *      later: slam_coverage_lookup (a new symbol only; no signature or structure changed);
+ *      later: the slam_smush_* family and its own slam_smush_gate (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -30,6 +30,10 @@ FLAG_NO_OVERLAP = 16  # SLAM_FLAG_NO_OVERLAP: not even for medium calls (several
 FLAG_NO_EXTERIOR = 32  # SLAM_FLAG_NO_EXTERIOR: CircuitTemplate(no_exterior_1q=True) -- layers 0 and k pinned at the identity
 MAX_MAXITER = 4000
 V2_MAX_SPAN = 5
+SMUSH_MAX_SLICES = 58  # SLAM_SMUSH_MAX_SLICES
+SMUSH_RAW = 2 + 2 * SMUSH_MAX_SLICES
+SMUSH_MAX_SPAN = 6
+SMUSH_MAX_N = 128
 OP_SUM, OP_MAX, OP_MIN = 0, 2, 3
 COMM_ID_BYTES = 128
 COST_BASIC, COST_SQUARE, COST_MAKHLIN = 0, 1, 2
@@ -72,6 +76,10 @@ EXPORTED_SYMBOLS = (
     "slam_v2_minimize_stage",
     "slam_v2_minimize_stage_trace",
     "slam_v2_decompose_range",
+    "slam_smush_set_gates",
+    "slam_smush_eval_loss_grad",
+    "slam_smush_minimize_stage",
+    "slam_smush_minimize_stage_trace",
     "slam_set_cost",
     "slam_synchronize",
     "slam_host_alloc",
@@ -129,6 +137,23 @@ class V2Gate(C.Structure):
     def __init__(self, n_params, sel, scale, offset):
         super().__init__(int(n_params), (C.c_int32 * 4)(*[int(v) for v in sel]), (C.c_double * 4)(*[float(v) for v in scale]),
                          (C.c_double * 4)(*[float(v) for v in offset]))
+
+
+class SmushGate(C.Structure):
+    """``slam_smush_gate``: raw pulse values (gc, gg, gx[0..N), gy[0..N))[r] = scale[r] * q[sel[r]] + offset[r] of a smush gate
+    with N slices of pulse time t (phases folded into the signs of gc / gg)."""
+
+    _fields_ = [("n_params", C.c_int32), ("n_slices", C.c_int32), ("t", C.c_double), ("sel", C.c_int32 * SMUSH_RAW),
+                ("scale", C.c_double * SMUSH_RAW), ("offset", C.c_double * SMUSH_RAW)]
+
+    def __init__(self, n_params, n_slices, t, sel, scale, offset):
+        nr = 2 + 2 * int(n_slices)
+        if not (len(sel) == len(scale) == len(offset) == nr) or nr > SMUSH_RAW:
+            raise ValueError(f"a smush gate of {n_slices} slices has {nr} raw values (at most {SMUSH_RAW})")
+        pad = SMUSH_RAW - nr
+        super().__init__(int(n_params), int(n_slices), float(t), (C.c_int32 * SMUSH_RAW)(*([int(v) for v in sel] + [-1] * pad)),
+                         (C.c_double * SMUSH_RAW)(*([float(v) for v in scale] + [0.0] * pad)),
+                         (C.c_double * SMUSH_RAW)(*([float(v) for v in offset] + [0.0] * pad)))
 
 
 class Stats(C.Structure):
@@ -213,6 +238,11 @@ def load_library() -> C.CDLL:
             lib.slam_v2_decompose_range.argtypes = [P, C.c_int64, C.c_int64, C.c_int, C.c_int, P, P, P, P, P, C.POINTER(OptParams), C.c_double, P, P, P]
         if hasattr(lib, "slam_v2_minimize_stage_trace"):
             lib.slam_v2_minimize_stage_trace.argtypes = [P, C.c_int, P, P, C.c_int64, P, P, P, P, P, C.POINTER(OptParams), C.c_double, C.c_int32] + [P] * 8
+    if hasattr(lib, "slam_smush_set_gates"):
+        lib.slam_smush_set_gates.argtypes = [P, C.POINTER(SmushGate), C.c_int32]
+        lib.slam_smush_eval_loss_grad.argtypes = [P, C.c_int, P, P, P, C.c_int64, P, P, P]
+        lib.slam_smush_minimize_stage.argtypes = [P, C.c_int, P, P, C.c_int64, P, P, P, P, P, C.POINTER(OptParams), C.c_double] + [P] * 7
+        lib.slam_smush_minimize_stage_trace.argtypes = [P, C.c_int, P, P, C.c_int64, P, P, P, P, P, C.POINTER(OptParams), C.c_double, C.c_int32] + [P] * 8
     lib.slam_set_cost.argtypes = [P, C.c_int]
     lib.slam_synchronize.argtypes = [P]
     if hasattr(lib, "slam_host_alloc"):
@@ -720,9 +750,10 @@ class Context:
         return loss, grad, (w.view(np.complex128).reshape(M, 4, 4) if want_unitary else None)
 
     def v2_minimize_stage(self, gate_seq: Sequence[int], params: OptParams, exit_loss: float, init_lo, init_hi, bound_lo=None,
-                          bound_hi=None, active: Optional[np.ndarray] = None, x0: Optional[np.ndarray] = None, want_items: bool = True) -> dict:
+                          bound_hi=None, active: Optional[np.ndarray] = None, x0: Optional[np.ndarray] = None, want_items: bool = True,
+                          _fn=None, _qn=None) -> dict:
         k = len(gate_seq)
-        n = 6 * (k + 1) + self.v2_qn * k
+        n = 6 * (k + 1) + (self.v2_qn if _qn is None else _qn) * k
         gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
         if active is not None:
             active = np.ascontiguousarray(active, dtype=np.int32)
@@ -751,7 +782,7 @@ class Context:
             "item_evals": np.empty((na, R), dtype=np.int32) if want_items else None,
         }
         _check(
-            self._lib.slam_v2_minimize_stage(
+            (_fn or self._lib.slam_v2_minimize_stage)(
                 self._h, k, _ptr(gs), _ptr(active), na, _ptr(x0), _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(vecs[3]),
                 C.byref(params), float(exit_loss), _ptr(out["best_loss"]), _ptr(out["best_x"]), _ptr(out["best_restart"]),
                 _ptr(out["item_loss"]), _ptr(out["item_iters"]), _ptr(out["item_status"]), _ptr(out["item_evals"]),
@@ -779,11 +810,11 @@ class Context:
         return best_loss, best_x, best_cycles
 
     def v2_minimize_stage_trace(self, gate_seq: Sequence[int], params: OptParams, exit_loss: float, trace_cap: int, init_lo, init_hi,
-                                bound_lo=None, bound_hi=None, active: Optional[np.ndarray] = None) -> dict:
+                                bound_lo=None, bound_hi=None, active: Optional[np.ndarray] = None, _fn=None, _qn=None) -> dict:
         """``v2_minimize_stage`` plus the loss / parameters after every accepted iteration of every restart
         (``trace_loss`` [na, R, cap], ``trace_x`` [na, R, cap, n]; NaN beyond an item's iterations)."""
         k = len(gate_seq)
-        n = 6 * (k + 1) + self.v2_qn * k
+        n = 6 * (k + 1) + (self.v2_qn if _qn is None else _qn) * k
         gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
         if active is not None:
             active = np.ascontiguousarray(active, dtype=np.int32)
@@ -801,11 +832,48 @@ class Context:
             "item_iters": np.empty((na, R), dtype=np.int32), "item_status": np.empty((na, R), dtype=np.int32),
             "trace_loss": np.empty((na, R, cap), dtype=np.float64), "trace_x": np.empty((na, R, cap, n), dtype=np.float64),
         }
-        _check(self._lib.slam_v2_minimize_stage_trace(
+        _check((_fn or self._lib.slam_v2_minimize_stage_trace)(
             self._h, k, _ptr(gs), _ptr(active), na, None, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(vecs[3]), C.byref(params),
             float(exit_loss), cap, _ptr(out["best_loss"]), _ptr(out["best_x"]), _ptr(out["best_restart"]), _ptr(out["item_loss"]),
             _ptr(out["item_iters"]), _ptr(out["item_status"]), _ptr(out["trace_loss"]), _ptr(out["trace_x"])))
         return out
+
+    # -- parallel-drive ("smush") gates: the same calls as the V2 family -------------------------
+    def smush_set_gates(self, gates: Sequence["SmushGate"]) -> None:
+        arr = (SmushGate * len(gates))(*gates)
+        _check(self._lib.slam_smush_set_gates(self._h, arr, len(gates)))
+        self.smush_qn = int(gates[0].n_params)
+
+    def smush_eval(self, gate_seq, x, target_of=None, want_grad=True, want_unitary=False):
+        """As ``v2_eval`` for a smush gate table (n = 6 (k + 1) + QN k)."""
+        return self._v2_like_eval(self._lib.slam_smush_eval_loss_grad, self.smush_qn, gate_seq, x, target_of, want_grad, want_unitary)
+
+    def smush_minimize_stage(self, gate_seq, params: OptParams, exit_loss: float, init_lo, init_hi, bound_lo=None, bound_hi=None,
+                             active=None, x0=None, want_items: bool = True) -> dict:
+        """As ``v2_minimize_stage`` for a smush gate table."""
+        return self.v2_minimize_stage(gate_seq, params, exit_loss, init_lo, init_hi, bound_lo, bound_hi, active, x0, want_items,
+                                      _fn=self._lib.slam_smush_minimize_stage, _qn=self.smush_qn)
+
+    def smush_minimize_stage_trace(self, gate_seq, params: OptParams, exit_loss: float, trace_cap: int, init_lo, init_hi, bound_lo=None,
+                                   bound_hi=None, active=None) -> dict:
+        """As ``v2_minimize_stage_trace`` for a smush gate table."""
+        return self.v2_minimize_stage_trace(gate_seq, params, exit_loss, trace_cap, init_lo, init_hi, bound_lo, bound_hi, active,
+                                            _fn=self._lib.slam_smush_minimize_stage_trace, _qn=self.smush_qn)
+
+    def _v2_like_eval(self, fn, qn, gate_seq, x, target_of, want_grad, want_unitary):
+        k = len(gate_seq)
+        n = 6 * (k + 1) + qn * k
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != n:
+            raise ValueError(f"x must have shape [M, {n}]")
+        M = x.shape[0]
+        tof = np.zeros(M, np.int32) if target_of is None else np.ascontiguousarray(target_of, dtype=np.int32)
+        gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
+        loss = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, n), dtype=np.float64) if want_grad else None
+        w = np.empty((M, 4, 4, 2), dtype=np.float64) if want_unitary else None
+        _check(fn(self._h, k, _ptr(gs), _ptr(x), _ptr(tof), M, _ptr(loss), _ptr(grad), _ptr(w)))
+        return loss, grad, (w.view(np.complex128).reshape(M, 4, 4) if want_unitary else None)
 
     def set_cost(self, kind: int) -> None:
         """0 = BasicCost (default), 1 = SquareCost, 2 = MakhlinFunctionalCost (per-span launches; not for decompose_multi / V2)."""

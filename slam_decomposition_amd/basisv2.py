@@ -19,7 +19,12 @@ layers at ``U(0, 0, 0)`` = identity, like ``vz_only`` fixes theta and phi.  ``se
 ``circuit_cost(x) <= c``, which the reference hands to SciPy's SLSQP, optimizer.py:260-265) is implemented for circuit costs that
 are affine in the parameters over the box -- ``RiSwapGate`` (cost = alpha), ``ConversionGainGate`` lambdas whose drive strengths
 are bounded to one sign -- as a projected quasi-Newton method on the box cut by the half-space (slam_v2_set_constraint).
-Not implemented: ``param_vec_expand`` (time-sliced "smush" gates: not conversion-gain family members), polytopes.
+``param_vec_expand=[offset, N, N]`` (basisv2.py:47-50,268-273): every gate takes ``sum(param_vec_expand)`` parameters through a
+``*v`` lambda.  A lambda returning a ``ConversionGainSmushGate`` (parallel drives in N time slices) runs on the smush kernels
+(``slam_smush_*``, csrc/slam_smush.hpp) when ``gc``, ``gg``, ``gx[s]``, ``gy[s]`` are each affine in at most one parameter, ``t`` is a
+constant and the phases are constants in {0, pi}; spans 1..6 with at most 128 device parameters.  A lambda returning a
+conversion-gain gate runs on the V2 kernels (at most 4 parameters).  Not implemented: general smush phases, polytopes and
+``set_constraint`` for smush templates.
 """
 from __future__ import annotations
 
@@ -31,6 +36,8 @@ import numpy as np
 from . import _ffi, runtime
 from .basis_abc import VariationalTemplate
 from .gates import RiSwapGate
+
+SMUSH_MAX_SPAN = _ffi.SMUSH_MAX_SPAN
 
 DEFAULT_BOUND = (-4 * np.pi, 4 * np.pi)  # parameter_guess default range, basisv2.py:160
 
@@ -47,9 +54,10 @@ def _raw_angles(gate) -> np.ndarray:
     raise NotImplementedError(f"parametrised gate {name}: only conversion-gain family gates (RiSwapGate, ConversionGainGate) run on the HIP path")
 
 
-def gate_map(gate_fn):
+def gate_map(gate_fn, qn=None):
     """Probe ``gate_fn`` for raw[r] = scale[r] * q[sel[r]] + offset[r].  Returns (n_params, sel, scale, offset)."""
-    qn = len(signature(gate_fn).parameters)  # basisv2.py:268-273
+    if qn is None:
+        qn = len(signature(gate_fn).parameters)  # basisv2.py:268-273
     if not 1 <= qn <= 4:
         raise NotImplementedError(f"parametrised gates with {qn} parameters: 1..4 are supported (fix the pulse time t with a lambda)")
     rng = np.random.default_rng(12345)
@@ -75,6 +83,68 @@ def gate_map(gate_fn):
     return qn, sel, scale, [float(v) for v in offset]
 
 
+def _smush_values(gate):
+    """(N, t, pc, pg, raw = [gc, gg, gx[0..N), gy[0..N)]) of a ConversionGainSmushGate."""
+    if type(gate).__name__ != "ConversionGainSmushGate":
+        raise NotImplementedError(f"param_vec_expand: the gate callable returned {type(gate).__name__}; ConversionGainSmushGate and "
+                                  "conversion-gain gates run on the HIP path")
+    prm = [float(v) for v in gate.params]
+    N = int(gate.xy_len)
+    return N, prm[-1], prm[0], prm[1], np.array([prm[2], prm[3], *prm[4 : 4 + 2 * N]])
+
+
+def _phase_sign(phi: float, what: str) -> float:
+    r = float(np.mod(phi, 2 * np.pi))
+    if min(r, 2 * np.pi - r) < 1e-12:
+        return 1.0
+    if abs(r - np.pi) < 1e-12:
+        return -1.0
+    raise NotImplementedError(f"smush gate phase {what} = {phi}: only 0 and pi are implemented on the HIP path (general phases need a 4x4 "
+                              "Hermitian eigen-solve)")
+
+
+def smush_map(gate_fn, qn: int):
+    """Probe a ``*v`` lambda returning ConversionGainSmushGate for raw[r] = scale[r] * q[sel[r]] + offset[r] over the raw pulse values
+    (gc, gg, gx[0..N), gy[0..N)), with the phases folded into the signs of gc / gg.  Returns (N, t, sel, scale, offset)."""
+    rng = np.random.default_rng(12345)
+    q0 = rng.uniform(0.2, 1.2, qn)
+    N, t, pc, pg, r0 = _smush_values(gate_fn(*q0))
+    M = np.zeros((r0.size, qn))
+    for m in range(qn):
+        e = np.zeros(qn)
+        e[m] = 0.37
+        N1, t1, pc1, pg1, r1 = _smush_values(gate_fn(*(q0 + e)))
+        if N1 != N or t1 != t:
+            raise NotImplementedError("smush gate: the number of slices and the pulse time t must be constants")
+        if pc1 != pc or pg1 != pg:
+            raise NotImplementedError("smush gate: the phases pc, pg must be constants")
+        M[:, m] = (r1 - r0) / 0.37
+    q1 = rng.uniform(-2.0, 2.0, qn)
+    N1, t1, pc1, pg1, r1 = _smush_values(gate_fn(*q1))
+    if N1 != N or t1 != t or pc1 != pc or pg1 != pg:
+        raise NotImplementedError("smush gate: the number of slices, t and the phases must be constants")
+    if not np.allclose(r1, r0 + M @ (q1 - q0), atol=1e-9):
+        raise NotImplementedError("smush gate: gc, gg and the drives must be affine in the parameters")
+    if N > _ffi.SMUSH_MAX_SLICES:
+        raise NotImplementedError(f"smush gate of {N} slices: at most {_ffi.SMUSH_MAX_SLICES} on the HIP path")
+    if not np.isfinite(t):
+        raise NotImplementedError("smush gate: the pulse time must be finite")
+    sign = np.ones(r0.size)
+    sign[0] = _phase_sign(pc, "pc")
+    sign[1] = _phase_sign(pg, "pg")
+    sel, scale = [-1] * r0.size, [0.0] * r0.size
+    for r in range(r0.size):
+        nz = np.nonzero(np.abs(M[r]) > 1e-12)[0]
+        if len(nz) > 1:
+            raise NotImplementedError("smush gate: each of gc, gg, gx[s], gy[s] may depend on one parameter only")
+        if len(nz) == 1:
+            sel[r], scale[r] = int(nz[0]), float(sign[r] * M[r, nz[0]])
+    offset = sign * (r0 - M @ q0)
+    offset[np.abs(offset) < 1e-15] = 0.0
+    snap = lambda v: float(np.round(v)) if abs(v - np.round(v)) < 1e-12 else float(v)  # (the probe's rounding on unit slopes)
+    return N, float(t), sel, [snap(v) for v in scale], [snap(v) for v in offset]
+
+
 class CircuitTemplateV2(VariationalTemplate):
     def __init__(
         self,
@@ -96,7 +166,7 @@ class CircuitTemplateV2(VariationalTemplate):
         if n_qubits != 2:
             raise NotImplementedError("the HIP template optimizer handles 2-qubit templates only")
         if param_vec_expand is not None:
-            raise NotImplementedError("param_vec_expand (time-sliced smush gates, basisv2.py:47-50) is not implemented on the HIP path")
+            assert len(base_gates) == 1  # basisv2.py:49-50
         for el in edge_params:
             for e in el:
                 if tuple(e) != (0, 1):
@@ -104,19 +174,39 @@ class CircuitTemplateV2(VariationalTemplate):
         self.filename = None
         self.n_qubits = n_qubits
         self.no_exterior_1q = bool(no_exterior_1q)
-        self.param_vec_expand = None
+        self.param_vec_expand = None if param_vec_expand is None else [int(v) for v in param_vec_expand]
         self.vz_only = bool(vz_only)
         self.base_gates = list(base_gates)
         self.edge_params = edge_params
         self.device = device
-        maps = [gate_map(g) for g in self.base_gates]
+        self.smush = False
+        if self.param_vec_expand is not None:
+            qn = sum(self.param_vec_expand)  # basisv2.py:268-273: a *vargs lambda takes sum(param_vec_expand) parameters
+            try:
+                probe = self.base_gates[0](*np.full(qn, 0.5))
+            except TypeError as exc:
+                raise NotImplementedError(f"param_vec_expand={self.param_vec_expand}: the gate callable does not take {qn} parameters") from exc
+            if type(probe).__name__ == "ConversionGainSmushGate":
+                if use_polytopes:
+                    raise NotImplementedError("smush templates: use_polytopes (smush coverage polytopes) is not implemented")
+                self.smush = True
+                N, t, sel, scale, offset = smush_map(self.base_gates[0], qn)
+                self.n_slices = N
+                maps = [(qn, sel, scale, offset)]
+                self._smush_gates = [_ffi.SmushGate(qn, N, t, sel, scale, offset)]
+            else:
+                if qn > 4:
+                    raise NotImplementedError(f"param_vec_expand with a conversion-gain gate: {qn} parameters, at most 4 on the HIP path")
+                maps = [gate_map(self.base_gates[0], qn)]
+        else:
+            maps = [gate_map(g) for g in self.base_gates]
         qns = {m[0] for m in maps}
         if len(qns) != 1:
             raise NotImplementedError("all parametrised base gates of a template must take the same number of parameters")
         self.n_gate_params = qns.pop()
-        # device gates take 1, 2 or 4 parameters: a 3-parameter gate gets a fixed dummy fourth
-        self._dev_qn = 4 if self.n_gate_params == 3 else self.n_gate_params
-        self._gate_maps = [_ffi.V2Gate(self._dev_qn, m[1], m[2], m[3]) for m in maps]
+        # device gates take 1, 2 or 4 parameters: a 3-parameter gate gets a fixed dummy fourth (smush gates: any number)
+        self._dev_qn = 4 if (self.n_gate_params == 3 and not self.smush) else self.n_gate_params
+        self._gate_maps = [] if self.smush else [_ffi.V2Gate(self._dev_qn, m[1], m[2], m[3]) for m in maps]
         # XXX (basisv2.py:60-65)
         self.bounds = {}  # parameter name -> (min, max)
         self.bounds_list = []
@@ -142,9 +232,18 @@ class CircuitTemplateV2(VariationalTemplate):
         self._reset()
         if n_repetitions <= 0:
             raise ValueError()
-        if n_repetitions > _ffi.V2_MAX_SPAN:
-            raise NotImplementedError(f"parametrised-gate templates run spans 1..{_ffi.V2_MAX_SPAN} on the HIP path")
+        self.check_span(int(n_repetitions))
         self.cycles = int(n_repetitions)
+
+    def check_span(self, k: int) -> None:
+        """NotImplementedError for a template size the device kernels do not hold."""
+        if self.smush:
+            n = 6 * (k + 1) + self._dev_qn * k
+            if k > SMUSH_MAX_SPAN or n > _ffi.SMUSH_MAX_N:
+                raise NotImplementedError(f"smush-gate templates run spans 1..{SMUSH_MAX_SPAN} with at most {_ffi.SMUSH_MAX_N} device parameters "
+                                          f"on the HIP path (span {k}: {n})")
+        elif k > _ffi.V2_MAX_SPAN:
+            raise NotImplementedError(f"parametrised-gate templates run spans 1..{_ffi.V2_MAX_SPAN} on the HIP path")
 
     def gate_sequence(self, k=None) -> List[int]:
         k = self.cycles if k is None else k
@@ -240,6 +339,8 @@ class CircuitTemplateV2(VariationalTemplate):
 
     def set_constraint(self, param_max_cost):
         """basisv2.py:192-200: the current basis must not cost more than ``param_max_cost`` (C(x) >= 0 form for SciPy)."""
+        if self.smush:
+            raise NotImplementedError("set_constraint on smush templates is not implemented on the HIP path")
         self.constraint_func = {"type": "ineq", "fun": lambda x: param_max_cost - self.circuit_cost(x)}
         self.param_max_cost = float(param_max_cost)
         self.using_constraints = True
@@ -365,9 +466,25 @@ class CircuitTemplateV2(VariationalTemplate):
         return np.asarray(Xdev, dtype=np.float64)[..., idx]
 
     # ---- numerics -----------------------------------------------------------------------------------
+    def set_device_gates(self, ctx) -> None:
+        """The template's gate table into a libslamhip context (V2 or smush family)."""
+        if self.smush:
+            ctx.smush_set_gates(self._smush_gates)
+        else:
+            ctx.v2_set_gates(self._gate_maps)
+
+    def device_eval(self, ctx, gate_seq, X, **kw):
+        return ctx.smush_eval(gate_seq, X, **kw) if self.smush else ctx.v2_eval(gate_seq, X, **kw)
+
+    def device_minimize_stage(self, ctx, *a, **kw):
+        return ctx.smush_minimize_stage(*a, **kw) if self.smush else ctx.v2_minimize_stage(*a, **kw)
+
+    def device_minimize_stage_trace(self, ctx, *a, **kw):
+        return ctx.smush_minimize_stage_trace(*a, **kw) if self.smush else ctx.v2_minimize_stage_trace(*a, **kw)
+
     def _ctx(self):
         ctx = runtime.get_context(self.device)
-        ctx.v2_set_gates(self._gate_maps)
+        self.set_device_gates(ctx)
         if ctx.n_targets == 0:
             ctx.set_targets(np.eye(4, dtype=np.complex128)[None])
         return ctx
@@ -376,7 +493,7 @@ class CircuitTemplateV2(VariationalTemplate):
         """basisv2.py:145-147: the template unitary, evaluated by the HIP library."""
         if self.cycles <= 0:
             raise ValueError("build() the template first")
-        _, _, W = self._ctx().v2_eval(self.gate_sequence(), self.to_device_vector(Xk), want_grad=False, want_unitary=True)
+        _, _, W = self.device_eval(self._ctx(), self.gate_sequence(), self.to_device_vector(Xk), want_grad=False, want_unitary=True)
         return W[0]
 
     def gates_of(self, Xk) -> list:

@@ -189,6 +189,65 @@ class ConversionGainGate(Gate2Q):
         return conversion_gain_matrix(p1, p2, g1, g2, t)
 
 
+_A = np.kron(np.array([[0, 0], [1, 0]], dtype=np.complex128), np.eye(2))  # a (x) I, a = qutip.create(2)
+_B = np.kron(np.eye(2), np.array([[0, 0], [1, 0]], dtype=np.complex128))  # I (x) a
+
+
+def smush_hamiltonian(phi_c: float, phi_g: float, gc: float, gg: float, gx: float, gy: float) -> np.ndarray:
+    """H = gx (A + A^+) + gy (B + B^+) + gc (e^{i phi_c} A B^+ + h.c.) + gg (e^{i phi_g} A B + h.c.)  (hamiltonian.py:114-144)."""
+    Ad, Bd = _A.conj().T, _B.conj().T
+    conv = np.exp(1j * phi_c) * (_A @ Bd)
+    gain = np.exp(1j * phi_g) * (_A @ _B)
+    return gx * (_A + Ad) + gy * (_B + Bd) + gc * (conv + conv.conj().T) + gg * (gain + gain.conj().T)
+
+
+def smush_matrix(phi_c, phi_g, gc, gg, gx: Sequence[float], gy: Sequence[float], t: float = 1.0) -> np.ndarray:
+    """U = U_{N-1} ... U_0,  U_s = exp(-i (t / N) H_s): the conversion-gain pulse with the single-qubit drives (gx[s], gy[s]) of
+    slice s (ConversionGainSmushGate, hamiltonian.py:114-144).  Each slice exponential through the eigen-decomposition of the
+    Hermitian H_s, for any phases."""
+    gx = np.atleast_1d(np.asarray(gx, dtype=np.float64))
+    gy = np.atleast_1d(np.asarray(gy, dtype=np.float64))
+    if gx.shape != gy.shape or gx.ndim != 1 or gx.size == 0:
+        raise ValueError("gx and gy must be sequences of the same, non-zero length")
+    tau = float(t) / gx.size
+    U = np.eye(4, dtype=np.complex128)
+    for s in range(gx.size):
+        w, V = np.linalg.eigh(smush_hamiltonian(float(phi_c), float(phi_g), float(gc), float(gg), gx[s], gy[s]))
+        U = (V * np.exp(-1j * tau * w)) @ V.conj().T @ U
+    return U
+
+
+class ConversionGainSmushGate(Gate2Q):
+    """``ConversionGainSmushGate(pc, pg, gc, gg, gx, gy, t_el)`` (custom_gates.py:215-257): a conversion-gain pulse with
+    single-qubit drives applied during it, cut into N = len(gx) time slices with their own drive amplitudes.  Params are
+    ``[pc, pg, gc, gg, *gx, *gy, t]``; ``xy_len`` = N."""
+
+    def __init__(self, pc, pg, gc, gg, gx, gy, t_el=1):
+        gx = [float(v) for v in np.atleast_1d(np.asarray(gx, dtype=np.float64))]
+        gy = [float(v) for v in np.atleast_1d(np.asarray(gy, dtype=np.float64))]
+        if len(gx) != len(gy) or not gx:
+            raise ValueError("gx and gy must have the same, non-zero length")
+        self.xy_len = len(gx)
+        super().__init__("2QSmushGate", [pc, pg, gc, gg, *gx, *gy, t_el])
+        self.duration = self.cost()
+
+    @property
+    def gx(self):
+        return self.params[4 : 4 + self.xy_len]
+
+    @property
+    def gy(self):
+        return self.params[4 + self.xy_len : 4 + 2 * self.xy_len]
+
+    def cost(self):
+        norm = np.pi / 2  # as ConversionGainGate: (|gc| + |gg|) t / (pi / 2)
+        return (abs(float(self.params[2])) + abs(float(self.params[3]))) * float(self.params[-1]) / norm
+
+    def _matrix(self):
+        pc, pg, gc, gg = (float(v) for v in self.params[:4])
+        return smush_matrix(pc, pg, gc, gg, self.gx, self.gy, float(self.params[-1]))
+
+
 def gate_matrix(gate) -> np.ndarray:
     """4x4 complex128 matrix of a gate object / array."""
     if hasattr(gate, "to_matrix"):

@@ -166,6 +166,9 @@ class TemplateOptimizer:
             flags=_ffi.FLAG_EARLY_EXIT | (_ffi.FLAG_ORDERED if self.deterministic else 0)
             | (0 if (self.deterministic and len(self.devices) == 1 and self.auto_shards <= 1) else _ffi.FLAG_NO_OVERLAP)
             | (_ffi.FLAG_NO_EXTERIOR if self._no_exterior else 0),  # basis.py:154,165: layers 0 and k pinned at the identity
+            # smush templates: no far-point stop -- their many drive parameters leave long flat stretches above the far-loss level
+            # (with it, every restart of the reference's vertex targets ended at 1e-6 .. 1e-5)
+            **({"gtol_far": 0.0} if getattr(self.basis, "smush", False) else {}),
         )
 
     # a span loop side by side for ALL targets (SLAM_FLAG_OVERLAP) runs the LAST span for every target of the call: it pays when
@@ -589,8 +592,7 @@ class TemplateOptimizer:
         for k in ks:
             if k <= 0:
                 raise ValueError()  # build(n_repetitions <= 0), basisv2.py:221-222
-            if k > _ffi.V2_MAX_SPAN:
-                raise NotImplementedError(f"parametrised-gate templates run spans 1..{_ffi.V2_MAX_SPAN} on the HIP path (got {k})")
+            basis.check_span(k)
         layouts = {}
         for k in ks:
             basis.build(k)
@@ -603,14 +605,14 @@ class TemplateOptimizer:
             ctx = runtime.get_context(device) if single else _ffi.Context(device)
             try:
                 ctx.set_targets(targets[first : first + count])
-                ctx.v2_set_gates(basis._gate_maps)
+                basis.set_device_gates(ctx)
                 for k, (w_dev, cost_max) in constraints.items():
                     ctx.v2_set_constraint(k, w_dev, cost_max)
                 ctx.set_cost(self._cost_kind)
                 ctx.reset_stats()
                 sp = _ffi.OptParams(restarts=prm.restarts, maxiter=prm.maxiter, gtol=prm.gtol, stop_loss=prm.stop_loss, seed=prm.seed,
                                     flags=prm.flags, gtol_far=prm.gtol_far, far_loss=prm.far_loss, target_base=first)
-                if ks == list(range(ks[0], ks[-1] + 1)):
+                if ks == list(range(ks[0], ks[-1] + 1)) and not basis.smush:
                     # the usual case, a run of template sizes: the whole span loop as one chain of kernels on the device
                     try:
                         bl, bx, bc = ctx.v2_decompose_range(0, count, ks[0], ks[-1], [layouts[k][0] for k in ks],
@@ -637,7 +639,8 @@ class TemplateOptimizer:
                         break
                     seq, _, idx, init_lo, init_hi, blo, bhi = layouts[k]
                     try:
-                        out = ctx.v2_minimize_stage(seq, sp, self.success_threshold, init_lo, init_hi, blo, bhi, active=act, want_items=False)
+                        out = basis.device_minimize_stage(ctx, seq, sp, self.success_threshold, init_lo, init_hi, blo, bhi, active=act,
+                                                          want_items=False)
                     except _ffi.SlamHipError as exc:
                         if exc.code == -3:  # SLAM_ERR_UNSUPPORTED: span x parameters-per-gate beyond what the device kernels hold
                             raise NotImplementedError(str(exc)) from exc
@@ -700,7 +703,7 @@ class TemplateOptimizer:
         ctx = runtime.get_context(self.devices[0])
         ctx.set_targets(targets)
         if self._v2:
-            ctx.v2_set_gates(self.basis._gate_maps)
+            self.basis.set_device_gates(ctx)
             if self.basis.using_constraints:
                 for k in sorted({int(k) for ks in spans_per_target for k in ks}):
                     ctx.v2_set_constraint(k, *self.basis.constraint_layout(k))
@@ -720,7 +723,9 @@ class TemplateOptimizer:
             if k <= 0:
                 raise ValueError()  # CircuitTemplate.build(n_repetitions <= 0), basis.py:127-128
             k_lim = _ffi.V2_MAX_SPAN if self._v2 else _ffi.MAX_SPAN_MINIMIZE  # (per-iteration traces: both kernel families)
-            if k > k_lim:
+            if self._v2:
+                self.basis.check_span(k)
+            elif k > k_lim:
                 raise NotImplementedError(f"template spans up to {k_lim} are implemented on the HIP path (got {k})")
             act = np.array([t for t in range(n) if k in spans_per_target[t] and not (best[t] is not None and best[t] < self.success_threshold)],
                            dtype=np.int32)
@@ -734,7 +739,8 @@ class TemplateOptimizer:
             cap = 256
             while True:
                 if self._v2:
-                    out = ctx.v2_minimize_stage_trace(seq, prm, self.success_threshold, cap, v2_ilo, v2_ihi, v2_blo, v2_bhi, active=act)
+                    out = self.basis.device_minimize_stage_trace(ctx, seq, prm, self.success_threshold, cap, v2_ilo, v2_ihi, v2_blo, v2_bhi,
+                                                                 active=act)
                 else:
                     out = ctx.minimize_stage_trace(seq, prm, self.success_threshold, cap, active=act)
                 need = int(out["item_iters"].max())
@@ -747,7 +753,7 @@ class TemplateOptimizer:
                 if not len(X):
                     return []
                 if self._v2:
-                    _, _, W = ctx.v2_eval(seq, X, want_grad=False, want_unitary=True)  # X is in device layout already
+                    _, _, W = self.basis.device_eval(ctx, seq, X, want_grad=False, want_unitary=True)  # X is in device layout already
                     C3 = ctx.c1c2c3(W)
                 else:
                     C3 = ctx.eval_c1c2c3(seq, X)
@@ -845,7 +851,10 @@ class TemplateOptimizer:
                 idx = np.nonzero(best_cycles == k)[0]
                 self.basis.build(int(k))
                 X = self.basis.to_device_vector(np.stack([best_xs[i] for i in idx]), int(k))
-                _, _, W = ctx.v2_eval(self.basis.gate_sequence(int(k)), X, want_grad=False, want_unitary=True)
+                self.basis.set_device_gates(ctx)
+                if ctx.n_targets == 0:
+                    ctx.set_targets(np.eye(4, dtype=np.complex128)[None])
+                _, _, W = self.basis.device_eval(ctx, self.basis.gate_sequence(int(k)), X, want_grad=False, want_unitary=True)
                 found[idx] = ctx.c1c2c3(W)
             return found
         ctx.set_gates(self.basis.gate_matrices)

@@ -68,6 +68,18 @@ int main() {
     EXPECT(slam_v2_minimize_stage(nullptr, 1, i32, nullptr, 1, nullptr, d, d, nullptr, nullptr, &prm, 1e-10, d, d, i32, d, i32, i32, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_v2_decompose_range(nullptr, 0, 1, 1, 1, i32, d, d, nullptr, nullptr, &prm, 1e-10, d, d, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_v2_minimize_stage_trace(nullptr, 1, i32, nullptr, 1, nullptr, d, d, nullptr, nullptr, &prm, 1e-10, 4, d, d, i32, d, i32, i32, d, d) == SLAM_ERR_INVALID);
+    {
+        static slam_smush_gate sg{};
+        sg.n_params = 8;
+        sg.n_slices = 4;
+        sg.t = 1.0;
+        EXPECT(slam_smush_set_gates(nullptr, &sg, 1) == SLAM_ERR_INVALID);
+        EXPECT(slam_smush_eval_loss_grad(nullptr, 1, i32, d, i32, 1, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(slam_smush_minimize_stage(nullptr, 1, i32, nullptr, 1, nullptr, d, d, nullptr, nullptr, &prm, 1e-10, d, d, i32, d, i32, i32, i32) ==
+               SLAM_ERR_INVALID);
+        EXPECT(slam_smush_minimize_stage_trace(nullptr, 1, i32, nullptr, 1, nullptr, d, d, nullptr, nullptr, &prm, 1e-10, 4, d, d, i32, d, i32, i32, d,
+                                               d) == SLAM_ERR_INVALID);
+    }
     EXPECT(slam_set_cost(nullptr, 0) == SLAM_ERR_INVALID);
     EXPECT(slam_synchronize(nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_get_stats(nullptr, &st) == SLAM_ERR_INVALID);
