@@ -214,6 +214,52 @@ int slam_coverage_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_
                          const double* points, const double* bounds, double tol, int64_t* counts_out, int32_t* entry_out);
 
 /*
+ * Parallel-drive coverage (the sampling half of src/slam/utils/gates/parallel_drive_volume.py:176-256; csrc/slam_pd.hpp).
+ *
+ * slam_pd_sample: n_samples random templates of k ConversionGainSmushGate(pc, pg, gc, gg, gx[0:N], gy[0:N], t), N = n_slices, with a
+ * U3 (x) U3 layer between consecutive gates and none outside (CircuitTemplateV2(no_exterior_1q=1, vz_only=0,
+ * param_vec_expand=[2, N, N])).  Every parameter is uniform in (-bound, bound), drawn on the device from Philox4x32-10 keyed
+ * (seed, sample index, k); sample i has index first_index + i, or indices[i] when indices is not NULL (replay of chosen samples).
+ * Each slice is exp(-i (t / N) H) of the full Hermitian H (free phases).  The Weyl coordinates of every product (8 digits with
+ * ndigits = 8, unrounded with ndigits < 0), folded to c1 <= 1/2, stay resident for slam_pd_extremes / slam_pd_filter.  Optional
+ * host outputs (NULL = not wanted): coords_out double[n][3]; params_out double[n][P], P = 6 (k - 1) + k (2 + 2N), in the template's
+ * index order (layer angles, then per gate pc, pg, gx[0..N), gy[0..N)); unitaries_out double[n][4][4][2].
+ * k in 1..SLAM_PD_MAX_SPAN and n_slices in 1..SLAM_PD_MAX_SLICES (else SLAM_ERR_UNSUPPORTED); t > 0, bound > 0, n_samples >= 1.
+ *
+ * slam_pd_extremes: for each of n_dirs directions (double[n_dirs][3]) the resident sample with the largest dot product (values
+ * compared in float precision, ties to the lower index): index_out int64[n_dirs], coords_out double[n_dirs][3].
+ *
+ * slam_pd_filter: the resident samples that are NOT strictly inside (by more than eps) every facet n . c <= b of facets
+ * double[n_facets][4] = (n, b) -- with the facets of the hull of some samples, exactly those that can be vertices of the hull of all
+ * of them.  *n_out = how many; the first min(*n_out, capacity) go to index_out int64[] / coords_out double[][3], in no fixed order.
+ */
+#define SLAM_PD_MAX_SPAN 8
+#define SLAM_PD_MAX_SLICES 16
+#define SLAM_PD_MAX_DIRS 1024
+#define SLAM_PD_MAX_FACETS (1 << 20)
+int slam_pd_sample(slam_ctx* ctx, double gc, double gg, double t, int32_t n_slices, int32_t k, double bound, uint64_t seed,
+                   int64_t first_index, int64_t n_samples, const int64_t* indices, int ndigits, double* coords_out, double* params_out,
+                   double* unitaries_out);
+int slam_pd_extremes(slam_ctx* ctx, const double* directions, int32_t n_dirs, int64_t* index_out, double* coords_out);
+int slam_pd_filter(slam_ctx* ctx, const double* facets, int32_t n_facets, double eps, int64_t capacity, int64_t* n_out, int64_t* index_out,
+                   double* coords_out);
+
+/*
+ * Region lookup on the device: the resident targets [first, first + count) against n_regions regions (<= SLAM_REGION_MAX), each a
+ * union of polytopes [region_offsets[r], region_offsets[r + 1]).  Polytope p has kinds[p]:
+ *   0  facets [facet_offsets[p], facet_offsets[p + 1]) of facets double[][4] = (n, b): inside iff n . c <= b + tol for all of them,
+ *      c = the target's Weyl coordinates (8 digits, c3 >= 0)
+ *   1  a coverage region of two or more gates: aux[p][0..14) = bounds as in slam_coverage_lookup kind 1
+ *   2  one gate's class: aux[p][0..4) = its alcove point as in slam_coverage_lookup kind 0
+ * aux: double[P][14] (may be NULL when every kind is 0); facet_offsets int32[P + 1] (P = region_offsets[n_regions]).
+ * counts_out int64[2 n_regions + 1]: targets inside region r (r = 0 .. n_regions - 1), then targets whose FIRST containing region is r,
+ * then targets in none.  Integer counts: the result does not depend on the order in which the device adds them up.
+ */
+#define SLAM_REGION_MAX 256
+int slam_region_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_regions, const int32_t* region_offsets, const int32_t* kinds,
+                       const int32_t* facet_offsets, const double* facets, const double* aux, double tol, int64_t* counts_out);
+
+/*
  * Upload the table of 2Q basis-gate matrices (CircuitTemplate(base_gates=...),
  * src/slam/basis.py:52-69; matrices from src/slam/utils/gates/custom_gates.py).
  * gates: double[n_gates][4][4][2].
@@ -582,7 +628,8 @@ const char* slam_version(void);
  *      slam_fetch_span_losses grow with them --, SLAM_FLAG_NO_EXTERIOR, kernel_ms_span[0];
  *   7  round 5: slam_host_alloc / slam_host_free (new symbols only);
  *      later: slam_coverage_lookup (a new symbol only; no signature or structure changed);
- *      later: the slam_smush_* family and its own slam_smush_gate (new symbols only).
+ *      later: the slam_smush_* family and its own slam_smush_gate (new symbols only);
+ *      later: slam_pd_sample, slam_pd_extremes, slam_pd_filter and slam_region_lookup (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

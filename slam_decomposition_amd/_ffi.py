@@ -37,6 +37,10 @@ SMUSH_MAX_N = 128
 OP_SUM, OP_MAX, OP_MIN = 0, 2, 3
 COMM_ID_BYTES = 128
 COST_BASIC, COST_SQUARE, COST_MAKHLIN = 0, 1, 2
+PD_MAX_SPAN = 8  # SLAM_PD_MAX_SPAN
+PD_MAX_SLICES = 16  # SLAM_PD_MAX_SLICES
+PD_MAX_DIRS = 1024  # SLAM_PD_MAX_DIRS
+REGION_MAX = 256  # SLAM_REGION_MAX
 
 # every symbol include/slam_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -80,6 +84,10 @@ EXPORTED_SYMBOLS = (
     "slam_smush_eval_loss_grad",
     "slam_smush_minimize_stage",
     "slam_smush_minimize_stage_trace",
+    "slam_pd_sample",
+    "slam_pd_extremes",
+    "slam_pd_filter",
+    "slam_region_lookup",
     "slam_set_cost",
     "slam_synchronize",
     "slam_host_alloc",
@@ -243,6 +251,12 @@ def load_library() -> C.CDLL:
         lib.slam_smush_eval_loss_grad.argtypes = [P, C.c_int, P, P, P, C.c_int64, P, P, P]
         lib.slam_smush_minimize_stage.argtypes = [P, C.c_int, P, P, C.c_int64, P, P, P, P, P, C.POINTER(OptParams), C.c_double] + [P] * 7
         lib.slam_smush_minimize_stage_trace.argtypes = [P, C.c_int, P, P, C.c_int64, P, P, P, P, P, C.POINTER(OptParams), C.c_double, C.c_int32] + [P] * 8
+    if hasattr(lib, "slam_pd_sample"):
+        lib.slam_pd_sample.argtypes = [P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_int64, C.c_int64,
+                                       P, C.c_int, P, P, P]
+        lib.slam_pd_extremes.argtypes = [P, P, C.c_int32, P, P]
+        lib.slam_pd_filter.argtypes = [P, P, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_int64), P, P]
+        lib.slam_region_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, P, C.c_double, P]
     lib.slam_set_cost.argtypes = [P, C.c_int]
     lib.slam_synchronize.argtypes = [P]
     if hasattr(lib, "slam_host_alloc"):
@@ -484,6 +498,67 @@ class Context:
                                               _ptr(bounds), float(tol), _ptr(counts), _ptr(entries)))
         per_table = [counts[int(offsets[t]) + 2 * t : int(offsets[t + 1]) + 2 * (t + 1)] for t in range(len(tables))]
         return per_table, entries
+
+    # -- parallel-drive coverage (slam_pd_*, slam_region_lookup) --------------------------------------------------------------------------
+    def pd_sample(self, gc: float, gg: float, t: float, n_slices: int, k: int, n_samples: int, seed: int = 0, bound: float = 4 * np.pi,
+                  first_index: int = 0, indices=None, ndigits: int = 8, want_coords: bool = False, want_params: bool = False,
+                  want_unitaries: bool = False):
+        """``n_samples`` random parallel-drive templates of k gates on the device (slam_pd_sample); their folded Weyl coordinates stay
+        resident for ``pd_extremes`` / ``pd_filter``.  ``indices`` (int64[n]) replays chosen samples instead of ``first_index + i``.
+        Returns ``(coords [n, 3], params [n, P], unitaries [n, 4, 4])``, each None unless asked for."""
+        idx = None
+        if indices is not None:
+            idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+            n_samples = idx.size
+        n = int(n_samples)
+        P = 6 * (int(k) - 1) + int(k) * (2 + 2 * int(n_slices))
+        coords = np.zeros((max(n, 0), 3)) if want_coords else None
+        params = np.zeros((max(n, 0), max(P, 0))) if want_params else None
+        uni = np.zeros((max(n, 0), 4, 4, 2)) if want_unitaries else None
+        _check(self._lib.slam_pd_sample(self._h, float(gc), float(gg), float(t), int(n_slices), int(k), float(bound),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index), n, _ptr(idx), int(ndigits), _ptr(coords),
+                                        _ptr(params), _ptr(uni)))
+        if uni is not None:
+            uni = uni[..., 0] + 1j * uni[..., 1]
+        return coords, params, uni
+
+    def pd_extremes(self, directions) -> Tuple[np.ndarray, np.ndarray]:
+        """The resident sample that is extreme in each direction (slam_pd_extremes): ``(indices int64[D], coords [D, 3])``."""
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        idx = np.zeros(len(d), dtype=np.int64)
+        out = np.zeros((len(d), 3))
+        _check(self._lib.slam_pd_extremes(self._h, _ptr(d), len(d), _ptr(idx), _ptr(out)))
+        return idx, out
+
+    def pd_filter(self, facets, capacity: int, eps: float = 1e-12) -> Tuple[np.ndarray, np.ndarray]:
+        """The resident samples not strictly inside every facet ``n . c <= b`` (rows (n, b)) -- slam_pd_filter; sorted by sample
+        index: ``(indices int64[m], coords [m, 3])``."""
+        f = np.ascontiguousarray(facets, dtype=np.float64).reshape(-1, 4)
+        cap = int(capacity)
+        idx = np.zeros(cap, dtype=np.int64)
+        out = np.zeros((cap, 3))
+        m = C.c_int64(0)
+        _check(self._lib.slam_pd_filter(self._h, _ptr(f), len(f), float(eps), cap, C.byref(m), _ptr(idx), _ptr(out)))
+        if m.value > cap:
+            raise RuntimeError(f"pd_filter: {m.value} survivors, capacity {cap}")
+        order = np.argsort(idx[: m.value], kind="stable")
+        return idx[: m.value][order], out[: m.value][order]
+
+    def region_lookup(self, region_offsets, kinds, facet_offsets, facets, aux=None, first: int = 0, count: Optional[int] = None,
+                      tol: float = 1e-7) -> np.ndarray:
+        """Resident targets [first, first + count) against unions of polytopes (slam_region_lookup): int64[2 R + 1] -- per region the
+        targets inside, then the first-containing-region histogram (last bin: in none)."""
+        ro = np.ascontiguousarray(region_offsets, dtype=np.int32).reshape(-1)
+        ki = np.ascontiguousarray(kinds, dtype=np.int32).reshape(-1)
+        fo = np.ascontiguousarray(facet_offsets, dtype=np.int32).reshape(-1)
+        fa = np.ascontiguousarray(facets, dtype=np.float64).reshape(-1, 4)
+        ax = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64).reshape(-1, 14)
+        count = self.n_targets - first if count is None else int(count)
+        R = len(ro) - 1
+        counts = np.zeros(2 * max(R, 0) + 1, dtype=np.int64)
+        _check(self._lib.slam_region_lookup(self._h, int(first), int(count), R, _ptr(ro), _ptr(ki), _ptr(fo), _ptr(fa), _ptr(ax), float(tol),
+                                            _ptr(counts)))
+        return counts
 
     def eval_c1c2c3(self, gate_seq: Sequence[int], x: np.ndarray, ndigits: int = 8) -> np.ndarray:
         """Weyl coordinates of CircuitTemplate.eval(x[m]) for ``x[M, n]`` (optimizer.py:85,103) -> float64[M, 3];

@@ -7,6 +7,7 @@
 #include "slam_v2.hpp"
 #include "slam_long.hpp"
 #include "slam_smush.hpp"
+#include "slam_pd.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -168,6 +169,9 @@ struct slam_ctx {
     int smush_qn = 0;
     DevBuf smush_maps, smush_hmem;
     int64_t resident_waves_smush = 0;  // 0 = not asked yet
+    // slam_pd_* / slam_region_lookup (slam_pd.hpp): resident sample coordinates [pd_n][3], per-call staging, region tables
+    DevBuf pd_coords, pd_stage, pd_out, reg_table, reg_counts;
+    int64_t pd_n = 0;
 
     ~slam_ctx() {
         DevBuf* all[] = {&targets, &gates, &active, &active2, &x0, &item_rec, &item_x, &stage_loss, &stage_x, &stage_restart, &best_loss,
@@ -193,6 +197,7 @@ struct slam_ctx {
         cov_table.release();
         cov_counts.release();
         cov_entries.release();
+        for (DevBuf* b : {&pd_coords, &pd_stage, &pd_out, &reg_table, &reg_counts}) b->release();
         if (ov_fork) (void)hipEventDestroy(ov_fork);
         for (hipEvent_t e : ov_join) if (e) (void)hipEventDestroy(e);
         for (slam_ctx* h : helper) {
@@ -3015,6 +3020,179 @@ int slam_smush_minimize_stage_trace(slam_ctx* ctx, int k, const int32_t* gate_se
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(trace_loss, ctx->trace_loss.p, rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(trace_x, ctx->trace_x.p, rows * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+// ---- parallel-drive coverage (slam_pd.hpp) ----------------------------------------------------------------------------------------
+int slam_pd_sample(slam_ctx* ctx, double gc, double gg, double t, int32_t n_slices, int32_t k, double bound, uint64_t seed,
+                   int64_t first_index, int64_t n_samples, const int64_t* indices, int ndigits, double* coords_out, double* params_out,
+                   double* unitaries_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (n_samples <= 0 || n_samples > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "n_samples must be in 1..2^31-1 (got %lld)", (long long)n_samples);
+    if (!(t > 0.0) || !std::isfinite(t)) return fail(SLAM_ERR_INVALID, "t must be a finite positive pulse time (got %g)", t);
+    if (!(bound > 0.0) || !std::isfinite(bound)) return fail(SLAM_ERR_INVALID, "bound must be finite and positive (got %g)", bound);
+    if (!std::isfinite(gc) || !std::isfinite(gg)) return fail(SLAM_ERR_INVALID, "gc and gg must be finite");
+    if (k < 1 || k > SLAM_PD_MAX_SPAN) return fail(SLAM_ERR_UNSUPPORTED, "k must be in 1..%d (got %d)", SLAM_PD_MAX_SPAN, k);
+    if (n_slices < 1 || n_slices > SLAM_PD_MAX_SLICES)
+        return fail(SLAM_ERR_UNSUPPORTED, "n_slices must be in 1..%d (got %d)", SLAM_PD_MAX_SLICES, n_slices);
+    if (first_index < 0 || first_index > 0x7fffffffffffLL) return fail(SLAM_ERR_INVALID, "first_index out of range");
+    if (indices)
+        for (int64_t i = 0; i < n_samples; ++i)
+            if (indices[i] < 0) return fail(SLAM_ERR_INVALID, "indices[%lld] < 0", (long long)i);
+    if (!indices && first_index + n_samples > 0xffffffffLL) return fail(SLAM_ERR_INVALID, "sample indices beyond 2^32");
+    static_assert(SLAM_PD_MAX_SPAN == kPdMaxSpan && SLAM_PD_MAX_SLICES == kPdMaxSlices, "slam_pd limits");
+    HIP_TRY(hipSetDevice(ctx->device));
+    PdSpec sp{};
+    sp.gc = gc;
+    sp.gg = gg;
+    sp.tau = t / n_slices;
+    sp.bound = bound;
+    sp.n_slices = n_slices;
+    sp.k = k;
+    sp.n_params = 6 * (k - 1) + k * (2 + 2 * n_slices);
+    sp.seed = seed;
+    // staging: indices, then parameter rows, then unitaries
+    const size_t idx_b = indices ? (size_t)n_samples * sizeof(int64_t) : 0;
+    const size_t prm_b = params_out ? (size_t)n_samples * sp.n_params * sizeof(double) : 0;
+    const size_t uni_b = unitaries_out ? (size_t)n_samples * 32 * sizeof(double) : 0;
+    HIP_TRY(ctx->pd_coords.reserve((size_t)n_samples * 3 * sizeof(double)));
+    ctx->pd_n = 0;
+    if (idx_b + prm_b + uni_b) HIP_TRY(ctx->pd_stage.reserve(idx_b + prm_b + uni_b));
+    char* st = ctx->pd_stage.as<char>();
+    if (indices) HIP_TRY(hipMemcpyAsync(st, indices, idx_b, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(pd_sample_kernel, dim3((unsigned)((n_samples + kPdBlock - 1) / kPdBlock)), dim3(kPdBlock), 0, ctx->stream, sp,
+                       first_index, n_samples, indices ? reinterpret_cast<const int64_t*>(st) : nullptr, ndigits, ctx->pd_coords.as<double>(),
+                       params_out ? reinterpret_cast<double*>(st + idx_b) : nullptr, unitaries_out ? reinterpret_cast<double*>(st + idx_b + prm_b) : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (coords_out)
+        HIP_TRY(hipMemcpyAsync(coords_out, ctx->pd_coords.p, (size_t)n_samples * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (params_out) HIP_TRY(hipMemcpyAsync(params_out, st + idx_b, prm_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (unitaries_out) HIP_TRY(hipMemcpyAsync(unitaries_out, st + idx_b + prm_b, uni_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->pd_n = n_samples;
+    return SLAM_OK;
+}
+
+int slam_pd_extremes(slam_ctx* ctx, const double* directions, int32_t n_dirs, int64_t* index_out, double* coords_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (ctx->pd_n <= 0) return fail(SLAM_ERR_STATE, "no resident samples: call slam_pd_sample first");
+    if (n_dirs < 1 || n_dirs > SLAM_PD_MAX_DIRS) return fail(SLAM_ERR_INVALID, "n_dirs must be in 1..%d (got %d)", SLAM_PD_MAX_DIRS, n_dirs);
+    if (!directions || !index_out || !coords_out) return fail(SLAM_ERR_INVALID, "NULL argument");
+    for (int32_t d = 0; d < 3 * n_dirs; ++d)
+        if (!std::isfinite(directions[d])) return fail(SLAM_ERR_INVALID, "directions must be finite");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // staging: directions [n_dirs][3], keys [n_dirs], indices [n_dirs], coordinates [n_dirs][3]
+    const size_t dir_b = (size_t)n_dirs * 3 * sizeof(double), key_b = (size_t)n_dirs * sizeof(unsigned long long);
+    const size_t idx_b = (size_t)n_dirs * sizeof(int64_t), crd_b = (size_t)n_dirs * 3 * sizeof(double);
+    HIP_TRY(ctx->pd_out.reserve(dir_b + key_b + idx_b + crd_b));
+    char* b = ctx->pd_out.as<char>();
+    HIP_TRY(hipMemcpyAsync(b, directions, dir_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(b + dir_b, 0, key_b, ctx->stream));
+    const int64_t n = ctx->pd_n;
+    hipLaunchKernelGGL(pd_extremes_kernel, dim3((unsigned)((n + kPdScanBlock - 1) / kPdScanBlock)), dim3(kPdScanBlock), 0, ctx->stream,
+                       ctx->pd_coords.as<double>(), n, reinterpret_cast<const double*>(b), n_dirs, reinterpret_cast<unsigned long long*>(b + dir_b));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(pd_gather_kernel, dim3((unsigned)((n_dirs + 63) / 64)), dim3(64), 0, ctx->stream, ctx->pd_coords.as<double>(),
+                       reinterpret_cast<const unsigned long long*>(b + dir_b), n_dirs, reinterpret_cast<int64_t*>(b + dir_b + key_b),
+                       reinterpret_cast<double*>(b + dir_b + key_b + idx_b));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(index_out, b + dir_b + key_b, idx_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(coords_out, b + dir_b + key_b + idx_b, crd_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+int slam_pd_filter(slam_ctx* ctx, const double* facets, int32_t n_facets, double eps, int64_t capacity, int64_t* n_out, int64_t* index_out,
+                   double* coords_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (ctx->pd_n <= 0) return fail(SLAM_ERR_STATE, "no resident samples: call slam_pd_sample first");
+    if (n_facets < 0 || n_facets > SLAM_PD_MAX_FACETS) return fail(SLAM_ERR_INVALID, "n_facets must be in 0..%d (got %d)", SLAM_PD_MAX_FACETS, n_facets);
+    if (n_facets > 0 && !facets) return fail(SLAM_ERR_INVALID, "facets is NULL");
+    if (!n_out || capacity < 0 || (capacity > 0 && (!index_out || !coords_out))) return fail(SLAM_ERR_INVALID, "bad output arguments");
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(SLAM_ERR_INVALID, "eps must be finite and >= 0");
+    for (int32_t f = 0; f < 4 * n_facets; ++f)
+        if (!std::isfinite(facets[f])) return fail(SLAM_ERR_INVALID, "facets must be finite");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t n = ctx->pd_n;
+    // staging: facets [n_facets][4], the counter (8 bytes), indices [n], coordinates [n][3]
+    const size_t fac_b = ((size_t)n_facets * 4 * sizeof(double) + 7) & ~(size_t)7, cnt_b = 8;
+    const size_t idx_b = (size_t)n * sizeof(int64_t), crd_b = (size_t)n * 3 * sizeof(double);
+    HIP_TRY(ctx->pd_out.reserve(fac_b + cnt_b + idx_b + crd_b));
+    char* b = ctx->pd_out.as<char>();
+    if (n_facets > 0) HIP_TRY(hipMemcpyAsync(b, facets, (size_t)n_facets * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(b + fac_b, 0, cnt_b, ctx->stream));
+    hipLaunchKernelGGL(pd_filter_kernel, dim3((unsigned)((n + kPdScanBlock - 1) / kPdScanBlock)), dim3(kPdScanBlock), 0, ctx->stream,
+                       ctx->pd_coords.as<double>(), n, reinterpret_cast<const double*>(b), n_facets, eps, reinterpret_cast<unsigned int*>(b + fac_b),
+                       reinterpret_cast<int64_t*>(b + fac_b + cnt_b), reinterpret_cast<double*>(b + fac_b + cnt_b + idx_b));
+    HIP_TRY(hipGetLastError());
+    unsigned int m = 0;
+    HIP_TRY(hipMemcpyAsync(&m, b + fac_b, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *n_out = (int64_t)m;
+    const int64_t copy = (int64_t)m < capacity ? (int64_t)m : capacity;
+    if (copy > 0) {
+        HIP_TRY(hipMemcpyAsync(index_out, b + fac_b + cnt_b, (size_t)copy * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(coords_out, b + fac_b + cnt_b + idx_b, (size_t)copy * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return SLAM_OK;
+}
+
+int slam_region_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_regions, const int32_t* region_offsets, const int32_t* kinds,
+                       const int32_t* facet_offsets, const double* facets, const double* aux, double tol, int64_t* counts_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets) return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (n_regions < 1 || n_regions > SLAM_REGION_MAX) return fail(SLAM_ERR_INVALID, "n_regions must be in 1..%d (got %d)", SLAM_REGION_MAX, n_regions);
+    if (!region_offsets || !counts_out) return fail(SLAM_ERR_INVALID, "region_offsets / counts_out is NULL");
+    if (!std::isfinite(tol)) return fail(SLAM_ERR_INVALID, "tol must be finite");
+    if (region_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "region_offsets[0] must be 0");
+    for (int32_t r = 0; r < n_regions; ++r)
+        if (region_offsets[r + 1] < region_offsets[r] || region_offsets[r + 1] > 0x00ffffff)
+            return fail(SLAM_ERR_INVALID, "region_offsets must be non-decreasing and below 2^24");
+    const int32_t P = region_offsets[n_regions];
+    if (P > 0 && (!kinds || !facet_offsets)) return fail(SLAM_ERR_INVALID, "kinds / facet_offsets is NULL");
+    bool need_aux = false;
+    for (int32_t p = 0; p < P; ++p) {
+        if (kinds[p] < 0 || kinds[p] > 2) return fail(SLAM_ERR_INVALID, "kinds[%d] = %d (0 facets, 1 coverage bounds, 2 one gate)", p, kinds[p]);
+        need_aux = need_aux || kinds[p] != 0;
+    }
+    if (P > 0 && facet_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "facet_offsets[0] must be 0");
+    for (int32_t p = 0; p < P; ++p)
+        if (facet_offsets[p + 1] < facet_offsets[p] || facet_offsets[p + 1] > 0x00ffffff)
+            return fail(SLAM_ERR_INVALID, "facet_offsets must be non-decreasing and below 2^24");
+    const int64_t F = P > 0 ? facet_offsets[P] : 0;
+    if (F > 0 && !facets) return fail(SLAM_ERR_INVALID, "facets is NULL");
+    if (need_aux && !aux) return fail(SLAM_ERR_INVALID, "aux is NULL");
+    const int64_t n_counts = 2 * (int64_t)n_regions + 1;
+    std::memset(counts_out, 0, (size_t)n_counts * sizeof(int64_t));
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one upload: region offsets, kinds, facet offsets (int32), then facets [F][4] and aux [P][14] (doubles, 8-byte aligned)
+    const size_t ro_b = 0, ki_b = (size_t)(n_regions + 1) * sizeof(int32_t), fo_b = ki_b + (size_t)P * sizeof(int32_t);
+    const size_t fa_b = ((fo_b + (size_t)(P + 1) * sizeof(int32_t)) + 7) & ~(size_t)7;
+    const size_t ax_b = fa_b + (size_t)F * 4 * sizeof(double);
+    const size_t total_b = ax_b + (size_t)P * kSpanPatterns * sizeof(double);
+    HIP_TRY(ctx->reg_table.reserve(total_b));
+    HIP_TRY(ctx->reg_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
+    char* tb = ctx->reg_table.as<char>();
+    HIP_TRY(hipMemcpyAsync(tb + ro_b, region_offsets, ki_b, hipMemcpyHostToDevice, ctx->stream));
+    if (P > 0) {
+        HIP_TRY(hipMemcpyAsync(tb + ki_b, kinds, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(tb + fo_b, facet_offsets, (size_t)(P + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        if (F > 0) HIP_TRY(hipMemcpyAsync(tb + fa_b, facets, (size_t)F * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (aux) HIP_TRY(hipMemcpyAsync(tb + ax_b, aux, (size_t)P * kSpanPatterns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipMemsetAsync(ctx->reg_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
+    static_assert(SLAM_REGION_MAX == kRegionMax, "region table size");
+    hipLaunchKernelGGL(region_lookup_kernel, dim3((unsigned)((count + kRegionBlock - 1) / kRegionBlock)), dim3(kRegionBlock), 0, ctx->stream,
+                       ctx->targets.as<double>() + first * 32, count, n_regions, reinterpret_cast<const int32_t*>(tb + ro_b),
+                       reinterpret_cast<const int32_t*>(tb + ki_b), reinterpret_cast<const int32_t*>(tb + fo_b),
+                       reinterpret_cast<const double*>(tb + fa_b), reinterpret_cast<const double*>(tb + ax_b), tol,
+                       ctx->reg_counts.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counts_out, ctx->reg_counts.p, (size_t)n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return SLAM_OK;
 }

@@ -43,6 +43,10 @@ int main() {
     EXPECT(slam_targets_c1c2c3(nullptr, 0, 1, 8, d) == SLAM_ERR_INVALID);
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
+    EXPECT(slam_pd_sample(nullptr, 1.0, 0.0, 1.0, 4, 1, 1.0, 0, 0, 1, nullptr, 8, d, nullptr, nullptr) == SLAM_ERR_INVALID);
+    EXPECT(slam_pd_extremes(nullptr, d, 1, &i64, d) == SLAM_ERR_INVALID);
+    EXPECT(slam_pd_filter(nullptr, d, 1, 0.0, 0, &i64, nullptr, nullptr) == SLAM_ERR_INVALID);
+    EXPECT(slam_region_lookup(nullptr, 0, 1, 1, i32, i32, i32, d, d, 1e-7, &i64) == SLAM_ERR_INVALID);
     EXPECT(slam_eval_c1c2c3(nullptr, 1, i32, d, 1, 8, d) == SLAM_ERR_INVALID);
     EXPECT(slam_set_gates(nullptr, d, 1) == SLAM_ERR_INVALID);
     EXPECT(slam_eval_loss_grad(nullptr, 1, i32, d, i32, 1, d, d) == SLAM_ERR_INVALID);
