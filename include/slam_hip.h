@@ -617,6 +617,19 @@ int slam_comm_merge_add(slam_comm* comm, slam_ctx* ctx, int64_t first_local, int
 int slam_comm_merge_add_host(slam_comm* comm, const double* loss, int64_t count, int64_t first_global);
 int slam_allreduce_min(slam_comm* comm, double threshold, int64_t* n_below, double* merged, int64_t merged_capacity);
 
+/*
+ * Hardware queues.  The HIP runtime maps all streams of a process onto GPU_MAX_HW_QUEUES hardware queues (its default: 4) and reads
+ * that variable once, at its first call; streams that share a queue serialise, so contexts that are meant to run side by side --
+ * several calls in flight from host threads, the helper streams of speculative / overlapped spans -- need one queue each.  The
+ * library asks for them itself: a load-time initialiser (before any HIP call of the library) sets GPU_MAX_HW_QUEUES to 16 when it is
+ * unset, not a number or below 16.  A value of 16 or more is kept: the variable is never lowered, and nothing above 32 is ever
+ * written.  SLAM_HW_QUEUES=0 in the environment switches the initialiser off, SLAM_HW_QUEUES=N (4 <= N <= 32) asks for N instead of
+ * 16; any other value is ignored.  A process that has initialised HIP BEFORE it loads the library is out of its reach: there the
+ * caller exports the variable, as before.
+ * Returns the value of GPU_MAX_HW_QUEUES in force after the initialiser ran, or 0 when it was switched off.
+ */
+int slam_hw_queues_requested(void);
+
 /* Library version string. */
 const char* slam_version(void);
 
@@ -629,7 +642,8 @@ const char* slam_version(void);
  *   7  round 5: slam_host_alloc / slam_host_free (new symbols only);
  *      later: slam_coverage_lookup (a new symbol only; no signature or structure changed);
  *      later: the slam_smush_* family and its own slam_smush_gate (new symbols only);
- *      later: slam_pd_sample, slam_pd_extremes, slam_pd_filter and slam_region_lookup (new symbols only).
+ *      later: slam_pd_sample, slam_pd_extremes, slam_pd_filter and slam_region_lookup (new symbols only);
+ *      later: slam_hw_queues_requested (a new symbol only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "slam_last_error",
     "slam_version",
     "slam_abi_version",
+    "slam_hw_queues_requested",
     "slam_device_count",
     "slam_ctx_create",
     "slam_ctx_destroy",
@@ -205,6 +206,8 @@ def load_library() -> C.CDLL:
     if abi != ABI_VERSION and not variant:
         raise ImportError(f"{LIB_PATH}: binary interface revision {abi}, this binding is written for {ABI_VERSION} (include/slam_hip.h: "
                           "SLAM_ABI_VERSION): rebuild the library with `make`")
+    if hasattr(lib, "slam_hw_queues_requested"):
+        lib.slam_hw_queues_requested.argtypes = []
     lib.slam_device_count.argtypes = [C.POINTER(C.c_int)]
     lib.slam_ctx_create.argtypes = [C.c_int, C.POINTER(P)]
     lib.slam_ctx_destroy.argtypes = [P]
@@ -286,6 +289,13 @@ def load_library() -> C.CDLL:
             fn.restype = C.c_int
     _lib = lib
     return lib
+
+
+def hw_queues_requested() -> int:
+    """``slam_hw_queues_requested``: the ``GPU_MAX_HW_QUEUES`` in force after the library's load-time initialiser ran (it raises
+    the variable to 16 by itself; ``SLAM_HW_QUEUES=0`` switches that off -> 0).  The change is made in the C environment:
+    ``os.environ`` is a snapshot taken at interpreter start and does not show it."""
+    return int(load_library().slam_hw_queues_requested())
 
 
 def _check(rc: int) -> None:

@@ -1479,9 +1479,48 @@ int decompose_multi_impl(slam_ctx** cs, int n, int64_t first, int64_t count, int
     return rc;
 }
 
+// ---- hardware queues, asked for when the library loads (include/slam_hip.h: slam_hw_queues_requested) ----
+// The HIP runtime maps every stream of the process onto GPU_MAX_HW_QUEUES hardware queues (its default: 4) and reads that variable
+// once, when its first call initialises it.  Streams that share a queue serialise, and the library lives on contexts that run side by
+// side: each has its own stream, and the speculative / overlapped spans add streams inside a call.  So the library raises the variable
+// itself, in the earliest constructor the toolchain gives a shared object (priorities up to 100 belong to the implementation).  No HIP
+// call is made here: the runtime stays uninitialised until the first real entry point.
+constexpr long HWQ_DEFAULT = 16, HWQ_MIN = 4, HWQ_MAX = 32;
+int g_hw_queues = 0;  // the value in force after the constructor ran; 0 = switched off
+
+// leading decimal digits as atoi reads them (what the runtime does with the variable); -1 = none
+long env_number(const char* s) {
+    if (!s) return -1;
+    char* end = nullptr;
+    const long v = std::strtol(s, &end, 10);
+    return end == s ? -1 : v;
+}
+
+__attribute__((constructor(101))) void request_hw_queues() {
+    long want = HWQ_DEFAULT;
+    if (const char* own = std::getenv("SLAM_HW_QUEUES")) {
+        char* end = nullptr;
+        const long v = std::strtol(own, &end, 10);
+        const bool whole = end != own && *end == '\0';
+        if (whole && v == 0) return;  // the integrator keeps their own number
+        if (whole && v >= HWQ_MIN && v <= HWQ_MAX) want = v;
+    }
+    const long have = env_number(std::getenv("GPU_MAX_HW_QUEUES"));
+    if (have >= want) {  // never lowered; a value above HWQ_MAX is the caller's and is not written here
+        g_hw_queues = have > 0x7fffffffL ? 0x7fffffff : (int)have;
+        return;
+    }
+    char buf[8];
+    snprintf(buf, sizeof(buf), "%ld", want);
+    if (setenv("GPU_MAX_HW_QUEUES", buf, 1) == 0) g_hw_queues = (int)want;
+    else g_hw_queues = have > 0 ? (int)have : 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int slam_hw_queues_requested(void) { return g_hw_queues; }
 
 const char* slam_last_error(void) { return g_err.c_str(); }
 

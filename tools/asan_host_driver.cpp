@@ -5,6 +5,7 @@
 #include "../include/slam_hip.h"
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -17,6 +18,11 @@ static int fails = 0;
 
 int main() {
     EXPECT(std::strstr(slam_version(), "gfx950") != nullptr);
+    {  // the load-time initialiser ran before main: off (SLAM_HW_QUEUES=0), or the variable holds what it reports, at least 4
+        const int q = slam_hw_queues_requested();
+        const char* e = std::getenv("GPU_MAX_HW_QUEUES");
+        EXPECT(q == 0 || (q >= 4 && e && std::atoi(e) == q));
+    }
     EXPECT(slam_device_count(nullptr) == SLAM_ERR_INVALID);
     int n = -1;
     const int rc_count = slam_device_count(&n);
