@@ -1,17 +1,26 @@
-# Build libslamhip.so (gfx950 only) and keep compiler temporaries under build/.
+# Build libslamhip.so (gfx950 only): one object per translation unit, compiler temporaries (ISA, resource reports) under build/.
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
-SRC   := slam_decomposition_amd/csrc/slam_hip.hip slam_decomposition_amd/csrc/slam_comm.hip
-HDRS  := slam_decomposition_amd/csrc/slam_device.hpp slam_decomposition_amd/csrc/slam_kernels.hpp slam_decomposition_amd/csrc/slam_sampler.hpp slam_decomposition_amd/csrc/slam_weyl.hpp slam_decomposition_amd/csrc/slam_sincos.hpp slam_decomposition_amd/csrc/slam_v2.hpp slam_decomposition_amd/csrc/slam_long.hpp slam_decomposition_amd/csrc/slam_long_eval.inc slam_decomposition_amd/csrc/slam_long_minimize.inc slam_decomposition_amd/csrc/slam_smush.hpp slam_decomposition_amd/csrc/slam_pd.hpp include/slam_hip.h
+CSRC  := slam_decomposition_amd/csrc
+UNITS := slam_hip slam_v2_host slam_smush_host slam_geometry slam_comm
+OBJS  := $(UNITS:%=build/%.o)
 OUT   := slam_decomposition_amd/lib/libslamhip.so
-FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-function -ldl
+FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function
 
 all: $(OUT)
 
-$(OUT): $(SRC) $(HDRS)
-	mkdir -p build slam_decomposition_amd/lib
-	$(HIPCC) $(FLAGS) -save-temps=obj -Rpass-analysis=kernel-resource-usage -o build/libslamhip.so $(SRC) 2> build/resource_usage.txt || (cat build/resource_usage.txt; exit 1)
+# the compiler's remarks (and, on failure, its errors) go to the unit's report; header dependencies to build/<unit>.d
+build/%.o: $(CSRC)/%.hip
+	@mkdir -p build
+	$(HIPCC) $(FLAGS) -c -save-temps=obj -Rpass-analysis=kernel-resource-usage -MMD -MF build/$*.d -o $@ $< 2> build/$*.resource_usage.txt || (cat build/$*.resource_usage.txt; exit 1)
+
+$(OUT): $(OBJS)
+	mkdir -p slam_decomposition_amd/lib
+	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o build/libslamhip.so $(OBJS) -ldl
+	cat $(UNITS:%=build/%.resource_usage.txt) > build/resource_usage.txt
 	cp build/libslamhip.so $(OUT)
+
+-include $(OBJS:.o=.d)
 
 clean:
 	rm -rf build $(OUT)

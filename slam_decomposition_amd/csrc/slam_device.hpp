@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "slam_sincos.hpp"
+#include "slam_types.hpp"
 
 namespace slamdev {
 
@@ -431,7 +432,7 @@ __device__ __forceinline__ void sincos_any(double x, const double2* tbl, double&
 // ---------------------------------------------------------------------------------
 //   GC_XRI1   GC_XRI whose block on (0,3) is the identity: RiSwapGate(alpha) = sqrt-iSWAP, iSWAP  4 real-scalar products
 enum : int { GC_DENSE = 0, GC_XGEN = 1, GC_XRI = 2, GC_CX = 3, GC_XRI1 = 4 };
-constexpr int kGateClasses = 5;
+// (kGateClasses, their number: slam_types.hpp)
 
 #define SLAM_GRE(r, s) G[((r) * 4 + (s)) * 2]
 #define SLAM_GIM(r, s) G[((r) * 4 + (s)) * 2 + 1]

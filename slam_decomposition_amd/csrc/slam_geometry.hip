@@ -1,0 +1,339 @@
+// slam_geometry.hip -- host side of libslamhip.so, geometry unit: Weyl coordinates, span prediction and coverage lookups, the Haar
+// sampler, parallel-drive coverage samples and region lookups (slam_weyl.hpp, slam_sampler.hpp, slam_pd.hpp).
+#include "slam_host.hpp"
+#include "slam_sampler.hpp"
+#include "slam_weyl.hpp"
+#include "slam_pd.hpp"
+
+int enqueue_c1c2c3(slam_ctx* c, const double* d_unitaries, int64_t count, int ndigits, double* d_out) {
+    hipLaunchKernelGGL(c1c2c3_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_unitaries, count, ndigits, d_out);
+    HIP_TRY(hipGetLastError());
+    return SLAM_OK;
+}
+
+int enqueue_span_predict(slam_ctx* c, int64_t first, int64_t count, int k_max, const double* point, const double* bounds, double tol,
+                         int32_t* d_spans) {
+    static_assert(sizeof(SpanRegions{}.bounds) / sizeof(SpanRegions{}.bounds[0]) == SLAM_MAX_SPAN_EVAL, "SpanRegions::bounds holds SLAM_MAX_SPAN_EVAL prefixes");
+    SpanRegions r{};
+    r.k_max = k_max;
+    r.tol = tol;
+    for (int j = 0; j < 4; ++j) r.point[j] = point[j];
+    for (int k = 2; k <= k_max; ++k)
+        for (int p = 0; p < kSpanPatterns; ++p) r.bounds[k - 1][p] = bounds[(size_t)(k - 1) * kSpanPatterns + p];
+    hipLaunchKernelGGL(span_predict_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, c->targets.as<double>() + first * 32, count, r,
+                       d_spans);
+    HIP_TRY(hipGetLastError());
+    return SLAM_OK;
+}
+
+// Weyl coordinates of `count` unitaries that are already in device memory
+static int weyl_device(slam_ctx* ctx, const double* d_unitaries, int64_t count, int ndigits, double* out) {
+    HIP_TRY(ctx->ev_weyl.reserve((size_t)count * 3 * sizeof(double)));
+    int rc = enqueue_c1c2c3(ctx, d_unitaries, count, ndigits, ctx->ev_weyl.as<double>());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, ctx->ev_weyl.p, (size_t)count * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+extern "C" {
+
+int slam_c1c2c3(slam_ctx* ctx, const double* unitaries, int64_t count, int ndigits, double* out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (count < 0) return fail(SLAM_ERR_INVALID, "count < 0");
+    if (count == 0) return SLAM_OK;
+    if (!unitaries || !out) return fail(SLAM_ERR_INVALID, "unitaries and out must be non-NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_unitary.reserve((size_t)count * 32 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(ctx->ev_unitary.p, unitaries, (size_t)count * 32 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return weyl_device(ctx, ctx->ev_unitary.as<double>(), count, ndigits, out);
+}
+
+int slam_targets_c1c2c3(slam_ctx* ctx, int64_t first, int64_t count, int ndigits, double* out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count == 0) return SLAM_OK;
+    if (!out) return fail(SLAM_ERR_INVALID, "out is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return weyl_device(ctx, ctx->targets.as<double>() + first * 32, count, ndigits, out);
+}
+
+int slam_predict_spans(slam_ctx* ctx, int64_t first, int64_t count, int k_max, const double* point, const double* bounds, double tol,
+                       int32_t* spans_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (k_max < 1 || k_max > SLAM_MAX_SPAN_EVAL) return fail(SLAM_ERR_INVALID, "k_max must be 1..%d (got %d)", SLAM_MAX_SPAN_EVAL, k_max);
+    if (!point || (k_max > 1 && !bounds)) return fail(SLAM_ERR_INVALID, "point / bounds is NULL");
+    if (count == 0) return SLAM_OK;
+    if (!spans_out) return fail(SLAM_ERR_INVALID, "spans_out is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_weyl.reserve((size_t)count * sizeof(int32_t)));
+    int rc = enqueue_span_predict(ctx, first, count, k_max, point, bounds, tol, ctx->ev_weyl.as<int32_t>());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(spans_out, ctx->ev_weyl.p, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+int slam_coverage_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_tables, const int32_t* table_offsets, const int32_t* kinds,
+                         const double* points, const double* bounds, double tol, int64_t* counts_out, int32_t* entry_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (n_tables < 1) return fail(SLAM_ERR_INVALID, "n_tables must be >= 1 (got %d)", n_tables);
+    if (!table_offsets) return fail(SLAM_ERR_INVALID, "table_offsets is NULL");
+    if (table_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "table_offsets[0] must be 0 (got %d)", table_offsets[0]);
+    int32_t max_bins = 0;
+    for (int32_t t = 0; t < n_tables; ++t) {
+        if (table_offsets[t + 1] < table_offsets[t])
+            return fail(SLAM_ERR_INVALID, "table_offsets must be non-decreasing (offsets[%d] = %d > offsets[%d] = %d)", t, table_offsets[t],
+                        t + 1, table_offsets[t + 1]);
+        if (table_offsets[t + 1] > 0x3fffffff) return fail(SLAM_ERR_INVALID, "too many coverage entries");
+        const int32_t nb = table_offsets[t + 1] - table_offsets[t] + 2;
+        if (nb > max_bins) max_bins = nb;
+    }
+    const int64_t E = table_offsets[n_tables];
+    if (E > 0 && (!kinds || !points || !bounds)) return fail(SLAM_ERR_INVALID, "kinds / points / bounds is NULL");
+    for (int64_t e = 0; e < E; ++e)
+        if (kinds[e] != 0 && kinds[e] != 1) return fail(SLAM_ERR_INVALID, "kinds[%lld] = %d (0 = one gate, 1 = half-spaces)", (long long)e, kinds[e]);
+    if (!counts_out) return fail(SLAM_ERR_INVALID, "counts_out is NULL");
+    const int64_t n_counts = E + 2 * (int64_t)n_tables;
+    std::memset(counts_out, 0, (size_t)n_counts * sizeof(int64_t));
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one upload: offsets, kinds (int32), then points [E][4] and bounds [E][14] (doubles, 8-byte aligned)
+    const size_t off_b = 0, kind_b = (size_t)(n_tables + 1) * sizeof(int32_t);
+    const size_t pt_b = ((kind_b + (size_t)E * sizeof(int32_t)) + 7) & ~(size_t)7;
+    const size_t bd_b = pt_b + (size_t)E * 4 * sizeof(double);
+    const size_t total_b = bd_b + (size_t)E * kSpanPatterns * sizeof(double);
+    HIP_TRY(ctx->cov_table.reserve(total_b));
+    HIP_TRY(ctx->cov_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
+    if (entry_out) HIP_TRY(ctx->cov_entries.reserve((size_t)n_tables * (size_t)count * sizeof(int32_t)));
+    char* tb = ctx->cov_table.as<char>();
+    HIP_TRY(hipMemcpyAsync(tb + off_b, table_offsets, kind_b, hipMemcpyHostToDevice, ctx->stream));
+    if (E > 0) {
+        HIP_TRY(hipMemcpyAsync(tb + kind_b, kinds, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(tb + pt_b, points, (size_t)E * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(tb + bd_b, bounds, (size_t)E * kSpanPatterns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipMemsetAsync(ctx->cov_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
+    const int32_t lds_bins = max_bins < kCoverageLdsBins ? max_bins : kCoverageLdsBins;
+    hipLaunchKernelGGL(coverage_lookup_kernel, dim3((unsigned)((count + kCoverageBlock - 1) / kCoverageBlock)), dim3(kCoverageBlock),
+                       (size_t)lds_bins * sizeof(unsigned int), ctx->stream, ctx->targets.as<double>() + first * 32, count, n_tables,
+                       reinterpret_cast<const int32_t*>(tb + off_b), reinterpret_cast<const int32_t*>(tb + kind_b),
+                       reinterpret_cast<const double*>(tb + pt_b), reinterpret_cast<const double*>(tb + bd_b), tol, lds_bins,
+                       ctx->cov_counts.as<unsigned long long>(), entry_out ? ctx->cov_entries.as<int32_t>() : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counts_out, ctx->cov_counts.p, (size_t)n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (entry_out)
+        HIP_TRY(hipMemcpyAsync(entry_out, ctx->cov_entries.p, (size_t)n_tables * (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+int slam_sample_haar(slam_ctx* ctx, uint64_t seed, int64_t first_index, int64_t n_targets) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (n_targets <= 0 || n_targets > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "n_targets must be in 1..2^31-1");
+    if (first_index < 0) return fail(SLAM_ERR_INVALID, "first_index < 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->targets.reserve((size_t)n_targets * 32 * sizeof(double)));
+    hipLaunchKernelGGL(haar_targets_kernel, dim3((unsigned)((n_targets + 127) / 128)), dim3(128), 0, ctx->stream,
+                       ctx->targets.as<double>(), first_index, n_targets, seed);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->n_targets = n_targets;
+    ctx->result_nmax = 0;
+    ctx->result_filled = 0;
+    return SLAM_OK;
+}
+
+int slam_get_targets(slam_ctx* ctx, int64_t first, int64_t count, double* out) {
+    if (!ctx || !out) return fail(SLAM_ERR_INVALID, "NULL argument");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, ctx->targets.as<double>() + first * 32, (size_t)count * 32 * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+// ---- parallel-drive coverage (slam_pd.hpp) ----------------------------------------------------------------------------------------
+int slam_pd_sample(slam_ctx* ctx, double gc, double gg, double t, int32_t n_slices, int32_t k, double bound, uint64_t seed,
+                   int64_t first_index, int64_t n_samples, const int64_t* indices, int ndigits, double* coords_out, double* params_out,
+                   double* unitaries_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (n_samples <= 0 || n_samples > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "n_samples must be in 1..2^31-1 (got %lld)", (long long)n_samples);
+    if (!(t > 0.0) || !std::isfinite(t)) return fail(SLAM_ERR_INVALID, "t must be a finite positive pulse time (got %g)", t);
+    if (!(bound > 0.0) || !std::isfinite(bound)) return fail(SLAM_ERR_INVALID, "bound must be finite and positive (got %g)", bound);
+    if (!std::isfinite(gc) || !std::isfinite(gg)) return fail(SLAM_ERR_INVALID, "gc and gg must be finite");
+    if (k < 1 || k > SLAM_PD_MAX_SPAN) return fail(SLAM_ERR_UNSUPPORTED, "k must be in 1..%d (got %d)", SLAM_PD_MAX_SPAN, k);
+    if (n_slices < 1 || n_slices > SLAM_PD_MAX_SLICES)
+        return fail(SLAM_ERR_UNSUPPORTED, "n_slices must be in 1..%d (got %d)", SLAM_PD_MAX_SLICES, n_slices);
+    if (first_index < 0 || first_index > 0x7fffffffffffLL) return fail(SLAM_ERR_INVALID, "first_index out of range");
+    if (indices)
+        for (int64_t i = 0; i < n_samples; ++i)
+            if (indices[i] < 0) return fail(SLAM_ERR_INVALID, "indices[%lld] < 0", (long long)i);
+    if (!indices && first_index + n_samples > 0xffffffffLL) return fail(SLAM_ERR_INVALID, "sample indices beyond 2^32");
+    static_assert(SLAM_PD_MAX_SPAN == kPdMaxSpan && SLAM_PD_MAX_SLICES == kPdMaxSlices, "slam_pd limits");
+    HIP_TRY(hipSetDevice(ctx->device));
+    PdSpec sp{};
+    sp.gc = gc;
+    sp.gg = gg;
+    sp.tau = t / n_slices;
+    sp.bound = bound;
+    sp.n_slices = n_slices;
+    sp.k = k;
+    sp.n_params = 6 * (k - 1) + k * (2 + 2 * n_slices);
+    sp.seed = seed;
+    // staging: indices, then parameter rows, then unitaries
+    const size_t idx_b = indices ? (size_t)n_samples * sizeof(int64_t) : 0;
+    const size_t prm_b = params_out ? (size_t)n_samples * sp.n_params * sizeof(double) : 0;
+    const size_t uni_b = unitaries_out ? (size_t)n_samples * 32 * sizeof(double) : 0;
+    HIP_TRY(ctx->pd_coords.reserve((size_t)n_samples * 3 * sizeof(double)));
+    ctx->pd_n = 0;
+    if (idx_b + prm_b + uni_b) HIP_TRY(ctx->pd_stage.reserve(idx_b + prm_b + uni_b));
+    char* st = ctx->pd_stage.as<char>();
+    if (indices) HIP_TRY(hipMemcpyAsync(st, indices, idx_b, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(pd_sample_kernel, dim3((unsigned)((n_samples + kPdBlock - 1) / kPdBlock)), dim3(kPdBlock), 0, ctx->stream, sp,
+                       first_index, n_samples, indices ? reinterpret_cast<const int64_t*>(st) : nullptr, ndigits, ctx->pd_coords.as<double>(),
+                       params_out ? reinterpret_cast<double*>(st + idx_b) : nullptr, unitaries_out ? reinterpret_cast<double*>(st + idx_b + prm_b) : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (coords_out)
+        HIP_TRY(hipMemcpyAsync(coords_out, ctx->pd_coords.p, (size_t)n_samples * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (params_out) HIP_TRY(hipMemcpyAsync(params_out, st + idx_b, prm_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (unitaries_out) HIP_TRY(hipMemcpyAsync(unitaries_out, st + idx_b + prm_b, uni_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->pd_n = n_samples;
+    return SLAM_OK;
+}
+
+int slam_pd_extremes(slam_ctx* ctx, const double* directions, int32_t n_dirs, int64_t* index_out, double* coords_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (ctx->pd_n <= 0) return fail(SLAM_ERR_STATE, "no resident samples: call slam_pd_sample first");
+    if (n_dirs < 1 || n_dirs > SLAM_PD_MAX_DIRS) return fail(SLAM_ERR_INVALID, "n_dirs must be in 1..%d (got %d)", SLAM_PD_MAX_DIRS, n_dirs);
+    if (!directions || !index_out || !coords_out) return fail(SLAM_ERR_INVALID, "NULL argument");
+    for (int32_t d = 0; d < 3 * n_dirs; ++d)
+        if (!std::isfinite(directions[d])) return fail(SLAM_ERR_INVALID, "directions must be finite");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // staging: directions [n_dirs][3], keys [n_dirs], indices [n_dirs], coordinates [n_dirs][3]
+    const size_t dir_b = (size_t)n_dirs * 3 * sizeof(double), key_b = (size_t)n_dirs * sizeof(unsigned long long);
+    const size_t idx_b = (size_t)n_dirs * sizeof(int64_t), crd_b = (size_t)n_dirs * 3 * sizeof(double);
+    HIP_TRY(ctx->pd_out.reserve(dir_b + key_b + idx_b + crd_b));
+    char* b = ctx->pd_out.as<char>();
+    HIP_TRY(hipMemcpyAsync(b, directions, dir_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(b + dir_b, 0, key_b, ctx->stream));
+    const int64_t n = ctx->pd_n;
+    hipLaunchKernelGGL(pd_extremes_kernel, dim3((unsigned)((n + kPdScanBlock - 1) / kPdScanBlock)), dim3(kPdScanBlock), 0, ctx->stream,
+                       ctx->pd_coords.as<double>(), n, reinterpret_cast<const double*>(b), n_dirs, reinterpret_cast<unsigned long long*>(b + dir_b));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(pd_gather_kernel, dim3((unsigned)((n_dirs + 63) / 64)), dim3(64), 0, ctx->stream, ctx->pd_coords.as<double>(),
+                       reinterpret_cast<const unsigned long long*>(b + dir_b), n_dirs, reinterpret_cast<int64_t*>(b + dir_b + key_b),
+                       reinterpret_cast<double*>(b + dir_b + key_b + idx_b));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(index_out, b + dir_b + key_b, idx_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(coords_out, b + dir_b + key_b + idx_b, crd_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+int slam_pd_filter(slam_ctx* ctx, const double* facets, int32_t n_facets, double eps, int64_t capacity, int64_t* n_out, int64_t* index_out,
+                   double* coords_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (ctx->pd_n <= 0) return fail(SLAM_ERR_STATE, "no resident samples: call slam_pd_sample first");
+    if (n_facets < 0 || n_facets > SLAM_PD_MAX_FACETS) return fail(SLAM_ERR_INVALID, "n_facets must be in 0..%d (got %d)", SLAM_PD_MAX_FACETS, n_facets);
+    if (n_facets > 0 && !facets) return fail(SLAM_ERR_INVALID, "facets is NULL");
+    if (!n_out || capacity < 0 || (capacity > 0 && (!index_out || !coords_out))) return fail(SLAM_ERR_INVALID, "bad output arguments");
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return fail(SLAM_ERR_INVALID, "eps must be finite and >= 0");
+    for (int32_t f = 0; f < 4 * n_facets; ++f)
+        if (!std::isfinite(facets[f])) return fail(SLAM_ERR_INVALID, "facets must be finite");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t n = ctx->pd_n;
+    // staging: facets [n_facets][4], the counter (8 bytes), indices [n], coordinates [n][3]
+    const size_t fac_b = ((size_t)n_facets * 4 * sizeof(double) + 7) & ~(size_t)7, cnt_b = 8;
+    const size_t idx_b = (size_t)n * sizeof(int64_t), crd_b = (size_t)n * 3 * sizeof(double);
+    HIP_TRY(ctx->pd_out.reserve(fac_b + cnt_b + idx_b + crd_b));
+    char* b = ctx->pd_out.as<char>();
+    if (n_facets > 0) HIP_TRY(hipMemcpyAsync(b, facets, (size_t)n_facets * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(b + fac_b, 0, cnt_b, ctx->stream));
+    hipLaunchKernelGGL(pd_filter_kernel, dim3((unsigned)((n + kPdScanBlock - 1) / kPdScanBlock)), dim3(kPdScanBlock), 0, ctx->stream,
+                       ctx->pd_coords.as<double>(), n, reinterpret_cast<const double*>(b), n_facets, eps, reinterpret_cast<unsigned int*>(b + fac_b),
+                       reinterpret_cast<int64_t*>(b + fac_b + cnt_b), reinterpret_cast<double*>(b + fac_b + cnt_b + idx_b));
+    HIP_TRY(hipGetLastError());
+    unsigned int m = 0;
+    HIP_TRY(hipMemcpyAsync(&m, b + fac_b, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *n_out = (int64_t)m;
+    const int64_t copy = (int64_t)m < capacity ? (int64_t)m : capacity;
+    if (copy > 0) {
+        HIP_TRY(hipMemcpyAsync(index_out, b + fac_b + cnt_b, (size_t)copy * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(coords_out, b + fac_b + cnt_b + idx_b, (size_t)copy * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return SLAM_OK;
+}
+
+int slam_region_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_regions, const int32_t* region_offsets, const int32_t* kinds,
+                       const int32_t* facet_offsets, const double* facets, const double* aux, double tol, int64_t* counts_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets) return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (n_regions < 1 || n_regions > SLAM_REGION_MAX) return fail(SLAM_ERR_INVALID, "n_regions must be in 1..%d (got %d)", SLAM_REGION_MAX, n_regions);
+    if (!region_offsets || !counts_out) return fail(SLAM_ERR_INVALID, "region_offsets / counts_out is NULL");
+    if (!std::isfinite(tol)) return fail(SLAM_ERR_INVALID, "tol must be finite");
+    if (region_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "region_offsets[0] must be 0");
+    for (int32_t r = 0; r < n_regions; ++r)
+        if (region_offsets[r + 1] < region_offsets[r] || region_offsets[r + 1] > 0x00ffffff)
+            return fail(SLAM_ERR_INVALID, "region_offsets must be non-decreasing and below 2^24");
+    const int32_t P = region_offsets[n_regions];
+    if (P > 0 && (!kinds || !facet_offsets)) return fail(SLAM_ERR_INVALID, "kinds / facet_offsets is NULL");
+    bool need_aux = false;
+    for (int32_t p = 0; p < P; ++p) {
+        if (kinds[p] < 0 || kinds[p] > 2) return fail(SLAM_ERR_INVALID, "kinds[%d] = %d (0 facets, 1 coverage bounds, 2 one gate)", p, kinds[p]);
+        need_aux = need_aux || kinds[p] != 0;
+    }
+    if (P > 0 && facet_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "facet_offsets[0] must be 0");
+    for (int32_t p = 0; p < P; ++p)
+        if (facet_offsets[p + 1] < facet_offsets[p] || facet_offsets[p + 1] > 0x00ffffff)
+            return fail(SLAM_ERR_INVALID, "facet_offsets must be non-decreasing and below 2^24");
+    const int64_t F = P > 0 ? facet_offsets[P] : 0;
+    if (F > 0 && !facets) return fail(SLAM_ERR_INVALID, "facets is NULL");
+    if (need_aux && !aux) return fail(SLAM_ERR_INVALID, "aux is NULL");
+    const int64_t n_counts = 2 * (int64_t)n_regions + 1;
+    std::memset(counts_out, 0, (size_t)n_counts * sizeof(int64_t));
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one upload: region offsets, kinds, facet offsets (int32), then facets [F][4] and aux [P][14] (doubles, 8-byte aligned)
+    const size_t ro_b = 0, ki_b = (size_t)(n_regions + 1) * sizeof(int32_t), fo_b = ki_b + (size_t)P * sizeof(int32_t);
+    const size_t fa_b = ((fo_b + (size_t)(P + 1) * sizeof(int32_t)) + 7) & ~(size_t)7;
+    const size_t ax_b = fa_b + (size_t)F * 4 * sizeof(double);
+    const size_t total_b = ax_b + (size_t)P * kSpanPatterns * sizeof(double);
+    HIP_TRY(ctx->reg_table.reserve(total_b));
+    HIP_TRY(ctx->reg_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
+    char* tb = ctx->reg_table.as<char>();
+    HIP_TRY(hipMemcpyAsync(tb + ro_b, region_offsets, ki_b, hipMemcpyHostToDevice, ctx->stream));
+    if (P > 0) {
+        HIP_TRY(hipMemcpyAsync(tb + ki_b, kinds, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(tb + fo_b, facet_offsets, (size_t)(P + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        if (F > 0) HIP_TRY(hipMemcpyAsync(tb + fa_b, facets, (size_t)F * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (aux) HIP_TRY(hipMemcpyAsync(tb + ax_b, aux, (size_t)P * kSpanPatterns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipMemsetAsync(ctx->reg_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
+    static_assert(SLAM_REGION_MAX == kRegionMax, "region table size");
+    hipLaunchKernelGGL(region_lookup_kernel, dim3((unsigned)((count + kRegionBlock - 1) / kRegionBlock)), dim3(kRegionBlock), 0, ctx->stream,
+                       ctx->targets.as<double>() + first * 32, count, n_regions, reinterpret_cast<const int32_t*>(tb + ro_b),
+                       reinterpret_cast<const int32_t*>(tb + ki_b), reinterpret_cast<const int32_t*>(tb + fo_b),
+                       reinterpret_cast<const double*>(tb + fa_b), reinterpret_cast<const double*>(tb + ax_b), tol,
+                       ctx->reg_counts.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counts_out, ctx->reg_counts.p, (size_t)n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,290 @@
+// slam_host.hpp -- what the host units of libslamhip.so share (internal: not installed, not part of the C ABI).
+// The units: slam_hip.hip (context, plain templates, the decompose family), slam_v2_host.hip, slam_smush_host.hip,
+// slam_geometry.hip and slam_comm.hip.  Every __global__ kernel is emitted by exactly one of them; where a unit needs another unit's
+// kernel it calls the enqueue_* function of the owner declared below.  Everything declared here has hidden visibility.
+#pragma once
+#include "../../include/slam_hip.h"
+#include "slam_types.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <algorithm>
+#include <vector>
+
+using namespace slamdev;
+
+#define SLAM_INTERNAL __attribute__((visibility("hidden")))
+
+// records the calling thread's error message (slam_last_error) and returns `code`
+SLAM_INTERNAL int fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                            \
+    do {                                                                                         \
+        hipError_t _e = (expr);                                                                  \
+        if (_e != hipSuccess)                                                                    \
+            return fail(SLAM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    } while (0)
+
+// growable device buffer
+struct SLAM_INTERNAL DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) {
+            hipError_t e = hipFree(p);
+            p = nullptr;
+            cap = 0;
+            if (e != hipSuccess) return e;
+        }
+        size_t want = bytes + bytes / 4 + 256;
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) {
+            want = bytes;
+            e = hipMalloc(&p, want);
+        }
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() { return static_cast<T*>(p); }
+};
+
+struct slam_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_a[SLAM_MAX_SPAN_EVAL + 1] = {}, ev_b[SLAM_MAX_SPAN_EVAL + 1] = {};  // optimizer-kernel bracket per span
+    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr; // whole-call bracket
+    // The host waits for a finished span loop on a blocking-sync event: the waiting thread sleeps instead of
+    // spinning, so that many contexts (one host thread each) can be in flight without the threads fighting
+    // over cores.  (Measured: with spinning waits, 32 batches in flight run 30 % slower than 16.)
+    hipEvent_t ev_done = nullptr;
+    StageCtl* h_ctl = nullptr;                   // pinned: the stages' control blocks, copied back once per call
+    double* h_gates = nullptr;                   // pinned mirror of span_gates
+    void* h_stage = nullptr;                     // pinned staging for result fetches (same reason: no spinning
+    size_t h_stage_cap = 0;                      // inside the runtime's pageable-copy path)
+    int64_t n_targets = 0;
+    int32_t n_gates = 0;
+    DevBuf targets, gates;
+    // stage work buffers
+    DevBuf active, active2, x0;
+    DevBuf item_rec, item_x;  // per work item: one 32-byte result record (slam_types.hpp: ItemRec), the parameter row
+    DevBuf stage_loss, stage_x, stage_restart;
+    // decompose results
+    DevBuf best_loss, best_x, best_cycles, span_loss;
+    DevBuf v2_hmem;              // inverse Hessians of the long parametrised-gate templates (slam_v2.hpp: v2_h_in_memory)
+    DevBuf v2_maps, v2_bounds;   // slam_v2_*: staged gate maps [SLAM_MAX_SPAN_EVAL], (init_lo, init_hi, bound_lo, bound_hi)[n]
+    std::vector<V2GateMap> v2_gates_host;
+    int v2_qn = 0;
+    // cost constraint per span (slam_v2_set_constraint): weights [n(k)] on the device, right-hand side; empty = none
+    DevBuf v2_cons_w[SLAM_V2_MAX_SPAN + 1];
+    int v2_cons_n[SLAM_V2_MAX_SPAN + 1] = {0};
+    double v2_cons_max[SLAM_V2_MAX_SPAN + 1] = {0};
+    double v2_cons_rho[SLAM_V2_MAX_SPAN + 1] = {0};  // penalty parameter of the multiplier method: 30 / max_i w_i^2
+    DevBuf trace_loss, trace_x;  // slam_minimize_stage_trace
+    int32_t trace_cap = 0;       // > 0 only inside slam_minimize_stage_trace
+    double stage_exit_loss = -1.0;  // single-stage calls: >= 0 overrides stop_loss as the ordered early-exit level
+    int32_t result_nmax = 0;
+    int64_t result_filled = 0;  // targets whose resident results have been initialised (+inf / -1) for result_nmax
+    DevBuf counters;  // StageCtl[SLAM_MAX_SPAN_EVAL + 2]: one control block per span stage (slam_types.hpp)
+    DevBuf long_hmem;  // inverse Hessian approximations of the wavefront-per-item kernels: [resident wavefronts][n][128] floats
+    DevBuf bucket_lists, bucket_counts;  // slam_decompose_predicted: per-size target lists [k_max][count], their sizes
+    int32_t* h_bucket_counts = nullptr;  // pinned mirror of bucket_counts
+    DevBuf solved;
+    DevBuf stage_targets;
+    DevBuf span_gates;  // 64 slots x [SLAM_MAX_SPAN_EVAL][32] doubles
+    struct StagedSeq { bool valid = false; int32_t seq[SLAM_MAX_SPAN_EVAL] = {}; } staged[SLAM_MAX_SPAN_EVAL + 1];
+    int cost_kind = 0;  // SLAM_COST_*
+    std::vector<double> gates_host;
+    int compute_units = 0;
+    int reserve_waves = 0;  // wavefront slots the persistent optimizer grid leaves free for the span loop's bookkeeping kernels
+    int64_t resident_waves[SLAM_MAX_SPAN_EVAL + 1][kGateClasses] = {};
+    // eval buffers
+    DevBuf ev_x, ev_tof, ev_loss, ev_grad, ev_unitary, ev_weyl;
+    DevBuf cov_table, cov_counts, cov_entries;  // slam_coverage_lookup: offsets / kinds / points / bounds, counts, entry per target
+    slam_stats stats{};
+    bool max_lds_set[SLAM_MAX_SPAN_EVAL + 1][kGateClasses][3] = {};  // [.][.][0] eval kernel, [1] optimizer kernel, [2] its multi-queue form
+    int64_t resident_waves_mq[SLAM_MAX_SPAN_EVAL + 1][kGateClasses] = {};
+    int64_t resident_waves_long = 0;  // wavefront-per-item kernels (slam_long.hpp): resident wavefronts; 0 = not asked yet
+    bool long_eval_ready = false;
+    // MakhlinFunctionalCost kernels (eval_mk_kernel / minimize_mk_kernel / the *_long_mk_kernel pair): attributes set, resident wavefronts
+    bool mk_lds_set[SLAM_MAX_SPAN_QUAD + 1][2] = {};
+    int64_t resident_waves_mk[SLAM_MAX_SPAN_QUAD + 1] = {};
+    int64_t resident_waves_long_mk = 0;
+    bool long_eval_mk_ready = false;
+    int64_t resident_waves_wl[kGateClasses] = {};  // span_wave_kernel<GC>: resident wavefronts (0 = not asked yet)
+    // speculative spans (span_spec_kernel): staging rows, two side streams, fork / join events
+    DevBuf spec_loss, spec_x, spec_ev;
+    hipStream_t spec_stream[2] = {nullptr, nullptr};
+    hipEvent_t spec_fork = nullptr, spec_join[2] = {nullptr, nullptr};
+    bool spec_attr_set[4][kGateClasses] = {};
+    // overlapped spans (decompose_overlapped): one helper context per span (own stream, own stage buffers; targets borrowed)
+    slam_ctx* helper[SLAM_MAX_SPAN_EVAL + 1] = {};
+    hipEvent_t ov_fork = nullptr, ov_join[SLAM_MAX_SPAN_EVAL + 1] = {};
+    DevBuf slot_ev;                 // (helper side) per-slot evaluation counts of its stage
+    bool slot_ev_on = false;        // (helper side) single-stage reductions write slot_ev instead of the stage's counters
+    uint64_t gates_version = 1;     // bumped by slam_set_gates
+    uint64_t helper_gates_version = 0;  // (helper side) the owner's gates_version its gate table is a copy of
+    // slam_decompose_multi (this context leads the call): the sub-problems' argument blocks / epilogue arguments per span, staged
+    // through pinned memory
+    DevBuf mq_args;
+    void* h_mq_args = nullptr;
+    size_t h_mq_cap = 0;
+    int v2_per_cu[SLAM_V2_MAX_SPAN + 1][3][2][2] = {};  // resident workgroups per CU of minimize_v2_kernel<K, QN, GQ, FREE> (0 = not asked yet)
+    // slam_smush_* (slam_smush.hpp): gate table, staged maps of a span, inverse Hessians of the resident wavefronts
+    std::vector<SmushMap> smush_gates_host;
+    int smush_qn = 0;
+    DevBuf smush_maps, smush_hmem;
+    int64_t resident_waves_smush = 0;  // 0 = not asked yet
+    // slam_pd_* / slam_region_lookup (slam_pd.hpp): resident sample coordinates [pd_n][3], per-call staging, region tables
+    DevBuf pd_coords, pd_stage, pd_out, reg_table, reg_counts;
+    int64_t pd_n = 0;
+
+    ~slam_ctx() {
+        DevBuf* all[] = {&targets, &gates, &active, &active2, &x0, &item_rec, &item_x, &stage_loss, &stage_x, &stage_restart, &best_loss,
+                         &best_x, &best_cycles, &span_loss, &trace_loss, &trace_x, &v2_maps, &v2_bounds, &v2_hmem, &long_hmem, &bucket_lists, &bucket_counts, &v2_cons_w[0], &v2_cons_w[1], &v2_cons_w[2], &v2_cons_w[3], &v2_cons_w[4], &v2_cons_w[5], &counters, &solved, &stage_targets, &span_gates, &ev_x, &ev_tof, &ev_loss, &ev_grad, &ev_unitary, &ev_weyl};
+        for (DevBuf* b : all) b->release();
+        for (hipEvent_t e : ev_a) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_b) if (e) (void)hipEventDestroy(e);
+        if (ev_t0) (void)hipEventDestroy(ev_t0);
+        if (ev_t1) (void)hipEventDestroy(ev_t1);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (h_ctl) (void)hipHostFree(h_ctl);
+        if (h_stage) (void)hipHostFree(h_stage);
+        if (h_gates) (void)hipHostFree(h_gates);
+        if (h_bucket_counts) (void)hipHostFree(h_bucket_counts);
+        if (h_mq_args) (void)hipHostFree(h_mq_args);
+        mq_args.release();
+        spec_loss.release();
+        spec_x.release();
+        spec_ev.release();
+        slot_ev.release();
+        smush_maps.release();
+        smush_hmem.release();
+        cov_table.release();
+        cov_counts.release();
+        cov_entries.release();
+        for (DevBuf* b : {&pd_coords, &pd_stage, &pd_out, &reg_table, &reg_counts}) b->release();
+        if (ov_fork) (void)hipEventDestroy(ov_fork);
+        for (hipEvent_t e : ov_join) if (e) (void)hipEventDestroy(e);
+        for (slam_ctx* h : helper) {
+            if (!h) continue;
+            h->targets.p = nullptr;  // borrowed from this context
+            h->targets.cap = 0;
+            delete h;
+        }
+        if (spec_fork) (void)hipEventDestroy(spec_fork);
+        for (int j = 0; j < 2; ++j) {
+            if (spec_join[j]) (void)hipEventDestroy(spec_join[j]);
+            if (spec_stream[j]) (void)hipStreamDestroy(spec_stream[j]);
+        }
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// ---- slam_hip.hip ----------------------------------------------------------------------------------------------------
+// Every API call leaves the context's stream drained: the per-span gate slots, the pinned staging buffers and
+// DevBuf::reserve's hipFree rely on it.  A call that fails after it has enqueued work therefore waits for that work
+// (ignoring the result: the error being reported is the first one) and forgets the cached gate slots.
+SLAM_INTERNAL int drained(slam_ctx* c, int rc);
+SLAM_INTERNAL int check_params(const slam_opt_params* p);
+inline StageCtl* stage_ctl(slam_ctx* c, int k) { return c->counters.as<StageCtl>() + k; }
+// After the stream has drained: fold the stages' control blocks and kernel brackets into the statistics.
+SLAM_INTERNAL int collect_stats(slam_ctx* c, int k_min, int k_max, const StageCtl* h_ctl, int restarts);
+// Resident results with rows of nmax parameters: (re)allocated and, where new, filled with (+inf, -1).
+SLAM_INTERNAL int ensure_results_n(slam_ctx* c, int nmax);
+
+// Results of the window [first, first + count) on their way to the host: small windows go through pinned
+// staging (asynchronous copies, no spinning inside the runtime's pageable path), big ones straight into the
+// caller's arrays.  enqueue_fetch only enqueues; finish_fetch runs after the stream has drained.
+struct FetchReq {
+    double* best_loss;
+    double* best_x;
+    int32_t* best_cycles;
+    size_t b_loss = 0, b_x = 0, b_cyc = 0;
+    bool staged = false;
+};
+
+SLAM_INTERNAL int enqueue_fetch_n(slam_ctx* ctx, int nmax, int64_t first, int64_t count, FetchReq& fr);
+SLAM_INTERNAL void finish_fetch(slam_ctx* ctx, const FetchReq& fr);
+
+// Per-item results of a single-stage call for the host: the records come over as they are and are unpacked into the
+// caller's arrays (any of which may be NULL).  The stream is idle (the caller has waited for the stage).
+SLAM_INTERNAL int fetch_item_records(slam_ctx* c, int64_t M, double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals);
+
+// The bookkeeping kernels (slam_kernels.hpp), enqueued on behalf of the other units:
+// set_n_active_kernel on c's stream: stage k works on n_active targets
+SLAM_INTERNAL int enqueue_set_n_active(slam_ctx* c, int k, int64_t n_active);
+// init_results_kernel on `stream`: resets the results of the n targets of the window [first, first + n) -- of the list already in
+// d_active with list_mode -- clears c's control blocks, publishes n as stage k_min's target count and, with d_active != nullptr,
+// writes the first active list and gathers the first stage's targets
+SLAM_INTERNAL int enqueue_init_results(slam_ctx* c, hipStream_t stream, int32_t* d_active, int64_t first, int64_t n, int k_min, int list_mode);
+// the epilogue of a span-loop stage with at most n_upper targets on c's stream: picks the kernel by n_upper
+SLAM_INTERNAL int enqueue_stage_epilogue(slam_ctx* c, int64_t n_upper, const EpilogueArgs& e);
+
+// Steps that the single-stage calls of the parametrised-gate families (slam_v2_*, slam_smush_*) share word for word:
+// (init_lo, init_hi, bound_lo, bound_hi) checked and packed into b[4 n]; *bounded: some bound is finite
+SLAM_INTERNAL int pack_stage_bounds(int n, const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi, double* b,
+                                    bool* bounded);
+// the caller's active list checked and copied into c->active (*d_active stays nullptr without one)
+SLAM_INTERNAL int upload_stage_active(slam_ctx* c, const int32_t* active, int64_t n_active, const int32_t** d_active);
+// explicit start points x0[count] checked and copied into c->x0 (*d_x0 stays nullptr without them); also the plain path's
+SLAM_INTERNAL int upload_stage_x0(slam_ctx* c, const double* x0, int64_t count, const double** d_x0);
+// after the optimizer kernel of stage k (rows of n parameters): the reduction over restarts (ordered winner rule), the results, the
+// per-item records and the statistics brought back
+SLAM_INTERNAL int finish_single_stage(slam_ctx* c, int k, int n, int64_t n_active, const slam_opt_params* prm, double exit_loss, double* best_loss,
+                                      double* best_x, int32_t* best_restart, double* item_loss, int32_t* item_iters, int32_t* item_status,
+                                      int32_t* item_evals);
+
+// ---- slam_geometry.hip ------------------------------------------------------------------------------------------------
+// c1c2c3_kernel on c's stream: Weyl coordinates of `count` unitaries in device memory into d_out[count][3]
+SLAM_INTERNAL int enqueue_c1c2c3(slam_ctx* c, const double* d_unitaries, int64_t count, int ndigits, double* d_out);
+// span_predict_kernel on c's stream: template sizes of the resident targets [first, first + count) into d_spans
+SLAM_INTERNAL int enqueue_span_predict(slam_ctx* c, int64_t first, int64_t count, int k_max, const double* point, const double* bounds, double tol,
+                                       int32_t* d_spans);
+
+// ---- the three *_minimize_stage_trace entry points --------------------------------------------------------------------
+// `span` checks k for the family and gives the template's parameter count; `stage` is the family's single-stage call, run with
+// ctx->trace_cap set.
+template <class Span, class Stage>
+int minimize_stage_trace(slam_ctx* ctx, const int32_t* active, int64_t n_active, const slam_opt_params* params, int32_t trace_cap,
+                         double* trace_loss, double* trace_x, Span span, Stage stage) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (!params) return fail(SLAM_ERR_INVALID, "params is NULL");
+    if (trace_cap <= 0 || !trace_loss || !trace_x) return fail(SLAM_ERR_INVALID, "trace buffers and trace_cap > 0 are required");
+    int n = 0;
+    int rc = span(&n);
+    if (rc) return rc;
+    if (!active) n_active = ctx->n_targets;
+    if (n_active <= 0 || params->restarts <= 0) return fail(SLAM_ERR_INVALID, "nothing to trace");
+    const int64_t M = n_active * (int64_t)params->restarts;
+    const size_t rows = (size_t)M * (size_t)trace_cap;
+    if (rows * (size_t)(n + 1) * sizeof(double) > ((size_t)4 << 30))
+        return fail(SLAM_ERR_INVALID, "trace of %lld items x %d iterations exceeds 4 GiB: trace fewer targets at a time", (long long)M, trace_cap);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->trace_loss.reserve(rows * sizeof(double)));
+    HIP_TRY(ctx->trace_x.reserve(rows * n * sizeof(double)));
+    // rows that no iteration reaches read as NaN
+    HIP_TRY(hipMemsetAsync(ctx->trace_loss.p, 0xFF, rows * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->trace_x.p, 0xFF, rows * n * sizeof(double), ctx->stream));
+    ctx->trace_cap = trace_cap;
+    rc = stage();
+    ctx->trace_cap = 0;
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(trace_loss, ctx->trace_loss.p, rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(trace_x, ctx->trace_x.p, rows * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}

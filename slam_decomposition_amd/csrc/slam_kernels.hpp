@@ -25,17 +25,7 @@ constexpr double kGrowMax = 1048576.0;  // happening).  Covers negative curvatur
 constexpr int kRestartPeriod = 128;
 static_assert((kRestartPeriod & (kRestartPeriod - 1)) == 0, "the periodic restart tests iters & (period - 1)");
 
-// One finished (or dropped) work item: the five scalars of its result as ONE 32-byte record = one sector, written by one lane as two
-// 16-byte stores (round 3 wrote them into five arrays: five partial-sector stores per item, WRITE_SIZE 2.2x the payload)
-struct __attribute__((aligned(32))) ItemRec {
-    double loss;
-    int32_t iters;
-    int32_t status;
-    int32_t evals;   // all loss+gradient evaluations of the item
-    int32_t acc;     // those whose point was accepted
-    int32_t pad[2];
-};
-static_assert(sizeof(ItemRec) == 32, "ItemRec layout");
+// (ItemRec, the record of one finished work item: slam_types.hpp)
 __device__ __forceinline__ unsigned long long pack2(int lo, int hi) { return (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32); }
 __device__ __forceinline__ void item_rec_store(ItemRec* r, double loss, int iters, int status, int evals, int acc) {
     // (field by field, all into the one sector: paired into 8- or 16-byte stores the operands need aligned register pairs / quads, and
@@ -57,19 +47,7 @@ __device__ __forceinline__ void item_rec_store_dropped(ItemRec* r, int status) {
 
 enum : int { ST_CONVERGED = 0, ST_MAXITER = 1, ST_LINESEARCH = 2, ST_NONFINITE = 3, ST_STALLED = 4, ST_PREEMPTED = 5 };
 
-// Device-side control block of one span stage.  The span loop (optimizer.py:233-303) is enqueued as one
-// chain of kernels without host round trips: the number of targets a stage works on is produced on the
-// device by the previous stage's compaction, and every kernel of the stage reads it from here.
-struct StageCtl {
-    unsigned long long evals;    // += fused loss+gradient evaluations (reduce kernel)
-    unsigned long long rounds;   // += lock-step evaluation rounds of every wavefront
-    unsigned int work_counter;   // work queue of the optimizer kernel
-    int32_t n_active;            // targets of this stage (written by init / the previous stage's compaction)
-    unsigned long long evals_accepted;   // += evaluations whose point was accepted (initial point or Armijo step)
-    unsigned long long evals_preempted;  // += evaluations of items that ended pre-empted by a sibling restart
-    int32_t pad[6];
-};
-static_assert(sizeof(StageCtl) == 64, "StageCtl layout");
+// (StageCtl, a stage's control block: slam_types.hpp)
 
 // internal bit of MinimizeArgs::flags (beside SLAM_FLAG_*): the launch records per-iteration traces
 constexpr uint32_t kFlagTrace = 0x100u;
@@ -999,6 +977,9 @@ struct SpanMergeArgs {
     double* span_loss;
 };
 
+// The plain __global__ kernels of the span loop's bookkeeping are emitted by the one unit that defines SLAM_STAGE_KERNELS (slam_hip.hip),
+// which enqueues them for the others (slam_host.hpp).
+#ifdef SLAM_STAGE_KERNELS
 __global__ void __launch_bounds__(kWave) span_merge_kernel(SpanMergeArgs a) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const bool live = i < a.count;
@@ -1052,34 +1033,9 @@ __global__ void __launch_bounds__(kWave) span_merge_kernel(SpanMergeArgs a) {
     const double* src = cyc >= 1 ? a.x[cyc] + (int64_t)i * a.xstride[cyc] : nullptr;
     for (int j = 0; j < a.nmax; ++j) a.best_x[(int64_t)t * a.nmax + j] = j < nv ? src[j] : 0.0;
 }
+#endif
 
-// ---------------------------------------------------------------------------------
-// per-target reduction over restarts: argmin of item_loss (ties -> lowest restart), then the span loop's
-// bookkeeping (TemplateOptimizer._run, optimizer.py:281-303): "if best_result is None or result.fun <
-// best_result" the stage result replaces the target's best (loss, parameters, cycles).
-// ---------------------------------------------------------------------------------
-struct ReduceArgs {
-    const ItemRec* item_rec;   // [n_active * R]
-    const double* item_x;      // [n_active * R][n]
-    double exit_loss;          // ordered == 1: the winner is the lowest-index restart below exit_loss (else the argmin)
-    int32_t ordered;
-    StageCtl* ctl;             // n_active; evals += sum of item_evals
-    int32_t restarts;
-    int32_t n;                 // parameters at this span
-    double* stage_loss;        // [n_active]
-    double* stage_x;           // [n_active][n]
-    int32_t* stage_restart;    // [n_active]
-    // merge into the resident results (best_loss == nullptr: single-stage call, no merge)
-    const int32_t* active;     // [n_active] target index of each stage slot (nullptr = identity)
-    int32_t nmax;
-    int32_t k;
-    double* best_loss;         // [n_targets]
-    double* best_x;            // [n_targets][nmax]
-    int32_t* best_cycles;      // [n_targets]
-    double* span_loss;         // [n_targets][kSpanLossStride]: running best after span k at [k - 1] ("Cycle (k =...), Best Loss")
-    // overlapped spans: the slot's evaluation counts (all, accepted, pre-empted) go here instead of into ctl -- the merge books them
-    unsigned long long* slot_ev;  // [n_active][3] or nullptr
-};
+// per-target reduction over restarts (ReduceArgs: slam_types.hpp)
 
 struct EvalCounts {
     unsigned long long all = 0, accepted = 0, preempted = 0;
@@ -1160,6 +1116,7 @@ __device__ __forceinline__ void publish_eval_counts(StageCtl* ctl, EvalCounts ev
     }
 }
 
+#ifdef SLAM_STAGE_KERNELS
 __global__ void reduce_merge_kernel(ReduceArgs a) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     EvalCounts ev;
@@ -1280,6 +1237,7 @@ __global__ void fill_results_kernel(double* best_loss, int32_t* best_cycles, dou
         for (int j = 0; j < kSpanLossStride; ++j) span_loss[t * kSpanLossStride + j] = NAN;
     }
 }
+#endif
 
 // Ordered compaction of the targets that still need a longer template:
 // keep t iff !(best_loss[t] < threshold)   (optimizer.py:301: break when best < threshold).
@@ -1319,16 +1277,7 @@ __device__ __forceinline__ int32_t compact_block(const int32_t* active_in, int64
 // optimizer waves (hundreds of microseconds each under load), so the chain is kept as short as possible.
 constexpr int64_t kEpilogueMaxTargets = 8192;
 
-struct EpilogueArgs {
-    ReduceArgs r;
-    int32_t has_next;
-    double threshold;
-    int32_t* active_out;     // [n_upper] next stage's active list
-    StageCtl* next;
-    const double* targets;   // resident targets
-    double* stage_targets;   // next stage's gathered targets
-    int32_t* solved;
-};
+// (EpilogueArgs: slam_types.hpp)
 
 // NT = 256 for the smallest batches: a 4-wave workgroup finds room on a busy GPU much sooner than a 16-wave one.
 template <int NT>
@@ -1396,11 +1345,13 @@ __device__ __forceinline__ void stage_epilogue_grid_body(const EpilogueArgs& a) 
     double2* dst = reinterpret_cast<double2*>(a.stage_targets) + (int64_t)base * 16;
     for (int e = tid; e < tot * 16; e += 256) dst[e] = src[(int64_t)kept_t[e >> 4] * 16 + (e & 15)];
 }
+#ifdef SLAM_STAGE_KERNELS
 __global__ void __launch_bounds__(256) stage_epilogue_grid_kernel(EpilogueArgs a) { stage_epilogue_grid_body(a); }
 // slam_decompose_multi: the same for n_sub sub-problems in one launch (blockIdx.y = sub-problem, its arguments in device memory)
 __global__ void __launch_bounds__(256) stage_epilogue_multi_kernel(const EpilogueArgs* arr) {
     const EpilogueArgs a = arr[blockIdx.y];
     stage_epilogue_grid_body(a);
 }
+#endif
 
 }  // namespace slamdev

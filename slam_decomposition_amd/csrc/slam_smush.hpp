@@ -31,21 +31,7 @@
 
 namespace slamdev {
 
-constexpr int kSmushMaxSpan = 6;
-constexpr int kSmushMaxLayers = kSmushMaxSpan + 1;
-constexpr int kSmushMaxSlices = 58;                       // SLAM_SMUSH_MAX_SLICES
-constexpr int kSmushRaw = 2 + 2 * kSmushMaxSlices;        // raw order: gc, gg, gx[0..N), gy[0..N)
-constexpr int kSmushNP = 128;                             // n <= 128: lane l holds components 2 l, 2 l + 1
-
-// device copy of slam_smush_gate (include/slam_hip.h): same layout
-struct SmushMap {
-    int32_t qn;
-    int32_t n_slices;
-    double t;
-    int32_t sel[kSmushRaw];
-    double scale[kSmushRaw];
-    double offset[kSmushRaw];
-};
+// (kSmushMaxSpan, kSmushMaxSlices, kSmushRaw, kSmushNP and SmushMap, the device copy of slam_smush_gate: slam_types.hpp)
 
 // LDS of one wavefront, in doubles
 constexpr int kSmOffTbl = 0;                                   // sincos table (64 double2)

@@ -1,0 +1,242 @@
+// slam_smush_host.hip -- host side of libslamhip.so, parallel-drive unit: slam_smush_* (CircuitTemplateV2(param_vec_expand=...),
+// ConversionGainSmushGate) on the kernels of slam_smush.hpp.  The reduction over restarts is enqueued through slam_hip.hip (slam_host.hpp).
+#include "slam_host.hpp"
+#include "slam_smush.hpp"
+
+static_assert(sizeof(SmushMap) == sizeof(slam_smush_gate), "SmushMap mirrors slam_smush_gate");
+static_assert(kSmushMaxSlices == SLAM_SMUSH_MAX_SLICES && kSmushMaxSpan == SLAM_SMUSH_MAX_SPAN && kSmushNP == SLAM_SMUSH_MAX_N, "smush limits");
+namespace {
+
+int smush_check(slam_ctx* c, int k) {
+    if (!c) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (c->cost_kind == SLAM_COST_MAKHLIN)
+        return fail(SLAM_ERR_UNSUPPORTED, "smush-gate templates do not run MakhlinFunctionalCost (SLAM_COST_MAKHLIN)");
+    if (c->smush_gates_host.empty()) return fail(SLAM_ERR_STATE, "no smush gates: call slam_smush_set_gates first");
+    if (k < 1 || k > SLAM_SMUSH_MAX_SPAN) return fail(SLAM_ERR_UNSUPPORTED, "smush-gate templates support spans 1..%d (got %d)", SLAM_SMUSH_MAX_SPAN, k);
+    const int n = 6 * (k + 1) + c->smush_qn * k;
+    if (n > SLAM_SMUSH_MAX_N)
+        return fail(SLAM_ERR_UNSUPPORTED, "span %d with %d parameters per gate has %d parameters: at most %d", k, c->smush_qn, n, SLAM_SMUSH_MAX_N);
+    return SLAM_OK;
+}
+
+int smush_stage_maps(slam_ctx* c, int k, const int32_t* gate_seq, const SmushMap** d_out) {
+    if (!gate_seq) return fail(SLAM_ERR_INVALID, "gate_seq is NULL");
+    std::vector<SmushMap> tmp((size_t)k);
+    for (int j = 0; j < k; ++j) {
+        if (gate_seq[j] < 0 || gate_seq[j] >= (int)c->smush_gates_host.size())
+            return fail(SLAM_ERR_INVALID, "gate_seq[%d] = %d outside the smush gate table (%d gates)", j, gate_seq[j], (int)c->smush_gates_host.size());
+        tmp[(size_t)j] = c->smush_gates_host[(size_t)gate_seq[j]];
+    }
+    HIP_TRY(c->smush_maps.reserve(sizeof(SmushMap) * SLAM_SMUSH_MAX_SPAN));
+    HIP_TRY(hipMemcpyAsync(c->smush_maps.p, tmp.data(), sizeof(SmushMap) * (size_t)k, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // tmp is a local buffer
+    *d_out = c->smush_maps.as<SmushMap>();
+    return SLAM_OK;
+}
+
+int smush_eval_body(slam_ctx* c, int k, const int32_t* gate_seq, const double* x, const int32_t* target_of, int64_t M, double* loss,
+                    double* grad, double* unitary) {
+    int rc = smush_check(c, k);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->n_targets <= 0) return fail(SLAM_ERR_STATE, "no targets: call slam_set_targets first");
+    if (M < 0) return fail(SLAM_ERR_INVALID, "M < 0");
+    if (M == 0) return SLAM_OK;
+    if (!x || !target_of || !loss) return fail(SLAM_ERR_INVALID, "x, target_of and loss must be non-NULL");
+    for (int64_t m = 0; m < M; ++m)
+        if (target_of[m] < 0 || target_of[m] >= c->n_targets) return fail(SLAM_ERR_INVALID, "target_of[%lld] outside the resident batch", (long long)m);
+    const SmushMap* d_maps = nullptr;
+    rc = smush_stage_maps(c, k, gate_seq, &d_maps);
+    if (rc) return rc;
+    const int n = 6 * (k + 1) + c->smush_qn * k;
+    HIP_TRY(c->ev_x.reserve((size_t)M * n * sizeof(double)));
+    HIP_TRY(c->ev_tof.reserve((size_t)M * sizeof(int32_t)));
+    HIP_TRY(c->ev_loss.reserve((size_t)M * sizeof(double)));
+    if (grad) HIP_TRY(c->ev_grad.reserve((size_t)M * n * sizeof(double)));
+    if (unitary) HIP_TRY(c->ev_unitary.reserve((size_t)M * 32 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(c->ev_x.p, x, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ev_tof.p, target_of, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    SmushEvalArgs a{};
+    a.targets = c->targets.as<double>();
+    a.x = c->ev_x.as<double>();
+    a.target_of = c->ev_tof.as<int32_t>();
+    a.n_items = M;
+    a.loss = c->ev_loss.as<double>();
+    a.grad = grad ? c->ev_grad.as<double>() : nullptr;
+    a.unitary = unitary ? c->ev_unitary.as<double>() : nullptr;
+    a.cost_kind = c->cost_kind;
+    a.maps = d_maps;
+    a.k = k;
+    a.qn = c->smush_qn;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_smush_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmLdsBytes));
+    const int64_t blocks = std::min<int64_t>(M, (int64_t)std::max(1, c->compute_units) * 16);
+    hipLaunchKernelGGL(eval_smush_kernel, dim3((unsigned)blocks), dim3(kWave), kSmLdsBytes, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(loss, c->ev_loss.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (grad) HIP_TRY(hipMemcpyAsync(grad, c->ev_grad.p, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (unitary) HIP_TRY(hipMemcpyAsync(unitary, c->ev_unitary.p, (size_t)M * 32 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SLAM_OK;
+}
+
+int smush_minimize_body(slam_ctx* c, int k, const int32_t* gate_seq, const int32_t* active, int64_t n_active, const double* x0,
+                        const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi,
+                        const slam_opt_params* prm, double exit_loss, double* best_loss, double* best_x, int32_t* best_restart,
+                        double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals) {
+    int rc = smush_check(c, k);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->n_targets <= 0) return fail(SLAM_ERR_STATE, "no targets: call slam_set_targets first");
+    rc = check_params(prm);
+    if (rc) return rc;
+    if (!active) n_active = c->n_targets;
+    if (n_active <= 0) return n_active == 0 ? SLAM_OK : fail(SLAM_ERR_INVALID, "n_active < 0");
+    if (!best_loss || !best_x) return fail(SLAM_ERR_INVALID, "best_loss and best_x must be non-NULL");
+    if (!init_lo || !init_hi) return fail(SLAM_ERR_INVALID, "init_lo and init_hi must be non-NULL");
+    const int n = 6 * (k + 1) + c->smush_qn * k;
+    const int64_t M = n_active * (int64_t)prm->restarts;
+    std::vector<double> b((size_t)4 * n);
+    bool bounded = false;
+    rc = pack_stage_bounds(n, init_lo, init_hi, bound_lo, bound_hi, b.data(), &bounded);
+    if (rc) return rc;
+    const SmushMap* d_maps = nullptr;
+    rc = smush_stage_maps(c, k, gate_seq, &d_maps);
+    if (rc) return rc;
+    const int32_t* d_active = nullptr;
+    rc = upload_stage_active(c, active, n_active, &d_active);
+    if (rc) return rc;
+    const double* d_x0 = nullptr;
+    rc = upload_stage_x0(c, x0, M * n, &d_x0);
+    if (rc) return rc;
+    HIP_TRY(c->v2_bounds.reserve(b.size() * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(c->v2_bounds.p, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // b is a local buffer
+    HIP_TRY(c->item_rec.reserve(M * sizeof(ItemRec)));
+    HIP_TRY(c->item_x.reserve(M * n * sizeof(double)));
+    HIP_TRY(c->stage_loss.reserve(n_active * sizeof(double)));
+    HIP_TRY(c->stage_x.reserve(n_active * n * sizeof(double)));
+    HIP_TRY(c->stage_restart.reserve(n_active * sizeof(int32_t)));
+    HIP_TRY(c->counters.reserve(sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2)));
+    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), c->stream));
+    rc = enqueue_set_n_active(c, k, n_active);
+    if (rc) return rc;
+    HIP_TRY(c->solved.reserve((size_t)n_active * sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(c->solved.p, 0, (size_t)n_active * sizeof(int32_t), c->stream));
+    const void* kern = reinterpret_cast<const void*>(&minimize_smush_kernel);
+    if (c->resident_waves_smush == 0) {
+        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmLdsBytes));
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, kSmLdsBytes));
+        c->resident_waves_smush = (int64_t)(per_cu < 1 ? 1 : per_cu) * std::max(1, c->compute_units);
+    }
+    int64_t blocks = std::min<int64_t>(M, c->resident_waves_smush);
+    if (blocks < 1) blocks = 1;
+    HIP_TRY(c->smush_hmem.reserve((size_t)c->resident_waves_smush * (size_t)SLAM_SMUSH_MAX_N * kSmushNP * sizeof(float)));
+    SmushArgs a{};
+    a.targets = c->targets.as<double>();
+    a.active = d_active;
+    a.n_active = (int32_t)n_active;
+    a.restarts = prm->restarts;
+    a.x0 = d_x0;
+    a.init_lo = c->v2_bounds.as<double>();
+    a.init_hi = a.init_lo + n;
+    a.bound_lo = a.init_lo + 2 * n;
+    a.bound_hi = a.init_lo + 3 * n;
+    a.maxiter = prm->maxiter;
+    a.gtol = prm->gtol;
+    a.stop_loss = prm->stop_loss;
+    a.gtol_far = prm->gtol_far;
+    a.far_loss = prm->far_loss;
+    a.exit_loss = exit_loss;
+    a.flags = prm->flags & (SLAM_FLAG_EARLY_EXIT | SLAM_FLAG_ORDERED);
+    a.seed = prm->seed;
+    a.target_base = prm->target_base;
+    a.cost_kind = c->cost_kind;
+    a.maps = d_maps;
+    a.k = k;
+    a.qn = c->smush_qn;
+    a.bounded = bounded ? 1 : 0;
+    a.solved = c->solved.as<int32_t>();
+    a.item_rec = c->item_rec.as<ItemRec>();
+    a.item_x = c->item_x.as<double>();
+    a.ctl = stage_ctl(c, k);
+    a.hmem = c->smush_hmem.as<float>();
+    a.trace_cap = c->trace_cap;
+    a.trace_loss = c->trace_cap > 0 ? c->trace_loss.as<double>() : nullptr;
+    a.trace_x = c->trace_cap > 0 ? c->trace_x.as<double>() : nullptr;
+    HIP_TRY(hipEventRecord(c->ev_a[k], c->stream));
+    hipLaunchKernelGGL(minimize_smush_kernel, dim3((unsigned)blocks), dim3(kWave), kSmLdsBytes, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_b[k], c->stream));
+    return finish_single_stage(c, k, n, n_active, prm, exit_loss, best_loss, best_x, best_restart, item_loss, item_iters, item_status, item_evals);
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_smush_set_gates(slam_ctx* ctx, const slam_smush_gate* gates, int32_t n_gates) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (!gates || n_gates <= 0 || n_gates > SLAM_MAX_GATES) return fail(SLAM_ERR_INVALID, "n_gates must be in 1..%d", SLAM_MAX_GATES);
+    const int qn = gates[0].n_params;
+    if (qn < 1 || qn > SLAM_SMUSH_MAX_N - 12) return fail(SLAM_ERR_UNSUPPORTED, "smush gates take 1..%d parameters (got %d)", SLAM_SMUSH_MAX_N - 12, qn);
+    std::vector<SmushMap> tmp((size_t)n_gates);
+    for (int g = 0; g < n_gates; ++g) {
+        const slam_smush_gate& s = gates[g];
+        if (s.n_params != qn) return fail(SLAM_ERR_UNSUPPORTED, "all smush gates of a template must take the same number of parameters");
+        if (s.n_slices < 1 || s.n_slices > SLAM_SMUSH_MAX_SLICES)
+            return fail(SLAM_ERR_UNSUPPORTED, "gate %d: %d time slices, 1..%d are supported", g, s.n_slices, SLAM_SMUSH_MAX_SLICES);
+        if (!std::isfinite(s.t)) return fail(SLAM_ERR_INVALID, "gate %d: pulse time is not finite", g);
+        SmushMap& m = tmp[(size_t)g];
+        std::memset(&m, 0, sizeof(m));
+        m.qn = qn;
+        m.n_slices = s.n_slices;
+        m.t = s.t;
+        const int nraw = 2 + 2 * s.n_slices;
+        for (int r = 0; r < SLAM_SMUSH_RAW; ++r) {
+            const bool used = r < nraw;
+            if (used && (s.sel[r] < -1 || s.sel[r] >= qn)) return fail(SLAM_ERR_INVALID, "gate %d: sel[%d] = %d outside [-1, %d)", g, r, s.sel[r], qn);
+            if (used && (!std::isfinite(s.scale[r]) || !std::isfinite(s.offset[r]))) return fail(SLAM_ERR_INVALID, "gate %d: non-finite map", g);
+            m.sel[r] = used ? s.sel[r] : -1;
+            m.scale[r] = (used && s.sel[r] >= 0) ? s.scale[r] : 0.0;
+            m.offset[r] = used ? s.offset[r] : 0.0;
+        }
+    }
+    ctx->smush_gates_host.swap(tmp);
+    ctx->smush_qn = qn;
+    return SLAM_OK;
+}
+
+int slam_smush_eval_loss_grad(slam_ctx* ctx, int k, const int32_t* gate_seq, const double* x, const int32_t* target_of, int64_t M,
+                              double* loss, double* grad, double* unitary) {
+    return drained(ctx, smush_eval_body(ctx, k, gate_seq, x, target_of, M, loss, grad, unitary));
+}
+
+int slam_smush_minimize_stage(slam_ctx* ctx, int k, const int32_t* gate_seq, const int32_t* active, int64_t n_active, const double* x0,
+                              const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi,
+                              const slam_opt_params* params, double exit_loss, double* best_loss, double* best_x, int32_t* best_restart,
+                              double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals) {
+    return drained(ctx, smush_minimize_body(ctx, k, gate_seq, active, n_active, x0, init_lo, init_hi, bound_lo, bound_hi, params, exit_loss,
+                                            best_loss, best_x, best_restart, item_loss, item_iters, item_status, item_evals));
+}
+
+int slam_smush_minimize_stage_trace(slam_ctx* ctx, int k, const int32_t* gate_seq, const int32_t* active, int64_t n_active, const double* x0,
+                                    const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi,
+                                    const slam_opt_params* params, double exit_loss, int32_t trace_cap, double* best_loss, double* best_x,
+                                    int32_t* best_restart, double* item_loss, int32_t* item_iters, int32_t* item_status, double* trace_loss,
+                                    double* trace_x) {
+    return minimize_stage_trace(
+        ctx, active, n_active, params, trace_cap, trace_loss, trace_x,
+        [&](int* n) {
+            const int rc = smush_check(ctx, k);
+            if (rc) return rc;
+            *n = 6 * (k + 1) + ctx->smush_qn * k;
+            return (int)SLAM_OK;
+        },
+        [&] {
+            return slam_smush_minimize_stage(ctx, k, gate_seq, active, n_active, x0, init_lo, init_hi, bound_lo, bound_hi, params, exit_loss, best_loss,
+                                             best_x, best_restart, item_loss, item_iters, item_status, nullptr);
+        });
+}
+
+}  // extern "C"

@@ -40,13 +40,7 @@
 
 namespace slamdev {
 
-struct V2GateMap {  // raw angle order: 0 a, 1 phi_c, 2 b, 3 phi_g
-    double scale[4];
-    double offset[4];
-    int32_t sel[4];
-    int32_t pad[4];
-};
-static_assert(sizeof(V2GateMap) == 96, "V2GateMap layout");
+// (V2GateMap, a gate's affine parameter map: slam_types.hpp)
 
 template <int K, int QN>
 struct CfgV2 {

@@ -1,7 +1,7 @@
-"""Dev tool: static instruction mix of one kernel in build/slam_hip-hip-amdgcn-amd-amdhsa-gfx950.s, split at basic-block labels.
+"""Dev tool: static instruction mix of one kernel in the units' build/*-hip-amdgcn-amd-amdhsa-gfx950.s, split at basic-block labels.
 usage: tools/isa_mix.py <mangled-name-prefix> [--blocks]"""
-import collections, re, sys
-t = open("build/slam_hip-hip-amdgcn-amd-amdhsa-gfx950.s").read().split("\n")
+import collections, glob, re, sys
+t = [l for p in sorted(glob.glob("build/*-hip-amdgcn-amd-amdhsa-gfx950.s")) for l in open(p).read().split("\n")]
 pref = sys.argv[1]
 start = next(i for i, l in enumerate(t) if l.startswith(pref) and ":" in l)
 end = next(i for i in range(start, len(t)) if t[i].startswith(".Lfunc_end"))
