@@ -177,6 +177,30 @@ int slam_targets_c1c2c3(slam_ctx* ctx, int64_t first, int64_t count, int ndigits
 int slam_eval_c1c2c3(slam_ctx* ctx, int k, const int32_t* gate_seq, const double* x, int64_t M, int ndigits, double* out);
 
 /*
+ * KAK decomposition on the device, one thread per unitary (csrc/slam_kak.hpp):
+ *     U = e^{i phase} (a1 (x) a2) CAN(c) (b1 (x) b2),   CAN(c) = exp(i pi/2 (c1 XX + c2 YY + c3 ZZ)),
+ * with a1, a2, b1, b2 in SU(2) (index 1: the qubit of the high bit of the basis index, qiskit's qubit 1) and c, in units of pi, the
+ * chamber point slam_c1c2c3 returns with ndigits < 0 (same fold, same c3 < 0 -> (1 - c1, c2, -c3) rule).  The reference has no such
+ * step of its own: its transpiler pass calls qiskit's KAK code, and VariationalTemplate.undo_invariant_transform
+ * (src/slam/basis_abc.py:86-90) is a stub.
+ *   phase double[count], a1 / a2 / b1 / b2 double[count][2][2][2], c double[count][3]   (out, all required)
+ *   slam_kak          unitaries from the host, double[count][4][4][2]
+ *   slam_targets_kak  the resident targets [first, first + count) (nothing is uploaded)
+ *
+ * slam_complete_locals: local-gate completion of M fits that hold up to single-qubit gates (MakhlinFunctionalCost, or
+ * SLAM_FLAG_NO_EXTERIOR templates).  Item m: W = template(x[m]) (gate_seq, k as in slam_eval_unitary; rows of no-exterior fits carry
+ * zeros in layers 0 and k), T = resident target target_of[m].  KAK of both, the chamber points aligned (the c3 = 0 mirror image
+ * (1 - c1, c2, -c3) of W's point is taken where it is closer to T's), L = A_T A_W^+ folded into layer k and R = B_W^+ B_T into layer 0:
+ *   x_out     double[M][6(k+1)]  the completed row; interior layers are copied
+ *   loss_out  double[M]          1 - |Tr(T^+ template(x_out))| / 4, from a forward pass of x_out
+ *   gap_out   double[M]          max-norm distance d of the two chamber points after alignment (units of pi); loss <= 1 - cos(1.5 pi d)
+ */
+int slam_kak(slam_ctx* ctx, const double* unitaries, int64_t count, double* phase, double* a1, double* a2, double* c, double* b1, double* b2);
+int slam_targets_kak(slam_ctx* ctx, int64_t first, int64_t count, double* phase, double* a1, double* a2, double* c, double* b1, double* b2);
+int slam_complete_locals(slam_ctx* ctx, int k, const int32_t* gate_seq, const double* x, const int32_t* target_of, int64_t M, double* x_out,
+                         double* loss_out, double* gap_out);
+
+/*
  * Span predictor on the device: for every resident target of [first, first + count) the smallest number k of leading gates of a
  * template whose coverage set contains the target -- the lookup CircuitTemplate.get_spanning_range makes with use_polytopes=True
  * (src/slam/basis.py:95-100 -> monodromy_range_from_target, src/slam/utils/polytopes/polytope_wrap.py:39-94).  The coverage sets
@@ -643,7 +667,8 @@ const char* slam_version(void);
  *      later: slam_coverage_lookup (a new symbol only; no signature or structure changed);
  *      later: the slam_smush_* family and its own slam_smush_gate (new symbols only);
  *      later: slam_pd_sample, slam_pd_extremes, slam_pd_filter and slam_region_lookup (new symbols only);
- *      later: slam_hw_queues_requested (a new symbol only).
+ *      later: slam_hw_queues_requested (a new symbol only);
+ *      later: slam_kak, slam_targets_kak and slam_complete_locals (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

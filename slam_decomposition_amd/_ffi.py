@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -56,6 +56,9 @@ EXPORTED_SYMBOLS = (
     "slam_set_gates",
     "slam_c1c2c3",
     "slam_targets_c1c2c3",
+    "slam_kak",
+    "slam_targets_kak",
+    "slam_complete_locals",
     "slam_predict_spans",
     "slam_coverage_lookup",
     "slam_eval_c1c2c3",
@@ -216,6 +219,10 @@ def load_library() -> C.CDLL:
     lib.slam_set_gates.argtypes = [P, P, C.c_int32]
     lib.slam_c1c2c3.argtypes = [P, P, C.c_int64, C.c_int32, P]
     lib.slam_targets_c1c2c3.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P]
+    if hasattr(lib, "slam_kak"):
+        lib.slam_kak.argtypes = [P, P, C.c_int64] + [P] * 6
+        lib.slam_targets_kak.argtypes = [P, C.c_int64, C.c_int64] + [P] * 6
+        lib.slam_complete_locals.argtypes = [P, C.c_int, P, P, P, C.c_int64, P, P, P]
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
     if hasattr(lib, "slam_coverage_lookup"):
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
@@ -394,6 +401,18 @@ result_pool = ResultPool(pinned=True)      # ONE blocking call alone on the devi
 pageable_pool = ResultPool(pinned=False)   # everything else
 
 
+class KakResult(NamedTuple):
+    """``U[i] = exp(1j * phase[i]) * kron(a1[i], a2[i]) @ CAN(c[i]) @ kron(b1[i], b2[i])``: phase float64[N], the SU(2) factors
+    complex128[N, 2, 2], c float64[N, 3] in units of pi (the chamber point of ``c1c2c3(..., ndigits=-1)``)."""
+
+    phase: np.ndarray
+    a1: np.ndarray
+    a2: np.ndarray
+    c: np.ndarray
+    b1: np.ndarray
+    b2: np.ndarray
+
+
 def _mat_to_ri(mats: np.ndarray) -> np.ndarray:
     """complex128[..., 4, 4] -> float64[..., 4, 4, 2] (row-major re, im), contiguous."""
     m = np.ascontiguousarray(np.asarray(mats, dtype=np.complex128))
@@ -465,6 +484,47 @@ class Context:
         out = np.zeros((count, 3), dtype=np.float64)
         _check(self._lib.slam_targets_c1c2c3(self._h, int(first), int(count), int(ndigits), _ptr(out)))
         return out
+
+    def _kak_call(self, fn, head, count: int) -> KakResult:
+        phase = np.zeros(count)
+        f = [np.zeros((count, 2, 2), dtype=np.complex128) for _ in range(4)]
+        c = np.zeros((count, 3))
+        _check(fn(self._h, *head, count, _ptr(phase), _ptr(f[0]), _ptr(f[1]), _ptr(c), _ptr(f[2]), _ptr(f[3])))
+        return KakResult(phase, f[0], f[1], c, f[2], f[3])
+
+    def kak(self, unitaries: np.ndarray) -> KakResult:
+        """KAK decomposition of ``unitaries[N, 4, 4]`` on the device (slam_kak): a :class:`KakResult`."""
+        u = np.ascontiguousarray(unitaries, dtype=np.complex128)
+        if u.ndim != 3 or u.shape[1:] != (4, 4):
+            raise ValueError("expected an array of shape [N, 4, 4]")
+        return self._kak_call(self._lib.slam_kak, (_ptr(u.view(np.float64)),), u.shape[0])
+
+    def targets_kak(self, first: int = 0, count: Optional[int] = None) -> KakResult:
+        """KAK decomposition of the resident targets [first, first + count) (slam_targets_kak): a :class:`KakResult`."""
+        count = self.n_targets - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > self.n_targets:
+            raise ValueError(f"target window [{first}, {first + count}) outside the resident batch of {self.n_targets}")
+        return self._kak_call(self._lib.slam_targets_kak, (int(first),), count)
+
+    def complete_locals(self, gate_seq: Sequence[int], x: np.ndarray, target_of: np.ndarray):
+        """Local-gate completion (slam_complete_locals): rows ``x[M, 6 (k + 1)]`` whose template unitaries equal the resident targets
+        ``target_of[M]`` up to single-qubit gates -> ``(x_out [M, 6 (k + 1)], loss [M], gap [M])``: the rows with the missing local
+        gates folded into layers 0 and k, their BasicCost loss against the targets, and the coordinate gap of the fit."""
+        k = len(gate_seq)
+        n = 6 * (k + 1)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if k < 1 or x.ndim != 2 or x.shape[1] != n:
+            raise ValueError(f"x must have shape [M, {n}] for a sequence of {k} gates")
+        M = x.shape[0]
+        tof = np.ascontiguousarray(target_of, dtype=np.int32)
+        if tof.shape != (M,):
+            raise ValueError("target_of must have shape [M]")
+        gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
+        x_out = np.zeros((M, n))
+        loss = np.zeros(M)
+        gap = np.zeros(M)
+        _check(self._lib.slam_complete_locals(self._h, k, _ptr(gs), _ptr(x), _ptr(tof), M, _ptr(x_out), _ptr(loss), _ptr(gap)))
+        return x_out, loss, gap
 
     def predict_spans(self, gate_coords_seq, k_max: int, first: int = 0, count: Optional[int] = None, tol: float = 2e-8) -> np.ndarray:
         """Template size every resident target of [first, first + count) needs with the gate sequence whose Weyl coordinates are

@@ -170,6 +170,26 @@ class CircuitTemplate(VariationalTemplate):
         w, _ = ctx.eval_unitary(self.gate_sequence(), self.device_vector(Xk))
         return w[0]
 
+    def undo_invariant_transform(self, target_U, Xk):
+        """The step the reference names and leaves a stub (basis_abc.py:86-90): ``Xk`` makes the built template equal to
+        ``target_U`` up to single-qubit gates (a MakhlinFunctionalCost fit, or a ``no_exterior_1q`` template); returned is the
+        parameter vector of the SAME gate sequence WITH exterior layers, 6 (cycles + 1) values in index order, whose circuit equals
+        ``target_U`` up to a global phase -- as far as the two are locally equivalent.  KAK decomposition of both sides and the
+        completion on the device (``slam_complete_locals``); ``target_U`` becomes the context's resident target."""
+        if self.cycles <= 0:
+            raise ValueError("build() the template first")
+        t = np.asarray(target_U, dtype=np.complex128)
+        if t.shape != (4, 4):
+            raise ValueError("target_U must be a 4x4 unitary")
+        Xk = np.asarray(Xk, dtype=np.float64).reshape(1, -1)
+        if Xk.shape[1] != self.n_params:
+            raise ValueError(f"expected {self.n_params} parameters, got {Xk.shape[1]}")
+        ctx = runtime.get_context(self.device)
+        ctx.set_gates(self.gate_matrices)
+        ctx.set_targets(t[None])
+        x_out, _, _ = ctx.complete_locals(self.gate_sequence(), self.device_vector(Xk), np.zeros(1, dtype=np.int32))
+        return x_out[0]
+
     def parameter_guess(self, t=0):
         """basis.py:106-111: uniform in [0, 2pi) from NumPy's global generator."""
         parent = super().parameter_guess(t)

@@ -1,9 +1,11 @@
 // slam_geometry.hip -- host side of libslamhip.so, geometry unit: Weyl coordinates, span prediction and coverage lookups, the Haar
-// sampler, parallel-drive coverage samples and region lookups (slam_weyl.hpp, slam_sampler.hpp, slam_pd.hpp).
+// sampler, parallel-drive coverage samples and region lookups, the KAK decomposition and local-gate completion (slam_weyl.hpp,
+// slam_sampler.hpp, slam_pd.hpp, slam_kak.hpp).
 #include "slam_host.hpp"
 #include "slam_sampler.hpp"
 #include "slam_weyl.hpp"
 #include "slam_pd.hpp"
+#include "slam_kak.hpp"
 
 int enqueue_c1c2c3(slam_ctx* c, const double* d_unitaries, int64_t count, int ndigits, double* d_out) {
     hipLaunchKernelGGL(c1c2c3_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_unitaries, count, ndigits, d_out);
@@ -36,7 +38,101 @@ static int weyl_device(slam_ctx* ctx, const double* d_unitaries, int64_t count, 
     return SLAM_OK;
 }
 
+// KAK records of `count` unitaries that are already in device memory, unpacked into the caller's arrays
+static int kak_device(slam_ctx* ctx, const double* d_unitaries, int64_t count, double* phase, double* a1, double* a2, double* c, double* b1,
+                      double* b2) {
+    HIP_TRY(ctx->ev_weyl.reserve((size_t)count * kKakRecord * sizeof(double)));
+    hipLaunchKernelGGL(kak_kernel, dim3((unsigned)((count + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, d_unitaries, count,
+                       ctx->ev_weyl.as<double>());
+    HIP_TRY(hipGetLastError());
+    std::vector<double> rec((size_t)count * kKakRecord);
+    HIP_TRY(hipMemcpyAsync(rec.data(), ctx->ev_weyl.p, rec.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < count; ++i) {
+        const double* r = rec.data() + (size_t)i * kKakRecord;
+        phase[i] = r[0];
+        std::memcpy(a1 + i * 8, r + 1, 8 * sizeof(double));
+        std::memcpy(a2 + i * 8, r + 9, 8 * sizeof(double));
+        std::memcpy(c + i * 3, r + 17, 3 * sizeof(double));
+        std::memcpy(b1 + i * 8, r + 20, 8 * sizeof(double));
+        std::memcpy(b2 + i * 8, r + 28, 8 * sizeof(double));
+    }
+    return SLAM_OK;
+}
+
 extern "C" {
+
+int slam_kak(slam_ctx* ctx, const double* unitaries, int64_t count, double* phase, double* a1, double* a2, double* c, double* b1, double* b2) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (count < 0) return fail(SLAM_ERR_INVALID, "count < 0");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many unitaries in one call (%lld)", (long long)count);
+    if (count == 0) return SLAM_OK;
+    if (!unitaries) return fail(SLAM_ERR_INVALID, "unitaries is NULL");
+    if (!phase || !a1 || !a2 || !c || !b1 || !b2) return fail(SLAM_ERR_INVALID, "phase, a1, a2, c, b1 and b2 must be non-NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_unitary.reserve((size_t)count * 32 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(ctx->ev_unitary.p, unitaries, (size_t)count * 32 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return kak_device(ctx, ctx->ev_unitary.as<double>(), count, phase, a1, a2, c, b1, b2);
+}
+
+int slam_targets_kak(slam_ctx* ctx, int64_t first, int64_t count, double* phase, double* a1, double* a2, double* c, double* b1, double* b2) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (count == 0) return SLAM_OK;
+    if (!phase || !a1 || !a2 || !c || !b1 || !b2) return fail(SLAM_ERR_INVALID, "phase, a1, a2, c, b1 and b2 must be non-NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return kak_device(ctx, ctx->targets.as<double>() + first * 32, count, phase, a1, a2, c, b1, b2);
+}
+
+int slam_complete_locals(slam_ctx* ctx, int k, const int32_t* gate_seq, const double* x, const int32_t* target_of, int64_t M, double* x_out,
+                         double* loss_out, double* gap_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (ctx->n_targets <= 0) return fail(SLAM_ERR_STATE, "no targets: call slam_set_targets first");
+    if (ctx->n_gates <= 0) return fail(SLAM_ERR_STATE, "no gates: call slam_set_gates first");
+    if (k < 1 || k > SLAM_MAX_SPAN_EVAL) return fail(SLAM_ERR_UNSUPPORTED, "span must be in 1..%d (got %d)", SLAM_MAX_SPAN_EVAL, k);
+    if (M < 0) return fail(SLAM_ERR_INVALID, "M < 0");
+    if (M > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many items in one call (%lld)", (long long)M);
+    if (M == 0) return SLAM_OK;
+    if (!gate_seq) return fail(SLAM_ERR_INVALID, "gate_seq is NULL");
+    if (!x || !target_of) return fail(SLAM_ERR_INVALID, "x and target_of must be non-NULL");
+    if (!x_out || !loss_out || !gap_out) return fail(SLAM_ERR_INVALID, "x_out, loss_out and gap_out must be non-NULL");
+    static_assert(sizeof(CompleteArgs{}.seq) / sizeof(int32_t) == SLAM_MAX_SPAN_EVAL, "CompleteArgs::seq holds SLAM_MAX_SPAN_EVAL gates");
+    CompleteArgs a{};
+    a.k = k;
+    for (int j = 0; j < k; ++j) {
+        if (gate_seq[j] < 0 || gate_seq[j] >= ctx->n_gates)
+            return fail(SLAM_ERR_INVALID, "gate_seq[%d] = %d outside the gate table (n_gates = %d)", j, gate_seq[j], ctx->n_gates);
+        a.seq[j] = gate_seq[j];
+    }
+    for (int64_t m = 0; m < M; ++m)
+        if (target_of[m] < 0 || target_of[m] >= ctx->n_targets)
+            return fail(SLAM_ERR_INVALID, "target_of[%lld] = %d outside [0, %lld)", (long long)m, target_of[m], (long long)ctx->n_targets);
+    const size_t n = 6 * ((size_t)k + 1);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_x.reserve((size_t)M * n * sizeof(double)));
+    HIP_TRY(ctx->ev_tof.reserve((size_t)M * sizeof(int32_t)));
+    HIP_TRY(ctx->ev_grad.reserve((size_t)M * n * sizeof(double)));  // the completed rows
+    HIP_TRY(ctx->ev_loss.reserve((size_t)M * 2 * sizeof(double)));  // losses, then gaps
+    HIP_TRY(hipMemcpyAsync(ctx->ev_x.p, x, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->ev_tof.p, target_of, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    a.gates = ctx->gates.as<double>();
+    a.targets = ctx->targets.as<double>();
+    a.x = ctx->ev_x.as<double>();
+    a.target_of = ctx->ev_tof.as<int32_t>();
+    a.M = M;
+    a.x_out = ctx->ev_grad.as<double>();
+    a.loss_out = ctx->ev_loss.as<double>();
+    a.gap_out = ctx->ev_loss.as<double>() + M;
+    hipLaunchKernelGGL(complete_locals_kernel, dim3((unsigned)((M + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(x_out, ctx->ev_grad.p, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(loss_out, a.loss_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(gap_out, a.gap_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
 
 int slam_c1c2c3(slam_ctx* ctx, const double* unitaries, int64_t count, int ndigits, double* out) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");

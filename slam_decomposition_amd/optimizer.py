@@ -900,6 +900,60 @@ class TemplateOptimizer:
             self._device_sampler = None
         return self.training_loss, self.coordinate_list, target_data
 
+    # ---- local-gate completion (the reference's stub undo_invariant_transform, basis_abc.py:86-90) ---------------------------------
+    completion_gaps = None  # after complete_local_gates: per target the coordinate gap of its fit (units of pi)
+
+    def complete_local_gates(self, targets, target_data) -> List[DataDictEntry]:
+        """Turn fits that hold up to single-qubit gates into circuits that equal their targets: ``targets`` ([N, 4, 4]) and the
+        ``DataDictEntry`` list of a finished ``approximate_from_distribution`` call (MakhlinFunctionalCost, or a template with
+        ``no_exterior_1q=True``).  Returns new entries: ``Xk`` has 6 (cycles + 1) values -- the same gate sequence with exterior
+        layers --, ``loss_result`` is the BasicCost loss of that circuit against the target, ``success_label`` compares it with the
+        success threshold.  The entries are grouped by ``cycles`` (a MixedOrderBasisCircuitTemplate: by the gate sequence of the
+        coverage entry each target ended with) and every group is one device call (``slam_complete_locals``).  A converged Makhlin
+        fit can still leave a coordinate gap d (``completion_gaps``); the loss is bounded by 1 - cos(1.5 pi d)."""
+        if self._v2:
+            raise NotImplementedError("complete_local_gates is implemented for fixed-gate templates (CircuitTemplate, "
+                                      "MixedOrderBasisCircuitTemplate), not for CircuitTemplateV2")
+        T = np.asarray(targets.as_array() if hasattr(targets, "as_array") else targets, dtype=np.complex128)
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("targets must have shape [N, 4, 4]")
+        entries = list(target_data)
+        if len(entries) != len(T):
+            raise ValueError(f"{len(T)} targets but {len(entries)} entries")
+        mixed = getattr(self.basis, "mixed_order", False)
+        if mixed and len(getattr(self, "circuit_polytopes", None) or []) != len(entries):
+            raise ValueError("a mixed-order template needs the coverage entries of the approximate_from_distribution call that "
+                             "produced target_data")
+        groups = {}
+        for i, e in enumerate(entries):
+            k = int(e.cycles)
+            if k < 1:
+                raise ValueError(f"entry {i}: cycles = {k}; only fitted circuits can be completed")
+            seq = tuple(self.circuit_polytopes[i].gate_indices) if mixed else tuple(self.basis.gate_sequence(k))
+            width = 6 * (k - 1) if self._no_exterior else 6 * (k + 1)
+            if len(seq) != k or len(e.Xk) != width:
+                raise ValueError(f"entry {i}: {len(e.Xk)} parameters and {len(seq)} gates do not fit cycles = {k}")
+            groups.setdefault(seq, []).append(i)
+        out = [None] * len(entries)
+        gaps = np.zeros(len(entries))
+        if not entries:
+            self.completion_gaps = gaps
+            return out
+        ctx = runtime.get_context(self.devices[0])
+        ctx.set_gates(self.basis.gate_matrices)
+        ctx.set_targets(T)
+        for seq, idx in groups.items():
+            k = len(seq)
+            X = np.stack([np.asarray(entries[i].Xk, dtype=np.float64) for i in idx])
+            if self._no_exterior:
+                X = self.basis.device_vector(X, k)
+            x_out, loss, gap = ctx.complete_locals(list(seq), X, np.asarray(idx, dtype=np.int32))
+            gaps[idx] = gap
+            for j, i in enumerate(idx):
+                out[i] = DataDictEntry(int(loss[j] <= self.success_threshold), float(loss[j]), x_out[j].tolist(), k)
+        self.completion_gaps = gaps
+        return out
+
     # ---- costs without optimisation (optimizer.py:156-178; pulse_cost.py) ---------------------------------------------------------
     cost_counts = None  # after cost_from_distribution: [(CircuitCoverage, count)] in cost order
     cost_local_count = None  # ... and the number of local targets (cost 0)
