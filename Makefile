@@ -5,7 +5,9 @@ CSRC  := slam_decomposition_amd/csrc
 UNITS := slam_hip slam_v2_host slam_smush_host slam_geometry slam_comm
 OBJS  := $(UNITS:%=build/%.o)
 OUT   := slam_decomposition_amd/lib/libslamhip.so
-FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function
+# -amdgpu-mfma-vgpr-form: the metric update's MFMAs (h_update_mfma) accumulate in VGPRs, where the metric lives, also in the kernels
+# that park spills in AGPRs (span 3); without it the compiler moves every block through AGPRs there (+50 registers, +212 instructions)
+FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -mllvm -amdgpu-mfma-vgpr-form
 
 all: $(OUT)
 

@@ -476,6 +476,19 @@ int slam_reset_stats(slam_ctx* ctx);
  * without a host round trip. */
 int slam_best_loss_device_ptr(slam_ctx* ctx, void** ptr, int64_t* n);
 
+/*
+ * Device check of the quasi-Newton metric's rank-2 update H += s w^T + v s^T (csrc/slam_device.hpp: h_update), one quad per item as
+ * in the optimizer kernels.  The update is applied to the caller's blocks once through the form the optimizer kernels run (the
+ * 4x4x1 fp32 MFMA where an instantiation has it) and once through the v_pk_fma_f32 form, which this kernel keeps as the reference;
+ * the two are expected to agree bit for bit (tests/test_gpu_metric_mfma.py).  na = slots per lane: 3, 5, 6 (spans 1, 2, 3).
+ *   h                     float[n_items][na (na + 1) / 2][4][4]  upper blocks, block (a, b), a <= b, at b (b + 1) / 2 + a;
+ *                                                                 element [q][e] = H[4a + q][4b + e]
+ *   s, w, v               float[n_items][4 na]                   component 4a + q
+ *   h_shipped, h_vector   like h (out)
+ */
+int slam_metric_update_check(slam_ctx* ctx, int na, const float* h, const float* s, const float* w, const float* v, int64_t n_items,
+                             float* h_shipped, float* h_vector);
+
 /* HIP device ordinal the context was created on (slam_comm_merge_add checks it against its communicator's). */
 int slam_ctx_device(slam_ctx* ctx, int* device);
 
@@ -668,7 +681,8 @@ const char* slam_version(void);
  *      later: the slam_smush_* family and its own slam_smush_gate (new symbols only);
  *      later: slam_pd_sample, slam_pd_extremes, slam_pd_filter and slam_region_lookup (new symbols only);
  *      later: slam_hw_queues_requested (a new symbol only);
- *      later: slam_kak, slam_targets_kak and slam_complete_locals (new symbols only).
+ *      later: slam_kak, slam_targets_kak and slam_complete_locals (new symbols only);
+ *      later: slam_metric_update_check (a new symbol only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -99,6 +99,7 @@ EXPORTED_SYMBOLS = (
     "slam_get_stats",
     "slam_reset_stats",
     "slam_best_loss_device_ptr",
+    "slam_metric_update_check",
     "slam_ctx_device",
     "slam_comm_get_unique_id",
     "slam_comm_init",
@@ -275,6 +276,7 @@ def load_library() -> C.CDLL:
     lib.slam_get_stats.argtypes = [P, C.POINTER(Stats)]
     lib.slam_reset_stats.argtypes = [P]
     lib.slam_best_loss_device_ptr.argtypes = [P, C.POINTER(P), C.POINTER(C.c_int64)]
+    lib.slam_metric_update_check.argtypes = [P, C.c_int, P, P, P, P, C.c_int64, P, P]
     if hasattr(lib, "slam_ctx_device"):
         lib.slam_ctx_device.argtypes = [P, C.POINTER(C.c_int)]
     if hasattr(lib, "slam_comm_init") and (abi >= 4 or not variant):  # (older variants: slam_allreduce_min had four arguments)
@@ -525,6 +527,24 @@ class Context:
         gap = np.zeros(M)
         _check(self._lib.slam_complete_locals(self._h, k, _ptr(gs), _ptr(x), _ptr(tof), M, _ptr(x_out), _ptr(loss), _ptr(gap)))
         return x_out, loss, gap
+
+    def metric_update_check(self, h: np.ndarray, s: np.ndarray, w: np.ndarray, v: np.ndarray):
+        """Device check of the metric's rank-2 update ``H += s w^T + v s^T`` (slam_metric_update_check): ``h[n, na (na + 1) / 2, 4, 4]``
+        upper blocks (block (a, b) at b (b + 1) / 2 + a, element [q][e] = H[4a + q][4b + e]) and ``s, w, v [n, 4 na]``, float32, na in
+        (3, 5, 6) -> ``(h_shipped, h_vector)``: the update through the form the optimizer kernels run and through the vector form."""
+        s = np.ascontiguousarray(s, dtype=np.float32)
+        if s.ndim != 2 or s.shape[1] % 4:
+            raise ValueError("s must have shape [n, 4 na]")
+        n, na = s.shape[0], s.shape[1] // 4
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        h = np.ascontiguousarray(h, dtype=np.float32)
+        if w.shape != s.shape or v.shape != s.shape or h.shape != (n, na * (na + 1) // 2, 4, 4):
+            raise ValueError(f"w, v must have shape {s.shape} and h [{n}, {na * (na + 1) // 2}, 4, 4]")
+        h_shipped = np.zeros_like(h)
+        h_vector = np.zeros_like(h)
+        _check(self._lib.slam_metric_update_check(self._h, na, _ptr(h), _ptr(s), _ptr(w), _ptr(v), n, _ptr(h_shipped), _ptr(h_vector)))
+        return h_shipped, h_vector
 
     def predict_spans(self, gate_coords_seq, k_max: int, first: int = 0, count: Optional[int] = None, tol: float = 2e-8) -> np.ndarray:
         """Template size every resident target of [first, first + count) needs with the gate sequence whose Weyl coordinates are

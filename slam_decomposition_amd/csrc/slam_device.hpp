@@ -1316,9 +1316,12 @@ __device__ __forceinline__ void h_matvec(const HMat<NA>& H, const double (&vd)[N
 }
 
 // H += s w^T + v s^T  (rank-2 BFGS inverse update), s, w, v distributed (already fp32)
+//
+// Vector form (the reference of metric_update_check_kernel; no optimizer kernel runs it): w and s are broadcast within the quad
+// through the fp32 overlay, then two dependent v_pk_fma_f32 per half block (v s^T first, s w^T second).
 template <int NA>
-__device__ __forceinline__ void h_update(HMat<NA>& H, const float (&s32)[NA], const float (&w32)[NA],
-                                         const float (&v32)[NA], float* xq32, int q) {
+__device__ __forceinline__ void h_update_valu(HMat<NA>& H, const float (&s32)[NA], const float (&w32)[NA],
+                                              const float (&v32)[NA], float* xq32, int q) {
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         xq32[4 * a + q] = w32[a];
@@ -1345,6 +1348,36 @@ __device__ __forceinline__ void h_update(HMat<NA>& H, const float (&s32)[NA], co
         }
     }
     lds_fence();
+}
+
+// Matrix-pipe form: v_mfma_f32_4x4x1_16b_f32 is sixteen independent 4 x 4 outer-product accumulations per wavefront,
+// one per quad: D[i][j] = A[i] B[j] + C[i][j] with A read from lane i, B from lane j and D[i][j] in register i of lane j.
+// Block (a, b) of HMat is that accumulator as it stands (register e = column 4b + e, lane q = row 4a + q), and slot b of
+// lane e / slot a of lane q are the operands: no broadcast, no LDS.  Per element the same two dependent fmaf as the vector
+// form, in the same order, so H is bit-identical.  The instruction ignores EXEC: callers are in wave-uniform control flow.
+template <int NA>
+__device__ __forceinline__ void h_update_mfma(HMat<NA>& H, const float (&s32)[NA], const float (&w32)[NA],
+                                              const float (&v32)[NA]) {
+#pragma unroll
+    for (int b = 0; b < NA; ++b) {
+#pragma unroll
+        for (int a = 0; a <= b; ++a) {
+            const f32x2 h0 = H.h[blk(a, b)][0], h1 = H.h[blk(a, b)][1];
+            f32x4 c = f32x4{h0.x, h0.y, h1.x, h1.y};
+            c = __builtin_amdgcn_mfma_f32_4x4x1f32(s32[b], v32[a], c, 0, 0, 0);  // += v_a s_b^T
+            c = __builtin_amdgcn_mfma_f32_4x4x1f32(w32[b], s32[a], c, 0, 0, 0);  // += s_a w_b^T
+            H.h[blk(a, b)][0] = f32x2{c.x, c.y};
+            H.h[blk(a, b)][1] = f32x2{c.z, c.w};
+        }
+    }
+}
+
+// The form every optimizer kernel runs (every instantiation holds its register budget with it: DESIGN.md section 2); the s / w area
+// of the fp32 overlay at xq32 goes unused.
+template <int NA>
+__device__ __forceinline__ void h_update(HMat<NA>& H, const float (&s32)[NA], const float (&w32)[NA],
+                                         const float (&v32)[NA], float* /*xq32*/, int /*q*/) {
+    h_update_mfma<NA>(H, s32, w32, v32);
 }
 
 template <int NA>

@@ -1928,4 +1928,39 @@ int slam_best_loss_device_ptr(slam_ctx* ctx, void** ptr, int64_t* n) {
     return SLAM_OK;
 }
 
+int slam_metric_update_check(slam_ctx* ctx, int na, const float* h, const float* s, const float* w, const float* v, int64_t n_items,
+                             float* h_shipped, float* h_vector) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (na != 3 && na != 5 && na != 6) return fail(SLAM_ERR_UNSUPPORTED, "na must be 3, 5 or 6 (spans 1, 2, 3; got %d)", na);
+    if (n_items < 0) return fail(SLAM_ERR_INVALID, "n_items < 0");
+    if (n_items > (1 << 20)) return fail(SLAM_ERR_INVALID, "too many items in one call (%lld)", (long long)n_items);
+    if (n_items == 0) return SLAM_OK;
+    if (!h || !s || !w || !v) return fail(SLAM_ERR_INVALID, "h, s, w and v must be non-NULL");
+    if (!h_shipped || !h_vector) return fail(SLAM_ERR_INVALID, "h_shipped and h_vector must be non-NULL");
+    const size_t h_b = (size_t)n_items * (na * (na + 1) / 2) * 16 * sizeof(float), vec_b = (size_t)n_items * 4 * na * sizeof(float);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_x.reserve(h_b + 3 * vec_b));  // h, s, w, v
+    HIP_TRY(ctx->ev_grad.reserve(2 * h_b));       // both results
+    char* in = ctx->ev_x.as<char>();
+    char* out = ctx->ev_grad.as<char>();
+    HIP_TRY(hipMemcpyAsync(in, h, h_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(in + h_b, s, vec_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(in + h_b + vec_b, w, vec_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(in + h_b + 2 * vec_b, v, vec_b, hipMemcpyHostToDevice, ctx->stream));
+    const dim3 grid((unsigned)((n_items + kQuadsPerWave - 1) / kQuadsPerWave)), block(kWave);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, reinterpret_cast<const float*>(in), reinterpret_cast<const float*>(in + h_b),
+                           reinterpret_cast<const float*>(in + h_b + vec_b), reinterpret_cast<const float*>(in + h_b + 2 * vec_b), n_items,
+                           reinterpret_cast<float*>(out), reinterpret_cast<float*>(out + h_b));
+    };
+    if (na == 3) launch(metric_update_check_kernel<3>);
+    else if (na == 5) launch(metric_update_check_kernel<5>);
+    else launch(metric_update_check_kernel<6>);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_shipped, out, h_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_vector, out + h_b, h_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
 }  // extern "C"

@@ -1354,4 +1354,48 @@ __global__ void __launch_bounds__(256) stage_epilogue_multi_kernel(const Epilogu
 }
 #endif
 
+// ---------------------------------------------------------------------------------
+// Device check of the metric's rank-2 update (slam_metric_update_check): one quad per item, as in the optimizer kernels.  The update
+// is applied once through h_update -- the form the optimizer kernels run -- and once through the vector form, which lives on as
+// the reference of this kernel.  H in / out: float[n][NA (NA + 1) / 2][4][4], block blk(a, b), element [q][e] = H[4a + q][4b + e];
+// s, w, v: float[n][4 NA], component 4a + q.  Every lane runs the update (the MFMA takes no notice of EXEC): quads past the
+// batch work on item n - 1 and store nothing.
+// ---------------------------------------------------------------------------------
+template <int NA>
+__global__ void __launch_bounds__(kWave) metric_update_check_kernel(const float* __restrict__ h_in, const float* __restrict__ s, const float* __restrict__ w,
+                                                                    const float* __restrict__ v, int64_t n, float* __restrict__ h_shipped,
+                                                                    float* __restrict__ h_vector) {
+    constexpr int NB = NA * (NA + 1) / 2;
+    __shared__ __attribute__((aligned(16))) float xchg32[kQuadsPerWave * 8 * NA];
+    const int lane = threadIdx.x, q = lane & 3, quad = lane >> 2;
+    const int64_t item = (int64_t)blockIdx.x * kQuadsPerWave + quad;
+    const bool valid = item < n;
+    const int64_t it = valid ? item : n - 1;
+    float* xq32 = xchg32 + quad * 8 * NA;
+    float s32[NA], w32[NA], v32[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        s32[a] = s[it * 4 * NA + 4 * a + q];
+        w32[a] = w[it * 4 * NA + 4 * a + q];
+        v32[a] = v[it * 4 * NA + 4 * a + q];
+    }
+    HMat<NA> Hs, Hv;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const f32x4 h = *reinterpret_cast<const f32x4*>(h_in + ((it * NB + b) * 4 + q) * 4);
+        Hs.h[b][0] = Hv.h[b][0] = f32x2{h.x, h.y};
+        Hs.h[b][1] = Hv.h[b][1] = f32x2{h.z, h.w};
+    }
+    h_update<NA>(Hs, s32, w32, v32, xq32, q);
+    __builtin_amdgcn_sched_barrier(0);
+    h_update_valu<NA>(Hv, s32, w32, v32, xq32, q);
+    if (valid) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            *reinterpret_cast<f32x4*>(h_shipped + ((it * NB + b) * 4 + q) * 4) = f32x4{Hs.h[b][0].x, Hs.h[b][0].y, Hs.h[b][1].x, Hs.h[b][1].y};
+            *reinterpret_cast<f32x4*>(h_vector + ((it * NB + b) * 4 + q) * 4) = f32x4{Hv.h[b][0].x, Hv.h[b][0].y, Hv.h[b][1].x, Hv.h[b][1].y};
+        }
+    }
+}
+
 }  // namespace slamdev

@@ -99,6 +99,7 @@ int main() {
     EXPECT(slam_get_stats(nullptr, &st) == SLAM_ERR_INVALID);
     EXPECT(slam_reset_stats(nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_best_loss_device_ptr(nullptr, &p, &i64) == SLAM_ERR_INVALID);
+    { float f32[1] = {0.0f}; EXPECT(slam_metric_update_check(nullptr, 3, f32, f32, f32, f32, 1, f32, f32) == SLAM_ERR_INVALID); }
     { int dev = 0; EXPECT(slam_ctx_device(nullptr, &dev) == SLAM_ERR_INVALID); }
     // communicator: bad arguments; without RCCL or without a device creation fails with a message
     slam_comm* comm = nullptr;
