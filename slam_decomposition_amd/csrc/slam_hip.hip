@@ -36,7 +36,7 @@ int drained(slam_ctx* c, int rc) {
         (void)hipStreamSynchronize(c->stream);
         for (hipStream_t st : c->spec_stream)
             if (st) (void)hipStreamSynchronize(st);
-        for (slam_ctx* h : c->helper)
+        for (const auto& h : c->helper)
             if (h && h->stream) (void)hipStreamSynchronize(h->stream);
         (void)hipGetLastError();
         for (auto& st : c->staged) st.valid = false;
@@ -110,15 +110,20 @@ int classify_gates(slam_ctx* c, int k, const int32_t* gate_seq) {
     return GC_DENSE;
 }
 
-template <int K, int GC>
-int launch_eval(slam_ctx* c, const int32_t* gate_seq, const double* d_x, const int32_t* d_tof, int64_t M,
-                double* d_loss, double* d_grad, double* d_unitary) {
-    const size_t lds = lds_bytes<K, GC>();
-    if (!c->max_lds_set[K][GC][0]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_kernel<K, GC>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->max_lds_set[K][GC][0] = true;
-    }
+// f(std::integral_constant<int, GC_...>{}) for the structure class gc: the one place the classes are enumerated
+template <class F>
+int with_gate_class(int gc, F&& f) {
+    if (gc == GC_CX) return f(std::integral_constant<int, GC_CX>{});
+    if (gc == GC_XRI1) return f(std::integral_constant<int, GC_XRI1>{});
+    if (gc == GC_XRI) return f(std::integral_constant<int, GC_XRI>{});
+    if (gc == GC_XGEN) return f(std::integral_constant<int, GC_XGEN>{});
+    return f(std::integral_constant<int, GC_DENSE>{});
+}
+
+template <int K, class Kernel>
+int launch_eval(slam_ctx* c, Kernel kernel, size_t lds, const int32_t* gate_seq, const double* d_x, const int32_t* d_tof, int64_t M, double* d_loss,
+                double* d_grad, double* d_unitary) {
+    { int rc = kernel_per_cu(c, reinterpret_cast<const void*>(kernel), lds, nullptr); if (rc) return rc; }
     EvalArgs<K> a{};
     a.targets = c->targets.as<double>();
     a.x = d_x;
@@ -130,34 +135,21 @@ int launch_eval(slam_ctx* c, const int32_t* gate_seq, const double* d_x, const i
     a.cost_kind = c->cost_kind;
     { int rc = stage_gates(c, K, gate_seq, &a.gates); if (rc) return rc; }
     const int64_t blocks = (M + kQuadsPerWave - 1) / kQuadsPerWave;
-    hipLaunchKernelGGL((eval_kernel<K, GC>), dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a);
     HIP_TRY(hipGetLastError());
     return SLAM_OK;
 }
 
-// MakhlinFunctionalCost: the dense gate class whatever the gates' structure (one instantiation per span)
+// the span's eval kernel; MakhlinFunctionalCost: the dense gate class whatever the gates' structure (one instantiation per span)
 template <int K>
-int launch_eval_mk(slam_ctx* c, const int32_t* gate_seq, const double* d_x, const int32_t* d_tof, int64_t M, double* d_loss, double* d_grad,
+int launch_eval_gc(slam_ctx* c, int gc, const int32_t* gate_seq, const double* d_x, const int32_t* d_tof, int64_t M, double* d_loss, double* d_grad,
                    double* d_unitary) {
-    const size_t lds = lds_bytes<K, GC_DENSE>();
-    if (!c->mk_lds_set[K][0]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_mk_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->mk_lds_set[K][0] = true;
-    }
-    EvalArgs<K> a{};
-    a.targets = c->targets.as<double>();
-    a.x = d_x;
-    a.target_of = d_tof;
-    a.n_items = M;
-    a.loss = d_loss;
-    a.grad = d_grad;
-    a.unitary = d_unitary;
-    a.cost_kind = c->cost_kind;
-    { int rc = stage_gates(c, K, gate_seq, &a.gates); if (rc) return rc; }
-    const int64_t blocks = (M + kQuadsPerWave - 1) / kQuadsPerWave;
-    hipLaunchKernelGGL((eval_mk_kernel<K>), dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    return SLAM_OK;
+    if (c->cost_kind == SLAM_COST_MAKHLIN)
+        return launch_eval<K>(c, &eval_mk_kernel<K>, lds_bytes<K, GC_DENSE>(), gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unitary);
+    return with_gate_class(gc, [&](auto g) -> int {
+        constexpr int GC = decltype(g)::value;
+        return launch_eval<K>(c, &eval_kernel<K, GC>, lds_bytes<K, GC>(), gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unitary);
+    });
 }
 
 struct StageLaunch {
@@ -177,55 +169,25 @@ template <int K>
 int build_minimize_args(slam_ctx* c, const StageLaunch& sl, MinimizeArgs<K>& a) {
     const slam_opt_params* prm = sl.prm;
     a = MinimizeArgs<K>{};
+    fill_stage_common(a, c, prm, sl.exit_loss);
     a.targets = sl.d_stage_targets;
     a.orig = sl.d_active;
     a.first_target = sl.first_target;
     a.x0 = sl.d_x0;
     a.ctl = sl.ctl;
-    a.restarts = prm->restarts;
-    a.maxiter = prm->maxiter;
-    a.gtol = prm->gtol;
-    a.stop_loss = prm->stop_loss;
-    a.gtol_far = prm->gtol_far;
-    a.far_loss = prm->far_loss;
-    a.exit_loss = sl.exit_loss;
-    a.seed = prm->seed;
-    a.target_base = prm->target_base;
-    a.flags = prm->flags & (SLAM_FLAG_EARLY_EXIT | SLAM_FLAG_ORDERED);  // (the upper bits are internal: kFlagTrace, kFlagNoExterior)
-    if (prm->flags & SLAM_FLAG_NO_EXTERIOR) a.flags |= kFlagNoExterior;
-    a.items_per_quad = prm->items_per_quad;
-    a.cost_kind = c->cost_kind;
-    a.solved = c->solved.as<int32_t>();
-    a.item_rec = c->item_rec.as<ItemRec>();
-    a.item_x = c->item_x.as<double>();
-    a.trace_cap = c->trace_cap;
-    a.trace_loss = c->trace_cap > 0 ? c->trace_loss.as<double>() : nullptr;
+    if (prm->flags & SLAM_FLAG_NO_EXTERIOR) a.flags |= kFlagNoExterior;  // (the upper bits are internal: kFlagTrace, kFlagNoExterior)
     if (a.trace_loss) a.flags |= kFlagTrace;
-    a.trace_x = c->trace_cap > 0 ? c->trace_x.as<double>() : nullptr;
+    a.items_per_quad = prm->items_per_quad;
     { int rc = stage_gates(c, K, sl.gate_seq, &a.gates); if (rc) return rc; }
     return SLAM_OK;
 }
 
-template <int K, int GC, bool MQ = false>
-int prepare_minimize_kernel(slam_ctx* c) {
-    const size_t lds = lds_bytes<K, GC>();
-    if (!c->max_lds_set[K][GC][MQ ? 2 : 1]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&minimize_kernel<K, GC, MQ>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&minimize_kernel<K, GC, MQ>),
-                                                             kWave, lds));
-        if (per_cu < 1) per_cu = 1;
-        (MQ ? c->resident_waves_mq : c->resident_waves)[K][GC] = (int64_t)per_cu * c->compute_units;
-        c->max_lds_set[K][GC][MQ ? 2 : 1] = true;
-    }
-    return SLAM_OK;
-}
-
-template <int K, int GC>
-int launch_minimize(slam_ctx* c, const StageLaunch& sl) {
-    const size_t lds = lds_bytes<K, GC>();
-    { int rc = prepare_minimize_kernel<K, GC>(c); if (rc) return rc; }
+// The per-span optimizer launch of spans 1..SLAM_MAX_SPAN_QUAD (minimize_kernel<K, GC>, minimize_mk_kernel<K>): the kernel's
+// argument block, then whatever the kernel takes after it (tail).
+template <int K, class Kernel, class... Tail>
+int launch_persistent(slam_ctx* c, const StageLaunch& sl, Kernel kernel, size_t lds, Tail... tail) {
+    int per_cu = 0;
+    { int rc = kernel_per_cu(c, reinterpret_cast<const void*>(kernel), lds, &per_cu); if (rc) return rc; }
     const slam_opt_params* prm = sl.prm;
     MinimizeArgs<K> a;
     { int rc = build_minimize_args<K>(c, sl, a); if (rc) return rc; }
@@ -239,81 +201,43 @@ int launch_minimize(slam_ctx* c, const StageLaunch& sl) {
     }
     // leave a few wavefront slots free: with several batches in flight the bookkeeping kernels of the other streams
     // (reduce / compaction / epilogue) otherwise wait for the tail of this stage before they can even start
-    const int64_t cap = c->resident_waves[K][GC] - c->reserve_waves > 0 ? c->resident_waves[K][GC] - c->reserve_waves : 1;
+    const int64_t resident = (int64_t)per_cu * c->compute_units;
+    const int64_t cap = resident - c->reserve_waves > 0 ? resident - c->reserve_waves : 1;
     if (blocks > cap) blocks = cap;
     HIP_TRY(hipEventRecord(c->ev_a[K], c->stream));
-    hipLaunchKernelGGL((minimize_kernel<K, GC>), dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a, (const MinimizeArgs<K>*)nullptr, 0);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a, tail...);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev_b[K], c->stream));
     return SLAM_OK;
 }
 
-// MakhlinFunctionalCost, spans 1..SLAM_MAX_SPAN_QUAD: the per-span optimizer launch of the dense gate class
+// MakhlinFunctionalCost: the dense gate class whatever the gates' structure
 template <int K>
-int launch_minimize_mk(slam_ctx* c, const StageLaunch& sl) {
-    const size_t lds = lds_bytes<K, GC_DENSE>();
-    if (!c->mk_lds_set[K][1]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&minimize_mk_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&minimize_mk_kernel<K>), kWave, lds));
-        if (per_cu < 1) per_cu = 1;
-        c->resident_waves_mk[K] = (int64_t)per_cu * c->compute_units;
-        c->mk_lds_set[K][1] = true;
-    }
-    const slam_opt_params* prm = sl.prm;
-    MinimizeArgs<K> a;
-    { int rc = build_minimize_args<K>(c, sl, a); if (rc) return rc; }
-    int64_t blocks = (sl.n_items_max + kQuadsPerWave - 1) / kQuadsPerWave;
-    if (prm->items_per_quad > 1) {
-        blocks = (sl.n_items_max + (int64_t)kQuadsPerWave * prm->items_per_quad - 1) / ((int64_t)kQuadsPerWave * prm->items_per_quad);
-        if (blocks < 1) blocks = 1;
-    }
-    const int64_t cap = c->resident_waves_mk[K] - c->reserve_waves > 0 ? c->resident_waves_mk[K] - c->reserve_waves : 1;
-    if (blocks > cap) blocks = cap;
-    HIP_TRY(hipEventRecord(c->ev_a[K], c->stream));
-    hipLaunchKernelGGL((minimize_mk_kernel<K>), dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_b[K], c->stream));
-    return SLAM_OK;
+int launch_minimize_gc(slam_ctx* c, int gc, const StageLaunch& sl) {
+    if (c->cost_kind == SLAM_COST_MAKHLIN) return launch_persistent<K>(c, sl, &minimize_mk_kernel<K>, lds_bytes<K, GC_DENSE>());
+    return with_gate_class(gc, [&](auto g) -> int {
+        constexpr int GC = decltype(g)::value;
+        return launch_persistent<K>(c, sl, &minimize_kernel<K, GC>, lds_bytes<K, GC>(), (const MinimizeArgs<K>*)nullptr, 0);
+    });
 }
 
 // templates of SLAM_MAX_SPAN_QUAD + 1 .. SLAM_MAX_SPAN_MINIMIZE gates: one wavefront per item (slam_long.hpp)
 int launch_minimize_long(slam_ctx* c, const StageLaunch& sl, int k) {
     const bool mk = c->cost_kind == SLAM_COST_MAKHLIN;
     const void* kern = mk ? reinterpret_cast<const void*>(&minimize_long_mk_kernel) : reinterpret_cast<const void*>(&minimize_long_kernel);
-    int64_t& resident = mk ? c->resident_waves_long_mk : c->resident_waves_long;
-    if (resident == 0) {
-        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes));
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, kLongLdsBytes));
-        resident = (int64_t)(per_cu < 1 ? 1 : per_cu) * c->compute_units;
-    }
+    int per_cu = 0;
+    { int rc = kernel_per_cu(c, kern, kLongLdsBytes, &per_cu); if (rc) return rc; }
+    const int64_t resident = (int64_t)per_cu * c->compute_units;
     const slam_opt_params* prm = sl.prm;
     LongArgs a{};
+    fill_stage_common(a, c, prm, sl.exit_loss);
     a.targets = sl.d_stage_targets;
     a.orig = sl.d_active;
     a.first_target = sl.first_target;
     a.x0 = sl.d_x0;
     a.ctl = sl.ctl;
-    a.restarts = prm->restarts;
-    a.maxiter = prm->maxiter;
-    a.gtol = prm->gtol;
-    a.stop_loss = prm->stop_loss;
-    a.gtol_far = prm->gtol_far;
-    a.far_loss = prm->far_loss;
-    a.exit_loss = sl.exit_loss;
-    a.seed = prm->seed;
-    a.target_base = prm->target_base;
-    a.flags = prm->flags & (SLAM_FLAG_EARLY_EXIT | SLAM_FLAG_ORDERED);
     if (prm->flags & SLAM_FLAG_NO_EXTERIOR) a.flags |= kFlagNoExterior;
-    a.cost_kind = c->cost_kind;
-    a.solved = c->solved.as<int32_t>();
-    a.item_rec = c->item_rec.as<ItemRec>();
-    a.item_x = c->item_x.as<double>();
     a.k = k;
-    a.trace_cap = c->trace_cap;
-    a.trace_loss = c->trace_cap > 0 ? c->trace_loss.as<double>() : nullptr;
-    a.trace_x = c->trace_cap > 0 ? c->trace_x.as<double>() : nullptr;
     { int rc = stage_gates(c, k, sl.gate_seq, &a.gates); if (rc) return rc; }
     int64_t blocks = sl.n_items_max;  // one item per wavefront at a time
     if (blocks > resident) blocks = resident;
@@ -332,12 +256,8 @@ int launch_minimize_long(slam_ctx* c, const StageLaunch& sl, int k) {
 int launch_eval_long(slam_ctx* c, int k, const int32_t* gate_seq, const double* d_x, const int32_t* d_tof, int64_t M, double* d_loss, double* d_grad,
                      double* d_unitary) {
     const bool mk = c->cost_kind == SLAM_COST_MAKHLIN;
-    bool& ready = mk ? c->long_eval_mk_ready : c->long_eval_ready;
-    if (!ready) {
-        HIP_TRY(hipFuncSetAttribute(mk ? reinterpret_cast<const void*>(&eval_long_mk_kernel) : reinterpret_cast<const void*>(&eval_long_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes));
-        ready = true;
-    }
+    const void* kern = mk ? reinterpret_cast<const void*>(&eval_long_mk_kernel) : reinterpret_cast<const void*>(&eval_long_kernel);
+    { int rc = kernel_per_cu(c, kern, kLongLdsBytes, nullptr); if (rc) return rc; }
     LongEvalArgs a{};
     a.targets = c->targets.as<double>();
     a.x = d_x;
@@ -468,21 +388,13 @@ int enqueue_stage(slam_ctx* c, int k, const int32_t* gate_seq, const int32_t* d_
     StageLaunch sl{exit_loss, gate_seq, d_stage_targets, d_active, 0, d_x0, M, prm, ctl};
     int rc;
     const int gc = classify_gates(c, k, gate_seq);
-#define SLAM_MIN_CASE(KK)                                                   \
-    case KK:                                                                \
-        if (c->cost_kind == SLAM_COST_MAKHLIN) rc = launch_minimize_mk<KK>(c, sl); \
-        else if (gc == GC_CX) rc = launch_minimize<KK, GC_CX>(c, sl);       \
-        else if (gc == GC_XRI1) rc = launch_minimize<KK, GC_XRI1>(c, sl);   \
-        else if (gc == GC_XRI) rc = launch_minimize<KK, GC_XRI>(c, sl);     \
-        else if (gc == GC_XGEN) rc = launch_minimize<KK, GC_XGEN>(c, sl);   \
-        else rc = launch_minimize<KK, GC_DENSE>(c, sl);                     \
-        break;
+    static_assert(SLAM_MAX_SPAN_QUAD == 5, "one case per quad-per-item span");
     switch (k) {
-        SLAM_MIN_CASE(1)
-        SLAM_MIN_CASE(2)
-        SLAM_MIN_CASE(3)
-        SLAM_MIN_CASE(4)
-        SLAM_MIN_CASE(5)
+        case 1: rc = launch_minimize_gc<1>(c, gc, sl); break;
+        case 2: rc = launch_minimize_gc<2>(c, gc, sl); break;
+        case 3: rc = launch_minimize_gc<3>(c, gc, sl); break;
+        case 4: rc = launch_minimize_gc<4>(c, gc, sl); break;
+        case 5: rc = launch_minimize_gc<5>(c, gc, sl); break;
         default:
             if (k < 1 || k > SLAM_MAX_SPAN_MINIMIZE) return fail(SLAM_ERR_UNSUPPORTED, "minimize supports spans 1..%d (got %d)", SLAM_MAX_SPAN_MINIMIZE, k);
             rc = launch_minimize_long(c, sl, k);  // SLAM_MAX_SPAN_QUAD < k: one wavefront per item
@@ -560,14 +472,8 @@ int enqueue_fetch_n(slam_ctx* ctx, int nmax, int64_t first, int64_t count, Fetch
     const size_t need = fr.b_loss + fr.b_x + fr.b_cyc;
     char* h = nullptr;
     if (need <= (size_t)1 << 20) {
-        if (need > ctx->h_stage_cap) {
-            if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-            ctx->h_stage = nullptr;
-            ctx->h_stage_cap = 0;
-            HIP_TRY(hipHostMalloc(&ctx->h_stage, need + need / 4, hipHostMallocDefault));
-            ctx->h_stage_cap = need + need / 4;
-        }
-        h = static_cast<char*>(ctx->h_stage);
+        if (need > ctx->h_stage.cap) HIP_TRY(ctx->h_stage.reserve(need + need / 4));
+        h = static_cast<char*>(ctx->h_stage.p);
         fr.staged = true;
     }
     // (big windows: an extra host copy of tens of MB costs more than the runtime's own staging -- round 5 A/B with everything staged:
@@ -583,7 +489,7 @@ int enqueue_fetch_n(slam_ctx* ctx, int nmax, int64_t first, int64_t count, Fetch
 
 void finish_fetch(slam_ctx* ctx, const FetchReq& fr) {
     if (!fr.staged) return;
-    const char* h = static_cast<const char*>(ctx->h_stage);
+    const char* h = static_cast<const char*>(ctx->h_stage.p);
     if (fr.best_loss) std::memcpy(fr.best_loss, h, fr.b_loss);
     if (fr.best_x) std::memcpy(fr.best_x, h + fr.b_loss, fr.b_x);
     if (fr.best_cycles) std::memcpy(fr.best_cycles, h + fr.b_loss + fr.b_x, fr.b_cyc);
@@ -711,41 +617,29 @@ namespace {
 // -----------------------------------------------------------------------------------------------------------------------
 constexpr int kWaveLoopTargetsPerSimd = 1;
 
-template <int GC>
-int launch_span_wave(slam_ctx* c, const WaveLoopArgs& a, int64_t count) {
-    const size_t lds = sizeof(double) * (size_t)(lds_doubles<3, GC>() + kWlLdsDoubles);
-    if (c->resident_waves_wl[GC] == 0) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&span_wave_kernel<GC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&span_wave_kernel<GC>), kWave, lds));
-        c->resident_waves_wl[GC] = (int64_t)(per_cu < 1 ? 1 : per_cu) * c->compute_units;
-    }
-    const int64_t blocks = count;  // one wavefront per target
-    hipLaunchKernelGGL((span_wave_kernel<GC>), dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    return SLAM_OK;
+int launch_span_wave(slam_ctx* c, int gc, const WaveLoopArgs& a, int64_t count) {
+    return with_gate_class(gc, [&](auto g) -> int {
+        constexpr int GC = decltype(g)::value;
+        const size_t lds = sizeof(double) * (size_t)(lds_doubles<3, GC>() + kWlLdsDoubles);
+        { int rc = kernel_per_cu(c, reinterpret_cast<const void*>(&span_wave_kernel<GC>), lds, nullptr); if (rc) return rc; }
+        const int64_t blocks = count;  // one wavefront per target
+        hipLaunchKernelGGL((span_wave_kernel<GC>), dim3((unsigned)blocks), dim3(kWave), lds, c->stream, a);
+        HIP_TRY(hipGetLastError());
+        return SLAM_OK;
+    });
 }
 
 // speculative spans: one launch per span, each on its own stream, then the merge (span_spec_kernel / span_merge_kernel)
-template <int K, int GC>
-int launch_span_spec(slam_ctx* c, const WaveLoopArgs& a, int64_t count, hipStream_t stream) {
-    const size_t lds = sizeof(double) * (size_t)(lds_doubles<K, GC>() + kWlLdsDoubles);
-    if (!c->spec_attr_set[K][GC]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&span_spec_kernel<K, GC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->spec_attr_set[K][GC] = true;
-    }
-    hipLaunchKernelGGL((span_spec_kernel<K, GC>), dim3((unsigned)count), dim3(kWave), lds, stream, a);
-    HIP_TRY(hipGetLastError());
-    return SLAM_OK;
-}
-
 template <int K>
-int launch_span_spec_gc(slam_ctx* c, int gc, const WaveLoopArgs& a, int64_t count, hipStream_t stream) {
-    if (gc == GC_CX) return launch_span_spec<K, GC_CX>(c, a, count, stream);
-    if (gc == GC_XRI1) return launch_span_spec<K, GC_XRI1>(c, a, count, stream);
-    if (gc == GC_XRI) return launch_span_spec<K, GC_XRI>(c, a, count, stream);
-    if (gc == GC_XGEN) return launch_span_spec<K, GC_XGEN>(c, a, count, stream);
-    return launch_span_spec<K, GC_DENSE>(c, a, count, stream);
+int launch_span_spec(slam_ctx* c, int gc, const WaveLoopArgs& a, int64_t count, hipStream_t stream) {
+    return with_gate_class(gc, [&](auto g) -> int {
+        constexpr int GC = decltype(g)::value;
+        const size_t lds = sizeof(double) * (size_t)(lds_doubles<K, GC>() + kWlLdsDoubles);
+        { int rc = kernel_per_cu(c, reinterpret_cast<const void*>(&span_spec_kernel<K, GC>), lds, nullptr); if (rc) return rc; }
+        hipLaunchKernelGGL((span_spec_kernel<K, GC>), dim3((unsigned)count), dim3(kWave), lds, stream, a);
+        HIP_TRY(hipGetLastError());
+        return SLAM_OK;
+    });
 }
 
 constexpr int64_t kOverlapMaxItems = 1 << 17;  // four times what the chip holds at once (2048 wavefronts x 16 items)
@@ -795,14 +689,8 @@ int decompose_wave_loop(slam_ctx* c, int64_t first, int64_t count, int k_min, in
     // argument blocks of the spans (the kernels' own MinimizeArgs layout), staged through pinned memory
     const size_t need = sizeof(MinimizeArgs<1>) * (size_t)(SLAM_MAX_SPAN_EVAL + 1);
     HIP_TRY(c->mq_args.reserve(need));
-    if (need > c->h_mq_cap) {
-        if (c->h_mq_args) (void)hipHostFree(c->h_mq_args);
-        c->h_mq_args = nullptr;
-        c->h_mq_cap = 0;
-        HIP_TRY(hipHostMalloc(&c->h_mq_args, need, hipHostMallocDefault));
-        c->h_mq_cap = need;
-    }
-    MinimizeArgs<1>* h = static_cast<MinimizeArgs<1>*>(c->h_mq_args);
+    HIP_TRY(c->h_mq_args.reserve(need));
+    MinimizeArgs<1>* h = static_cast<MinimizeArgs<1>*>(c->h_mq_args.p);
     const int32_t* gs = gate_seqs;
     for (int k = k_min; k <= k_max; ++k) {
         StageLaunch sl{success_threshold, gs, c->targets.as<double>(), nullptr, 0, nullptr, count * (int64_t)prm->restarts, prm, stage_ctl(c, k)};
@@ -857,10 +745,10 @@ int decompose_wave_loop(slam_ctx* c, int64_t first, int64_t count, int k_min, in
         a.spec_ev = c->spec_ev.as<unsigned long long>();
         if (!c->spec_stream[0]) {
             for (int j = 0; j < 2; ++j) {
-                HIP_TRY(hipStreamCreateWithFlags(&c->spec_stream[j], hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&c->spec_join[j], hipEventDisableTiming));
+                HIP_TRY(hipStreamCreateWithFlags(&c->spec_stream[j].h, hipStreamNonBlocking));
+                HIP_TRY(hipEventCreateWithFlags(&c->spec_join[j].h, hipEventDisableTiming));
             }
-            HIP_TRY(hipEventCreateWithFlags(&c->spec_fork, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&c->spec_fork.h, hipEventDisableTiming));
         }
         HIP_TRY(hipEventRecord(c->spec_fork, c->stream));
         // the longest stage first, on the call's own stream; the others beside it
@@ -873,9 +761,9 @@ int decompose_wave_loop(slam_ctx* c, int64_t first, int64_t count, int k_min, in
             }
             HIP_TRY(hipEventRecord(c->ev_a[k], st));  // span k's own launch (the spans overlap in time: kernel_ms_span[k])
             switch (k) {
-                case 1: rc = launch_span_spec_gc<1>(c, gc, a, count, st); break;
-                case 2: rc = launch_span_spec_gc<2>(c, gc, a, count, st); break;
-                default: rc = launch_span_spec_gc<3>(c, gc, a, count, st); break;
+                case 1: rc = launch_span_spec<1>(c, gc, a, count, st); break;
+                case 2: rc = launch_span_spec<2>(c, gc, a, count, st); break;
+                default: rc = launch_span_spec<3>(c, gc, a, count, st); break;
             }
             if (rc) return rc;
             HIP_TRY(hipEventRecord(c->ev_b[k], st));
@@ -909,11 +797,7 @@ int decompose_wave_loop(slam_ctx* c, int64_t first, int64_t count, int k_min, in
         HIP_TRY(hipGetLastError());
         n_launch = (k_max - k_min + 1) + 1;
     } else {
-        if (gc == GC_CX) rc = launch_span_wave<GC_CX>(c, a, count);
-        else if (gc == GC_XRI1) rc = launch_span_wave<GC_XRI1>(c, a, count);
-        else if (gc == GC_XRI) rc = launch_span_wave<GC_XRI>(c, a, count);
-        else if (gc == GC_XGEN) rc = launch_span_wave<GC_XGEN>(c, a, count);
-        else rc = launch_span_wave<GC_DENSE>(c, a, count);
+        rc = launch_span_wave(c, gc, a, count);
         if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(c->ev_b[0], c->stream));
@@ -976,19 +860,20 @@ int decompose_overlapped(slam_ctx* c, int64_t first, int64_t count, int k_min, i
     // helper contexts (one per span), created on first use; their targets are this context's (borrowed for the call)
     for (int k = k_min; k <= k_max; ++k) {
         if (!c->helper[k]) {
-            int rc = slam_ctx_create(c->device, &c->helper[k]);
+            slam_ctx* h = nullptr;
+            int rc = slam_ctx_create(c->device, &h);
             if (rc) return rc;
-            HIP_TRY(hipEventCreateWithFlags(&c->ov_join[k], hipEventDisableTiming));
+            c->helper[k].reset(h);
+            HIP_TRY(hipEventCreateWithFlags(&c->ov_join[k].h, hipEventDisableTiming));
         }
     }
-    if (!c->ov_fork) HIP_TRY(hipEventCreateWithFlags(&c->ov_fork, hipEventDisableTiming));
+    if (!c->ov_fork) HIP_TRY(hipEventCreateWithFlags(&c->ov_fork.h, hipEventDisableTiming));
     struct Unborrow {
         slam_ctx* c;
         ~Unborrow() {
-            for (slam_ctx* h : c->helper)
+            for (const auto& h : c->helper)
                 if (h) {
-                    h->targets.p = nullptr;
-                    h->targets.cap = 0;
+                    h->targets.unborrow();
                     h->n_targets = 0;
                 }
         }
@@ -1007,9 +892,8 @@ int decompose_overlapped(slam_ctx* c, int64_t first, int64_t count, int k_min, i
         gs += k;
     }
     for (int k = k_max; k >= k_min; --k) {
-        slam_ctx* h = c->helper[k];
-        h->targets.p = c->targets.p;
-        h->targets.cap = c->targets.cap;
+        slam_ctx* h = c->helper[k].get();
+        h->targets.borrow(c->targets);
         h->n_targets = c->n_targets;
         if (h->helper_gates_version != c->gates_version) {
             h->gates_host = c->gates_host;
@@ -1197,9 +1081,11 @@ int decompose_impl(slam_ctx* c, int64_t first, int64_t count, int k_min, int k_m
 template <int K, int GC>
 int launch_minimize_multi(slam_ctx* lead, const MinimizeArgs<K>& common, const MinimizeArgs<K>* d_subs, int n, int64_t items_max_total) {
     const size_t lds = lds_bytes<K, GC>();
-    { int rc = prepare_minimize_kernel<K, GC, true>(lead); if (rc) return rc; }
+    int per_cu = 0;
+    { int rc = kernel_per_cu(lead, reinterpret_cast<const void*>(&minimize_kernel<K, GC, true>), lds, &per_cu); if (rc) return rc; }
     int64_t blocks = (items_max_total + kQuadsPerWave - 1) / kQuadsPerWave;
-    const int64_t cap = lead->resident_waves_mq[K][GC] > 0 ? lead->resident_waves_mq[K][GC] : 1;
+    const int64_t resident = (int64_t)per_cu * lead->compute_units;
+    const int64_t cap = resident > 0 ? resident : 1;
     if (blocks > cap) blocks = cap;
     if (blocks < n) blocks = n;  // every sub-problem has a wavefront that starts on it
     hipLaunchKernelGGL((minimize_kernel<K, GC, true>), dim3((unsigned)blocks), dim3(kWave), lds, lead->stream, common, d_subs, n);
@@ -1257,13 +1143,7 @@ int decompose_multi_body(slam_ctx** cs, int n, int64_t first, int64_t count, int
     const size_t slot = (size_t)n * (sz_ma + sz_ep);
     const size_t need = slot * (size_t)(k_max + 1);
     HIP_TRY(lead->mq_args.reserve(need));
-    if (need > lead->h_mq_cap) {
-        if (lead->h_mq_args) (void)hipHostFree(lead->h_mq_args);
-        lead->h_mq_args = nullptr;
-        lead->h_mq_cap = 0;
-        HIP_TRY(hipHostMalloc(&lead->h_mq_args, need, hipHostMallocDefault));
-        lead->h_mq_cap = need;
-    }
+    HIP_TRY(lead->h_mq_args.reserve(need));
     HIP_TRY(hipEventRecord(lead->ev_t0, lead->stream));
     for (int i = 0; i < n; ++i) {
         slam_ctx* c = cs[i];
@@ -1281,7 +1161,7 @@ int decompose_multi_body(slam_ctx** cs, int n, int64_t first, int64_t count, int
     }
     const int32_t* gs = gate_seqs;
     for (int k = k_min; k <= k_max; ++k) {
-        char* h = static_cast<char*>(lead->h_mq_args) + slot * (size_t)k;
+        char* h = static_cast<char*>(lead->h_mq_args.p) + slot * (size_t)k;
         char* d = static_cast<char*>(lead->mq_args.p) + slot * (size_t)k;
         MinimizeArgs<1>* h_ma = reinterpret_cast<MinimizeArgs<1>*>(h);  // (one layout for every span)
         EpilogueArgs* h_ep = reinterpret_cast<EpilogueArgs*>(h + (size_t)n * sz_ma);
@@ -1306,16 +1186,6 @@ int decompose_multi_body(slam_ctx** cs, int n, int64_t first, int64_t count, int
             h_ep[slot_i] = build_epilogue_args(c, k, r, step);
         }
         HIP_TRY(hipMemcpyAsync(d, h, slot, hipMemcpyHostToDevice, lead->stream));
-#define SLAM_MQ_CASE(KK)                                                                                                                         \
-    case KK: {                                                                                                                                   \
-        const MinimizeArgs<KK>& a0 = *reinterpret_cast<const MinimizeArgs<KK>*>(&h_ma[lo]);                                                      \
-        const MinimizeArgs<KK>* dsub = reinterpret_cast<const MinimizeArgs<KK>*>(d) + lo;                                                        \
-        if (gc == GC_CX) rc = launch_minimize_multi<KK, GC_CX>(lead, a0, dsub, cnt, items_total);                                                \
-        else if (gc == GC_XRI1) rc = launch_minimize_multi<KK, GC_XRI1>(lead, a0, dsub, cnt, items_total);                                       \
-        else if (gc == GC_XRI) rc = launch_minimize_multi<KK, GC_XRI>(lead, a0, dsub, cnt, items_total);                                         \
-        else if (gc == GC_XGEN) rc = launch_minimize_multi<KK, GC_XGEN>(lead, a0, dsub, cnt, items_total);                                       \
-        else rc = launch_minimize_multi<KK, GC_DENSE>(lead, a0, dsub, cnt, items_total);                                                         \
-    } break;
         HIP_TRY(hipEventRecord(lead->ev_a[k], lead->stream));
         for (int lo = 0; lo < n;) {
             const int gc = cls[(size_t)order[(size_t)lo]];
@@ -1323,10 +1193,16 @@ int decompose_multi_body(slam_ctx** cs, int n, int64_t first, int64_t count, int
             while (hi < n && cls[(size_t)order[(size_t)hi]] == gc) ++hi;
             const int cnt = hi - lo;
             const int64_t items_total = (int64_t)cnt * N * prm->restarts;
+            auto launch = [&](auto kc) -> int {
+                constexpr int KK = decltype(kc)::value;
+                const MinimizeArgs<KK>& a0 = *reinterpret_cast<const MinimizeArgs<KK>*>(&h_ma[lo]);
+                const MinimizeArgs<KK>* dsub = reinterpret_cast<const MinimizeArgs<KK>*>(d) + lo;
+                return with_gate_class(gc, [&](auto g) -> int { return launch_minimize_multi<KK, decltype(g)::value>(lead, a0, dsub, cnt, items_total); });
+            };
             switch (k) {
-                SLAM_MQ_CASE(1)
-                SLAM_MQ_CASE(2)
-                SLAM_MQ_CASE(3)
+                case 1: rc = launch(std::integral_constant<int, 1>{}); break;
+                case 2: rc = launch(std::integral_constant<int, 2>{}); break;
+                case 3: rc = launch(std::integral_constant<int, 3>{}); break;
                 default: return fail(SLAM_ERR_UNSUPPORTED, "slam_decompose_multi runs spans 1..3");
             }
             if (rc) return rc;
@@ -1334,7 +1210,6 @@ int decompose_multi_body(slam_ctx** cs, int n, int64_t first, int64_t count, int
             lo = hi;
         }
         HIP_TRY(hipEventRecord(lead->ev_b[k], lead->stream));
-#undef SLAM_MQ_CASE
         hipLaunchKernelGGL(stage_epilogue_multi_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)n), dim3(256), 0, lead->stream,
                            reinterpret_cast<const EpilogueArgs*>(d + (size_t)n * sz_ma));
         HIP_TRY(hipGetLastError());
@@ -1460,19 +1335,19 @@ int slam_ctx_create(int device, slam_ctx** out) {
     if (!c) return fail(SLAM_ERR_NOMEM, "out of host memory");
     c->device = device;
     if (const char* e = std::getenv("SLAM_RESERVE_WAVES")) c->reserve_waves = std::atoi(e) > 0 ? std::atoi(e) : 0;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    hipError_t e = hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking);
     for (int k = 0; k <= SLAM_MAX_SPAN_EVAL && e == hipSuccess; ++k) {
-        e = hipEventCreate(&c->ev_a[k]);
-        if (e == hipSuccess) e = hipEventCreate(&c->ev_b[k]);
+        e = hipEventCreate(&c->ev_a[k].h);
+        if (e == hipSuccess) e = hipEventCreate(&c->ev_b[k].h);
     }
-    if (e == hipSuccess) e = hipEventCreate(&c->ev_t0);
-    if (e == hipSuccess) e = hipEventCreate(&c->ev_t1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done, hipEventBlockingSync | hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreate(&c->ev_t0.h);
+    if (e == hipSuccess) e = hipEventCreate(&c->ev_t1.h);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done.h, hipEventBlockingSync | hipEventDisableTiming);
 
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->h_ctl), sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), hipHostMallocDefault);
+    if (e == hipSuccess) e = c->h_ctl.reserve(sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2));
     if (e == hipSuccess) e = c->counters.reserve(sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2));
     if (e == hipSuccess) e = c->span_gates.reserve((size_t)64 * SLAM_MAX_SPAN_EVAL * 32 * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->h_gates), (size_t)64 * SLAM_MAX_SPAN_EVAL * 32 * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = c->h_gates.reserve((size_t)64 * SLAM_MAX_SPAN_EVAL * 32 * sizeof(double));
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
         e = hipGetDeviceProperties(&prop, device);
@@ -1567,29 +1442,13 @@ static int eval_body(slam_ctx* ctx, int k, const int32_t* gate_seq, const double
     const double* d_x = ctx->ev_x.as<double>();
     const int32_t* d_tof = ctx->ev_tof.as<int32_t>();
     const int gc = classify_gates(ctx, k, gate_seq);
-#define SLAM_EVAL_CASE(KK)                                                                                  \
-    case KK:                                                                                                \
-        if (ctx->cost_kind == SLAM_COST_MAKHLIN) rc = launch_eval_mk<KK>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); \
-        else if (gc == GC_CX) rc = launch_eval<KK, GC_CX>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);   \
-        else if (gc == GC_XRI1) rc = launch_eval<KK, GC_XRI1>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); \
-        else if (gc == GC_XRI) rc = launch_eval<KK, GC_XRI>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); \
-        else if (gc == GC_XGEN) rc = launch_eval<KK, GC_XGEN>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); \
-        else rc = launch_eval<KK, GC_DENSE>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);          \
-        break;
     switch (k) {
-        SLAM_EVAL_CASE(1)
-        SLAM_EVAL_CASE(2)
-        SLAM_EVAL_CASE(3)
-        SLAM_EVAL_CASE(4)
-        default:
-            if (k > SLAM_MAX_SPAN_QUAD) { rc = launch_eval_long(ctx, k, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break; }
-            if (ctx->cost_kind == SLAM_COST_MAKHLIN) rc = launch_eval_mk<5>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
-            else if (gc == GC_CX) rc = launch_eval<5, GC_CX>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
-            else if (gc == GC_XRI1) rc = launch_eval<5, GC_XRI1>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
-            else if (gc == GC_XRI) rc = launch_eval<5, GC_XRI>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
-            else if (gc == GC_XGEN) rc = launch_eval<5, GC_XGEN>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
-            else rc = launch_eval<5, GC_DENSE>(ctx, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit);
-            break;
+        case 1: rc = launch_eval_gc<1>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
+        case 2: rc = launch_eval_gc<2>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
+        case 3: rc = launch_eval_gc<3>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
+        case 4: rc = launch_eval_gc<4>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
+        case 5: rc = launch_eval_gc<5>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
+        default: rc = launch_eval_long(ctx, k, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;  // SLAM_MAX_SPAN_QUAD < k: one wavefront per item
     }
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(loss, ctx->ev_loss.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1745,7 +1604,7 @@ int decompose_predicted_body(slam_ctx* c, int64_t first, int64_t count, int k_ma
     HIP_TRY(c->bucket_lists.reserve((size_t)k_max * N * sizeof(int32_t)));
     HIP_TRY(c->bucket_counts.reserve((size_t)(SLAM_MAX_SPAN_EVAL + 2) * sizeof(int32_t)));
     HIP_TRY(c->ev_weyl.reserve((size_t)N * sizeof(int32_t)));
-    if (!c->h_bucket_counts) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_bucket_counts), (SLAM_MAX_SPAN_EVAL + 2) * sizeof(int32_t), hipHostMallocDefault));
+    HIP_TRY(c->h_bucket_counts.reserve((SLAM_MAX_SPAN_EVAL + 2) * sizeof(int32_t)));
     rc = reserve_stage_buffers(c, N, k_max, prm);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(c->ev_t0, c->stream));

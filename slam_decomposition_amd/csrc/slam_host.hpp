@@ -13,9 +13,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 using namespace slamdev;
@@ -32,12 +35,21 @@ SLAM_INTERNAL int fail(int code, const char* fmt, ...);
             return fail(SLAM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
-// growable device buffer
+// The owners of a context's device resources: four small move-only types (declaring the moves deletes the copies), each empty until
+// its resource exists, each releasing it in its destructor.
+
+// growable device buffer; owns its allocation unless it borrows another buffer's (borrow / unborrow)
 struct SLAM_INTERNAL DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    bool borrowed = false;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), borrowed(o.borrowed) { o.p = nullptr, o.cap = 0, o.borrowed = false; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p), std::swap(cap, o.cap), std::swap(borrowed, o.borrowed); return *this; }
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
+        if (borrowed) return hipErrorInvalidValue;  // the owner's allocation is not this buffer's to free
         if (p) {
             hipError_t e = hipFree(p);
             p = nullptr;
@@ -53,28 +65,76 @@ struct SLAM_INTERNAL DevBuf {
         if (e == hipSuccess) cap = want;
         return e;
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+    // a view of owner's allocation for as long as the owner keeps it; never freed from here
+    void borrow(const DevBuf& owner) {
+        release();
+        p = owner.p;
+        cap = owner.cap;
+        borrowed = true;
     }
+    void unborrow() { if (borrowed) release(); }
     template <class T>
     T* as() { return static_cast<T*>(p); }
+
+private:
+    void release() {
+        if (p && !borrowed) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        borrowed = false;
+    }
 };
 
+// pinned host block of T (hipHostMallocDefault); reserve keeps the block when it is big enough, contents are not carried over
+template <class T>
+struct SLAM_INTERNAL PinnedBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // bytes
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept { std::swap(p, o.p), std::swap(cap, o.cap); return *this; }
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), bytes, hipHostMallocDefault);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    operator T*() const { return p; }
+};
+
+// an event or a stream: created in place (&x.h) where it always was, converts to the raw handle
+template <class T, hipError_t (*Destroy)(T)>
+struct SLAM_INTERNAL Handle {
+    T h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator T() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+
+// Declaration order is the teardown order, reversed: the streams come first, so every buffer, pinned block and event is released
+// before the stream it was used on is destroyed; `helper` follows `targets`, so the helpers (which borrow targets inside a call) go first.
 struct slam_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_a[SLAM_MAX_SPAN_EVAL + 1] = {}, ev_b[SLAM_MAX_SPAN_EVAL + 1] = {};  // optimizer-kernel bracket per span
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr; // whole-call bracket
+    Stream stream;
+    Stream spec_stream[2];  // speculative spans (span_spec_kernel): two side streams
+    Event ev_a[SLAM_MAX_SPAN_EVAL + 1], ev_b[SLAM_MAX_SPAN_EVAL + 1];  // optimizer-kernel bracket per span
+    Event ev_t0, ev_t1;                          // whole-call bracket
     // The host waits for a finished span loop on a blocking-sync event: the waiting thread sleeps instead of
     // spinning, so that many contexts (one host thread each) can be in flight without the threads fighting
     // over cores.  (Measured: with spinning waits, 32 batches in flight run 30 % slower than 16.)
-    hipEvent_t ev_done = nullptr;
-    StageCtl* h_ctl = nullptr;                   // pinned: the stages' control blocks, copied back once per call
-    double* h_gates = nullptr;                   // pinned mirror of span_gates
-    void* h_stage = nullptr;                     // pinned staging for result fetches (same reason: no spinning
-    size_t h_stage_cap = 0;                      // inside the runtime's pageable-copy path)
+    Event ev_done;
+    PinnedBuf<StageCtl> h_ctl;                   // the stages' control blocks, copied back once per call
+    PinnedBuf<double> h_gates;                   // mirror of span_gates
+    PinnedBuf<void> h_stage;                     // staging for result fetches (same reason: no spinning inside the
+                                                 // runtime's pageable-copy path)
     int64_t n_targets = 0;
     int32_t n_gates = 0;
     DevBuf targets, gates;
@@ -101,7 +161,7 @@ struct slam_ctx {
     DevBuf counters;  // StageCtl[SLAM_MAX_SPAN_EVAL + 2]: one control block per span stage (slam_types.hpp)
     DevBuf long_hmem;  // inverse Hessian approximations of the wavefront-per-item kernels: [resident wavefronts][n][128] floats
     DevBuf bucket_lists, bucket_counts;  // slam_decompose_predicted: per-size target lists [k_max][count], their sizes
-    int32_t* h_bucket_counts = nullptr;  // pinned mirror of bucket_counts
+    PinnedBuf<int32_t> h_bucket_counts;  // mirror of bucket_counts
     DevBuf solved;
     DevBuf stage_targets;
     DevBuf span_gates;  // 64 slots x [SLAM_MAX_SPAN_EVAL][32] doubles
@@ -110,29 +170,17 @@ struct slam_ctx {
     std::vector<double> gates_host;
     int compute_units = 0;
     int reserve_waves = 0;  // wavefront slots the persistent optimizer grid leaves free for the span loop's bookkeeping kernels
-    int64_t resident_waves[SLAM_MAX_SPAN_EVAL + 1][kGateClasses] = {};
+    std::vector<std::pair<const void*, int>> launch_cache;  // kernel_per_cu: (kernel, resident workgroups per CU) of every kernel prepared so far
     // eval buffers
     DevBuf ev_x, ev_tof, ev_loss, ev_grad, ev_unitary, ev_weyl;
     DevBuf cov_table, cov_counts, cov_entries;  // slam_coverage_lookup: offsets / kinds / points / bounds, counts, entry per target
     slam_stats stats{};
-    bool max_lds_set[SLAM_MAX_SPAN_EVAL + 1][kGateClasses][3] = {};  // [.][.][0] eval kernel, [1] optimizer kernel, [2] its multi-queue form
-    int64_t resident_waves_mq[SLAM_MAX_SPAN_EVAL + 1][kGateClasses] = {};
-    int64_t resident_waves_long = 0;  // wavefront-per-item kernels (slam_long.hpp): resident wavefronts; 0 = not asked yet
-    bool long_eval_ready = false;
-    // MakhlinFunctionalCost kernels (eval_mk_kernel / minimize_mk_kernel / the *_long_mk_kernel pair): attributes set, resident wavefronts
-    bool mk_lds_set[SLAM_MAX_SPAN_QUAD + 1][2] = {};
-    int64_t resident_waves_mk[SLAM_MAX_SPAN_QUAD + 1] = {};
-    int64_t resident_waves_long_mk = 0;
-    bool long_eval_mk_ready = false;
-    int64_t resident_waves_wl[kGateClasses] = {};  // span_wave_kernel<GC>: resident wavefronts (0 = not asked yet)
-    // speculative spans (span_spec_kernel): staging rows, two side streams, fork / join events
+    // speculative spans (span_spec_kernel): staging rows, fork / join events
     DevBuf spec_loss, spec_x, spec_ev;
-    hipStream_t spec_stream[2] = {nullptr, nullptr};
-    hipEvent_t spec_fork = nullptr, spec_join[2] = {nullptr, nullptr};
-    bool spec_attr_set[4][kGateClasses] = {};
+    Event spec_fork, spec_join[2];
     // overlapped spans (decompose_overlapped): one helper context per span (own stream, own stage buffers; targets borrowed)
-    slam_ctx* helper[SLAM_MAX_SPAN_EVAL + 1] = {};
-    hipEvent_t ov_fork = nullptr, ov_join[SLAM_MAX_SPAN_EVAL + 1] = {};
+    std::unique_ptr<slam_ctx> helper[SLAM_MAX_SPAN_EVAL + 1];
+    Event ov_fork, ov_join[SLAM_MAX_SPAN_EVAL + 1];
     DevBuf slot_ev;                 // (helper side) per-slot evaluation counts of its stage
     bool slot_ev_on = false;        // (helper side) single-stage reductions write slot_ev instead of the stage's counters
     uint64_t gates_version = 1;     // bumped by slam_set_gates
@@ -140,59 +188,57 @@ struct slam_ctx {
     // slam_decompose_multi (this context leads the call): the sub-problems' argument blocks / epilogue arguments per span, staged
     // through pinned memory
     DevBuf mq_args;
-    void* h_mq_args = nullptr;
-    size_t h_mq_cap = 0;
-    int v2_per_cu[SLAM_V2_MAX_SPAN + 1][3][2][2] = {};  // resident workgroups per CU of minimize_v2_kernel<K, QN, GQ, FREE> (0 = not asked yet)
+    PinnedBuf<void> h_mq_args;
     // slam_smush_* (slam_smush.hpp): gate table, staged maps of a span, inverse Hessians of the resident wavefronts
     std::vector<SmushMap> smush_gates_host;
     int smush_qn = 0;
     DevBuf smush_maps, smush_hmem;
-    int64_t resident_waves_smush = 0;  // 0 = not asked yet
     // slam_pd_* / slam_region_lookup (slam_pd.hpp): resident sample coordinates [pd_n][3], per-call staging, region tables
     DevBuf pd_coords, pd_stage, pd_out, reg_table, reg_counts;
     int64_t pd_n = 0;
-
-    ~slam_ctx() {
-        DevBuf* all[] = {&targets, &gates, &active, &active2, &x0, &item_rec, &item_x, &stage_loss, &stage_x, &stage_restart, &best_loss,
-                         &best_x, &best_cycles, &span_loss, &trace_loss, &trace_x, &v2_maps, &v2_bounds, &v2_hmem, &long_hmem, &bucket_lists, &bucket_counts, &v2_cons_w[0], &v2_cons_w[1], &v2_cons_w[2], &v2_cons_w[3], &v2_cons_w[4], &v2_cons_w[5], &counters, &solved, &stage_targets, &span_gates, &ev_x, &ev_tof, &ev_loss, &ev_grad, &ev_unitary, &ev_weyl};
-        for (DevBuf* b : all) b->release();
-        for (hipEvent_t e : ev_a) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_b) if (e) (void)hipEventDestroy(e);
-        if (ev_t0) (void)hipEventDestroy(ev_t0);
-        if (ev_t1) (void)hipEventDestroy(ev_t1);
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        if (h_ctl) (void)hipHostFree(h_ctl);
-        if (h_stage) (void)hipHostFree(h_stage);
-        if (h_gates) (void)hipHostFree(h_gates);
-        if (h_bucket_counts) (void)hipHostFree(h_bucket_counts);
-        if (h_mq_args) (void)hipHostFree(h_mq_args);
-        mq_args.release();
-        spec_loss.release();
-        spec_x.release();
-        spec_ev.release();
-        slot_ev.release();
-        smush_maps.release();
-        smush_hmem.release();
-        cov_table.release();
-        cov_counts.release();
-        cov_entries.release();
-        for (DevBuf* b : {&pd_coords, &pd_stage, &pd_out, &reg_table, &reg_counts}) b->release();
-        if (ov_fork) (void)hipEventDestroy(ov_fork);
-        for (hipEvent_t e : ov_join) if (e) (void)hipEventDestroy(e);
-        for (slam_ctx* h : helper) {
-            if (!h) continue;
-            h->targets.p = nullptr;  // borrowed from this context
-            h->targets.cap = 0;
-            delete h;
-        }
-        if (spec_fork) (void)hipEventDestroy(spec_fork);
-        for (int j = 0; j < 2; ++j) {
-            if (spec_join[j]) (void)hipEventDestroy(spec_join[j]);
-            if (spec_stream[j]) (void)hipStreamDestroy(spec_stream[j]);
-        }
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
+
+// The one place a kernel with dynamic LDS is prepared.  First call for `fn` on this context: sets MaxDynamicSharedMemorySize = lds and
+// asks the occupancy; every call: *per_cu (may be nullptr) = resident workgroups of 64 threads per CU, at least 1.  Keyed by the
+// kernel's address and scanned linearly (a process sees a few dozen instantiations); a context is driven by one host thread at a time.
+// lds must be the same on every call for fn (it is a function of the instantiation); 64 is kWave, the block size of every kernel
+// launched through here.
+inline int kernel_per_cu(slam_ctx* c, const void* fn, size_t lds, int* per_cu) {
+    int v = 0;
+    for (const auto& e : c->launch_cache)
+        if (e.first == fn) { v = e.second; break; }
+    if (v == 0) {
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, 64, lds));
+        if (v < 1) v = 1;
+        c->launch_cache.emplace_back(fn, v);
+    }
+    if (per_cu) *per_cu = v;
+    return SLAM_OK;
+}
+
+// The stage fields that the optimizer kernels' argument blocks (MinimizeArgs, LongArgs, MinimizeV2Args, SmushArgs) spell the same way;
+// everything family-specific (more flags, lists, bounds, hmem, ...) is the caller's.
+template <class A>
+void fill_stage_common(A& a, slam_ctx* c, const slam_opt_params* prm, double exit_loss) {
+    a.restarts = prm->restarts;
+    a.maxiter = prm->maxiter;
+    a.gtol = prm->gtol;
+    a.stop_loss = prm->stop_loss;
+    a.gtol_far = prm->gtol_far;
+    a.far_loss = prm->far_loss;
+    a.exit_loss = exit_loss;
+    a.seed = prm->seed;
+    a.target_base = prm->target_base;
+    a.flags = prm->flags & (SLAM_FLAG_EARLY_EXIT | SLAM_FLAG_ORDERED);
+    a.cost_kind = c->cost_kind;
+    a.solved = c->solved.as<int32_t>();
+    a.item_rec = c->item_rec.as<ItemRec>();
+    a.item_x = c->item_x.as<double>();
+    a.trace_cap = c->trace_cap;
+    a.trace_loss = c->trace_cap > 0 ? c->trace_loss.as<double>() : nullptr;
+    a.trace_x = c->trace_cap > 0 ? c->trace_x.as<double>() : nullptr;
+}
 
 // ---- slam_hip.hip ----------------------------------------------------------------------------------------------------
 // Every API call leaves the context's stream drained: the per-span gate slots, the pinned staging buffers and

@@ -68,7 +68,7 @@ int smush_eval_body(slam_ctx* c, int k, const int32_t* gate_seq, const double* x
     a.maps = d_maps;
     a.k = k;
     a.qn = c->smush_qn;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_smush_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmLdsBytes));
+    { rc = kernel_per_cu(c, reinterpret_cast<const void*>(&eval_smush_kernel), kSmLdsBytes, nullptr); if (rc) return rc; }
     const int64_t blocks = std::min<int64_t>(M, (int64_t)std::max(1, c->compute_units) * 16);
     hipLaunchKernelGGL(eval_smush_kernel, dim3((unsigned)blocks), dim3(kWave), kSmLdsBytes, c->stream, a);
     HIP_TRY(hipGetLastError());
@@ -122,48 +122,28 @@ int smush_minimize_body(slam_ctx* c, int k, const int32_t* gate_seq, const int32
     if (rc) return rc;
     HIP_TRY(c->solved.reserve((size_t)n_active * sizeof(int32_t)));
     HIP_TRY(hipMemsetAsync(c->solved.p, 0, (size_t)n_active * sizeof(int32_t), c->stream));
-    const void* kern = reinterpret_cast<const void*>(&minimize_smush_kernel);
-    if (c->resident_waves_smush == 0) {
-        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmLdsBytes));
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, kSmLdsBytes));
-        c->resident_waves_smush = (int64_t)(per_cu < 1 ? 1 : per_cu) * std::max(1, c->compute_units);
-    }
-    int64_t blocks = std::min<int64_t>(M, c->resident_waves_smush);
+    int per_cu = 0;
+    { rc = kernel_per_cu(c, reinterpret_cast<const void*>(&minimize_smush_kernel), kSmLdsBytes, &per_cu); if (rc) return rc; }
+    const int64_t resident = (int64_t)per_cu * std::max(1, c->compute_units);
+    int64_t blocks = std::min<int64_t>(M, resident);
     if (blocks < 1) blocks = 1;
-    HIP_TRY(c->smush_hmem.reserve((size_t)c->resident_waves_smush * (size_t)SLAM_SMUSH_MAX_N * kSmushNP * sizeof(float)));
+    HIP_TRY(c->smush_hmem.reserve((size_t)resident * (size_t)SLAM_SMUSH_MAX_N * kSmushNP * sizeof(float)));
     SmushArgs a{};
+    fill_stage_common(a, c, prm, exit_loss);
     a.targets = c->targets.as<double>();
     a.active = d_active;
     a.n_active = (int32_t)n_active;
-    a.restarts = prm->restarts;
     a.x0 = d_x0;
     a.init_lo = c->v2_bounds.as<double>();
     a.init_hi = a.init_lo + n;
     a.bound_lo = a.init_lo + 2 * n;
     a.bound_hi = a.init_lo + 3 * n;
-    a.maxiter = prm->maxiter;
-    a.gtol = prm->gtol;
-    a.stop_loss = prm->stop_loss;
-    a.gtol_far = prm->gtol_far;
-    a.far_loss = prm->far_loss;
-    a.exit_loss = exit_loss;
-    a.flags = prm->flags & (SLAM_FLAG_EARLY_EXIT | SLAM_FLAG_ORDERED);
-    a.seed = prm->seed;
-    a.target_base = prm->target_base;
-    a.cost_kind = c->cost_kind;
     a.maps = d_maps;
     a.k = k;
     a.qn = c->smush_qn;
     a.bounded = bounded ? 1 : 0;
-    a.solved = c->solved.as<int32_t>();
-    a.item_rec = c->item_rec.as<ItemRec>();
-    a.item_x = c->item_x.as<double>();
     a.ctl = stage_ctl(c, k);
     a.hmem = c->smush_hmem.as<float>();
-    a.trace_cap = c->trace_cap;
-    a.trace_loss = c->trace_cap > 0 ? c->trace_loss.as<double>() : nullptr;
-    a.trace_x = c->trace_cap > 0 ? c->trace_x.as<double>() : nullptr;
     HIP_TRY(hipEventRecord(c->ev_a[k], c->stream));
     hipLaunchKernelGGL(minimize_smush_kernel, dim3((unsigned)blocks), dim3(kWave), kSmLdsBytes, c->stream, a);
     HIP_TRY(hipGetLastError());

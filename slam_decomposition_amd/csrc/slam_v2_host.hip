@@ -28,7 +28,7 @@ template <int K, int QN>
 int v2_launch_eval(slam_ctx* c, const V2GateMap* d_maps, const double* d_x, const int32_t* d_tof, int64_t M, double* d_loss, double* d_grad,
                    double* d_unitary) {
     const size_t lds = v2_lds_bytes<K, QN>();
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_v2_kernel<K, QN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    { int rc = kernel_per_cu(c, reinterpret_cast<const void*>(&eval_v2_kernel<K, QN>), lds, nullptr); if (rc) return rc; }
     EvalV2Args<K, QN> a{};
     a.targets = c->targets.as<double>();
     a.x = d_x;
@@ -65,42 +65,21 @@ int v2_launch_minimize_gq(slam_ctx* c, const V2Stage& sgt) {
     const size_t lds = v2_lds_bytes<K, QN>();
     // attribute + occupancy once per context and instantiation (both were runtime calls inside every stage launch of the
     // span loop's chain)
-    int& per_cu = c->v2_per_cu[K][QN == 1 ? 0 : (QN == 2 ? 1 : 2)][GQ][FREE ? 1 : 0];
-    if (per_cu == 0) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&minimize_v2_kernel<K, QN, GQ, FREE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int v = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(&minimize_v2_kernel<K, QN, GQ, FREE>), kWave, lds));
-        per_cu = v < 1 ? 1 : v;
-    }
+    int per_cu = 0;
+    { int rc = kernel_per_cu(c, reinterpret_cast<const void*>(&minimize_v2_kernel<K, QN, GQ, FREE>), lds, &per_cu); if (rc) return rc; }
     constexpr int n = CfgV2<K, QN>::N;
     MinimizeV2Args<K, QN> a{};
+    fill_stage_common(a, c, sgt.prm, sgt.exit_loss);
     a.targets = c->targets.as<double>();
     a.active = sgt.d_active;
     a.n_active = sgt.count_on_device ? -1 : sgt.n_active;
-    a.restarts = sgt.prm->restarts;
     a.x0 = sgt.d_x0;
     a.init_lo = sgt.d_bounds;
     a.init_hi = sgt.d_bounds + n;
     a.bound_lo = sgt.d_bounds + 2 * n;
     a.bound_hi = sgt.d_bounds + 3 * n;
-    a.maxiter = sgt.prm->maxiter;
-    a.gtol = sgt.prm->gtol;
-    a.stop_loss = sgt.prm->stop_loss;
-    a.gtol_far = sgt.prm->gtol_far;
-    a.far_loss = sgt.prm->far_loss;
-    a.exit_loss = sgt.exit_loss;
-    a.flags = sgt.prm->flags & (SLAM_FLAG_EARLY_EXIT | SLAM_FLAG_ORDERED);
-    a.seed = sgt.prm->seed;
-    a.target_base = sgt.prm->target_base;
-    a.cost_kind = c->cost_kind;
     a.maps = sgt.d_maps;
-    a.solved = c->solved.as<int32_t>();
-    a.item_rec = c->item_rec.as<ItemRec>();
-    a.item_x = c->item_x.as<double>();
     a.ctl = stage_ctl(c, K);
-    a.trace_cap = c->trace_cap;
-    a.trace_loss = c->trace_cap > 0 ? c->trace_loss.as<double>() : nullptr;
-    a.trace_x = c->trace_cap > 0 ? c->trace_x.as<double>() : nullptr;
     a.bounded = sgt.bounded ? 1 : 0;
     if (c->v2_cons_n[K] > 0) {
         if (c->v2_cons_n[K] != n) return fail(SLAM_ERR_STATE, "the cost constraint of span %d was set for %d parameters, the template has %d (set the gates first)", K, c->v2_cons_n[K], n);
