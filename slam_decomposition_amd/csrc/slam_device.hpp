@@ -1247,6 +1247,22 @@ __device__ __forceinline__ void h_set_identity_where(HMat<NA>& H, int q, bool wh
             }
 }
 
+// The same reset for the lanes that execute it: called inside a divergent region (a quad that takes an item), the plain
+// assignments become moves under the region's EXEC mask -- no select per element, no read of the old value.
+template <int NA>
+__device__ __forceinline__ void h_set_identity(HMat<NA>& H, int q) {
+    const f32x2 z = f32x2{0.0f, 0.0f};
+    const f32x2 d0 = f32x2{q == 0 ? 1.0f : 0.0f, q == 1 ? 1.0f : 0.0f};
+    const f32x2 d1 = f32x2{q == 2 ? 1.0f : 0.0f, q == 3 ? 1.0f : 0.0f};
+#pragma unroll
+    for (int b = 0; b < NA; ++b)
+#pragma unroll
+        for (int a = 0; a <= b; ++a) {
+            H.h[blk(a, b)][0] = (a == b) ? d0 : z;
+            H.h[blk(a, b)][1] = (a == b) ? d1 : z;
+        }
+}
+
 // out = H v  (v, out distributed: slot a of lane q = component 4a + q); fp32 arithmetic.
 // Lane q holds row q of each upper block (a, b): it adds H[4a+q][4b+e] v[4b+e] to its own out[a]
 // and owes H[4a+q][4b+e] v[4a+q] to lane e's out[b]; those "transposed" sums go through LDS as soon

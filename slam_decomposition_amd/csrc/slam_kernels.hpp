@@ -490,6 +490,9 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
                         alpha = 0.0; gp = 0.0; f = 0.0; grow = 1.0; pp = 0.0; hs1 = 0.0;
                         nev = 0; iters = 0; nback = 0; nstall = 0; status = ST_MAXITER;
                         scaled = false; fresh = true; live = true; taken = true;
+                        // (plain assignments inside this divergent region: moves under EXEC, no select per element of H; no MFMA
+                        // in here -- h_update ignores EXEC and stays in wave-uniform flow)
+                        h_set_identity<NA>(H, q);
                     }
                     if constexpr (kRing) {
                         if (shared && get) {
@@ -538,7 +541,6 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
                     }
                 }
             }
-            if (__any(taken)) h_set_identity_where<NA>(H, q, taken);
             if constexpr (MK) {
                 if (__any(taken)) {  // (all lanes: the quad exchanges; tcol is a valid column for idle quads too)
                     double g3[3];
