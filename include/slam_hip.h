@@ -163,6 +163,32 @@ int slam_sample_haar(slam_ctx* ctx, uint64_t seed, int64_t first_index, int64_t 
 int slam_get_targets(slam_ctx* ctx, int64_t first, int64_t count, double* out);
 
 /*
+ * The same generator for an explicit list of stream indices: T_i = Haar(seed, indices[i]) becomes the resident batch (it replaces
+ * the resident targets like slam_sample_haar).  indices: host memory, int64[n_targets], each >= 0, any order, repeats allowed.
+ * slam_sample_haar_indexed(seed, {s, s + 1, ..}) gives the bits of slam_sample_haar(seed, s, ..).
+ */
+int slam_sample_haar_indexed(slam_ctx* ctx, uint64_t seed, const int64_t* indices, int64_t n_targets);
+
+/*
+ * Haar targets of a known template size, selected on the device: Haar2Sample / Haar3Sample (src/slam/sampler.py:73-107: draw, run the
+ * analytic sqrt(iSWAP) pass, count its gates, discard on a mismatch) for any gate sequence.  Every candidate i of
+ * [first_index, first_index + n_candidates) gets the unitary of slam_sample_haar(seed, i) and the span of slam_predict_spans for the
+ * half-spaces `point`, `bounds[k_max][14]`, `tol` (0 local, 1 .. k_max, k_max + 1 out of reach), both in registers: a rejected
+ * candidate costs no memory traffic.  A candidate is selected when span_lo <= span <= span_hi and, with margin > 0, when it gets the
+ * same span with tol + margin and with tol - margin (it is clear of every region boundary by `margin`, units of pi).
+ *   n_selected   the number of selected candidates of the whole range (may exceed capacity)
+ *   indices_out  host memory, int64[capacity]: the stream indices of the first min(*n_selected, capacity) selected candidates in
+ *                increasing order -- ranks come from ballots and prefix sums, never from an atomic, so the list depends on the
+ *                arguments alone; feed it to slam_sample_haar_indexed
+ *   span_counts  optional, host memory, int64[k_max + 2]: ADDED TO with the number of scanned candidates per span at the plain tol
+ *                (their shares are the Haar volumes of the prefix regions)
+ * The resident targets are not touched.  n_candidates <= 2^31 - 1 per call, 0 <= span_lo <= span_hi <= k_max + 1, margin >= 0.
+ */
+int slam_haar_select_spans(slam_ctx* ctx, uint64_t seed, int64_t first_index, int64_t n_candidates, int k_max, const double* point,
+                           const double* bounds, double tol, double margin, int32_t span_lo, int32_t span_hi, int64_t capacity,
+                           int64_t* n_selected, int64_t* indices_out, int64_t* span_counts);
+
+/*
  * Weyl-chamber coordinates (c1, c2, c3), in units of pi, of 4x4 unitaries -- weylchamber.c1c2c3 as called by
  * VariationalTemplate.target_invariant (src/slam/basis_abc.py:80-84) and on the optimizer's results
  * (src/slam/optimizer.py:85,103,224) -- computed on the device, one thread per unitary.  ndigits >= 0 rounds like
@@ -682,7 +708,8 @@ const char* slam_version(void);
  *      later: slam_pd_sample, slam_pd_extremes, slam_pd_filter and slam_region_lookup (new symbols only);
  *      later: slam_hw_queues_requested (a new symbol only);
  *      later: slam_kak, slam_targets_kak and slam_complete_locals (new symbols only);
- *      later: slam_metric_update_check (a new symbol only).
+ *      later: slam_metric_update_check (a new symbol only);
+ *      later: slam_haar_select_spans and slam_sample_haar_indexed (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -63,6 +63,8 @@ EXPORTED_SYMBOLS = (
     "slam_coverage_lookup",
     "slam_eval_c1c2c3",
     "slam_sample_haar",
+    "slam_sample_haar_indexed",
+    "slam_haar_select_spans",
     "slam_get_targets",
     "slam_eval_loss_grad",
     "slam_eval_unitary",
@@ -229,6 +231,10 @@ def load_library() -> C.CDLL:
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
     lib.slam_eval_c1c2c3.argtypes = [P, C.c_int32, P, P, C.c_int64, C.c_int32, P]
     lib.slam_sample_haar.argtypes = [P, C.c_uint64, C.c_int64, C.c_int64]
+    if hasattr(lib, "slam_haar_select_spans"):
+        lib.slam_sample_haar_indexed.argtypes = [P, C.c_uint64, P, C.c_int64]
+        lib.slam_haar_select_spans.argtypes = [P, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, C.c_double, C.c_int32,
+                                               C.c_int32, C.c_int64, C.POINTER(C.c_int64), P, P]
     lib.slam_get_targets.argtypes = [P, C.c_int64, C.c_int64, P]
     lib.slam_eval_loss_grad.argtypes = [P, C.c_int, P, P, P, C.c_int64, P, P]
     lib.slam_eval_unitary.argtypes = [P, C.c_int, P, P, P, C.c_int64, P, P]
@@ -429,6 +435,21 @@ def device_count() -> int:
     return n.value
 
 
+def _span_half_spaces(gate_coords_seq, k_max: int):
+    """What slam_predict_spans / slam_haar_select_spans take for a gate sequence: the first gate's alcove point [4] and the half-spaces
+    of the prefixes g_1 .. g_k, k = 2 .. k_max, as rows k - 1 of [k_max, 14] (coverage.region)."""
+    from . import coverage
+
+    g = np.asarray(gate_coords_seq, dtype=np.float64).reshape(-1, 3)
+    if not 1 <= k_max <= min(len(g), MAX_SPAN_EVAL):
+        raise ValueError(f"k_max must be 1..{min(len(g), MAX_SPAN_EVAL)}")
+    point = np.ascontiguousarray(coverage.alcove_coordinates(g[:1])[0])
+    bounds = np.full((k_max, len(coverage._PATTERNS)), -np.inf)
+    for k in range(2, k_max + 1):
+        bounds[k - 1] = coverage.region(g[:k])
+    return point, bounds
+
+
 class Context:
     """One GPU: resident targets + gate table + work buffers (``slam_ctx``)."""
 
@@ -550,16 +571,8 @@ class Context:
         """Template size every resident target of [first, first + count) needs with the gate sequence whose Weyl coordinates are
         ``gate_coords_seq`` (0 local, 1..k_max, k_max + 1 out of reach): ``coverage.minimal_prefix`` evaluated on the device
         (slam_predict_spans) -- the half-spaces of the sequence's prefixes are computed here, the targets never leave the GPU."""
-        from . import coverage
-
-        g = np.asarray(gate_coords_seq, dtype=np.float64).reshape(-1, 3)
-        if not 1 <= k_max <= min(len(g), MAX_SPAN_EVAL):
-            raise ValueError(f"k_max must be 1..{min(len(g), MAX_SPAN_EVAL)}")
+        point, bounds = _span_half_spaces(gate_coords_seq, k_max)
         count = self.n_targets - first if count is None else count
-        point = np.ascontiguousarray(coverage.alcove_coordinates(g[:1])[0])
-        bounds = np.full((k_max, len(coverage._PATTERNS)), -np.inf)
-        for k in range(2, k_max + 1):
-            bounds[k - 1] = coverage.region(g[:k])
         out = np.zeros(count, dtype=np.int32)
         _check(self._lib.slam_predict_spans(self._h, int(first), int(count), int(k_max), _ptr(point), _ptr(bounds), float(tol), _ptr(out)))
         return out
@@ -666,6 +679,31 @@ class Context:
         """Generate the resident batch on the device: T_i = Haar(seed, first_index + i)."""
         _check(self._lib.slam_sample_haar(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index), int(n_targets)))
         self.n_targets = int(n_targets)
+
+    def sample_haar_indexed(self, seed: int, indices) -> None:
+        """Generate the resident batch on the device from chosen stream indices: T_i = Haar(seed, indices[i]) (any order, repeats
+        allowed) -- slam_sample_haar_indexed."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        _check(self._lib.slam_sample_haar_indexed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(idx), idx.size))
+        self.n_targets = int(idx.size)
+
+    def haar_select_spans(self, seed: int, first_index: int, n_candidates: int, gate_coords_seq, k_max: int, span_lo: int, span_hi: int,
+                          capacity: int, tol: float = 2e-8, margin: float = 0.0):
+        """Among the Haar candidates ``first_index .. first_index + n_candidates`` of the stream ``seed``, those whose template size
+        with the gate sequence ``gate_coords_seq`` (as ``predict_spans`` sees it: 0 local, 1..k_max, k_max + 1 out of reach) lies in
+        ``[span_lo, span_hi]`` -- and, with ``margin > 0``, does not change at ``tol + margin`` and ``tol - margin``
+        (slam_haar_select_spans: drawn, classified and ranked on the device; the resident targets are not touched).  Returns
+        ``(indices, n_selected, span_counts)``: the stream indices of the first ``min(n_selected, capacity)`` selected candidates in
+        increasing order (int64), the number selected in the whole range, and int64[k_max + 2] candidates per span at ``tol``."""
+        point, bounds = _span_half_spaces(gate_coords_seq, k_max)
+        cap = max(int(capacity), 0)
+        idx = np.zeros(cap, dtype=np.int64)
+        counts = np.zeros(int(k_max) + 2, dtype=np.int64)
+        m = C.c_int64(0)
+        _check(self._lib.slam_haar_select_spans(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index), int(n_candidates), int(k_max),
+                                                _ptr(point), _ptr(bounds), float(tol), float(margin), int(span_lo), int(span_hi),
+                                                int(capacity), C.byref(m), _ptr(idx) if cap else None, _ptr(counts)))
+        return idx[: min(int(m.value), cap)], int(m.value), counts
 
     def get_targets(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """Resident targets [first, first + count) as complex128[count, 4, 4]."""

@@ -1,9 +1,10 @@
 // slam_geometry.hip -- host side of libslamhip.so, geometry unit: Weyl coordinates, span prediction and coverage lookups, the Haar
-// sampler, parallel-drive coverage samples and region lookups, the KAK decomposition and local-gate completion (slam_weyl.hpp,
-// slam_sampler.hpp, slam_pd.hpp, slam_kak.hpp).
+// sampler and its selection by template size, parallel-drive coverage samples and region lookups, the KAK decomposition and
+// local-gate completion (slam_weyl.hpp, slam_sampler.hpp, slam_span_sampler.hpp, slam_pd.hpp, slam_kak.hpp).
 #include "slam_host.hpp"
 #include "slam_sampler.hpp"
 #include "slam_weyl.hpp"
+#include "slam_span_sampler.hpp"
 #include "slam_pd.hpp"
 #include "slam_kak.hpp"
 
@@ -13,8 +14,8 @@ int enqueue_c1c2c3(slam_ctx* c, const double* d_unitaries, int64_t count, int nd
     return SLAM_OK;
 }
 
-int enqueue_span_predict(slam_ctx* c, int64_t first, int64_t count, int k_max, const double* point, const double* bounds, double tol,
-                         int32_t* d_spans) {
+// the caller's half-spaces (slam_predict_spans: point[4], bounds[k_max][14], tol) as the kernels' argument block
+static SpanRegions span_regions(int k_max, const double* point, const double* bounds, double tol) {
     static_assert(sizeof(SpanRegions{}.bounds) / sizeof(SpanRegions{}.bounds[0]) == SLAM_MAX_SPAN_EVAL, "SpanRegions::bounds holds SLAM_MAX_SPAN_EVAL prefixes");
     SpanRegions r{};
     r.k_max = k_max;
@@ -22,6 +23,12 @@ int enqueue_span_predict(slam_ctx* c, int64_t first, int64_t count, int k_max, c
     for (int j = 0; j < 4; ++j) r.point[j] = point[j];
     for (int k = 2; k <= k_max; ++k)
         for (int p = 0; p < kSpanPatterns; ++p) r.bounds[k - 1][p] = bounds[(size_t)(k - 1) * kSpanPatterns + p];
+    return r;
+}
+
+int enqueue_span_predict(slam_ctx* c, int64_t first, int64_t count, int k_max, const double* point, const double* bounds, double tol,
+                         int32_t* d_spans) {
+    const SpanRegions r = span_regions(k_max, point, bounds, tol);
     hipLaunchKernelGGL(span_predict_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, c->targets.as<double>() + first * 32, count, r,
                        d_spans);
     HIP_TRY(hipGetLastError());
@@ -244,6 +251,89 @@ int slam_sample_haar(slam_ctx* ctx, uint64_t seed, int64_t first_index, int64_t 
     ctx->n_targets = n_targets;
     ctx->result_nmax = 0;
     ctx->result_filled = 0;
+    return SLAM_OK;
+}
+
+int slam_sample_haar_indexed(slam_ctx* ctx, uint64_t seed, const int64_t* indices, int64_t n_targets) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (n_targets <= 0 || n_targets > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "n_targets must be in 1..2^31-1");
+    if (!indices) return fail(SLAM_ERR_INVALID, "indices is NULL");
+    for (int64_t i = 0; i < n_targets; ++i)
+        if (indices[i] < 0) return fail(SLAM_ERR_INVALID, "indices[%lld] < 0", (long long)i);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->targets.reserve((size_t)n_targets * 32 * sizeof(double)));
+    HIP_TRY(ctx->sel_indices.reserve((size_t)n_targets * sizeof(int64_t)));
+    HIP_TRY(hipMemcpyAsync(ctx->sel_indices.p, indices, (size_t)n_targets * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(haar_indexed_kernel, dim3((unsigned)((n_targets + 127) / 128)), dim3(128), 0, ctx->stream, ctx->targets.as<double>(),
+                       ctx->sel_indices.as<int64_t>(), n_targets, seed);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->n_targets = n_targets;
+    ctx->result_nmax = 0;
+    ctx->result_filled = 0;
+    return SLAM_OK;
+}
+
+int slam_haar_select_spans(slam_ctx* ctx, uint64_t seed, int64_t first_index, int64_t n_candidates, int k_max, const double* point,
+                           const double* bounds, double tol, double margin, int32_t span_lo, int32_t span_hi, int64_t capacity,
+                           int64_t* n_selected, int64_t* indices_out, int64_t* span_counts) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (n_candidates < 0 || n_candidates > 0x7fffffffLL)
+        return fail(SLAM_ERR_INVALID, "n_candidates must be in 0..2^31-1 (got %lld)", (long long)n_candidates);
+    if (first_index < 0 || first_index > INT64_MAX - n_candidates) return fail(SLAM_ERR_INVALID, "first_index out of range (%lld)", (long long)first_index);
+    if (k_max < 1 || k_max > SLAM_MAX_SPAN_EVAL) return fail(SLAM_ERR_INVALID, "k_max must be 1..%d (got %d)", SLAM_MAX_SPAN_EVAL, k_max);
+    if (!point || (k_max > 1 && !bounds)) return fail(SLAM_ERR_INVALID, "point / bounds is NULL");
+    if (!std::isfinite(tol)) return fail(SLAM_ERR_INVALID, "tol must be finite");
+    if (!(margin >= 0.0) || !std::isfinite(margin)) return fail(SLAM_ERR_INVALID, "margin must be finite and >= 0 (got %g)", margin);
+    if (span_lo > span_hi) return fail(SLAM_ERR_INVALID, "span_lo > span_hi (%d > %d)", span_lo, span_hi);
+    if (span_lo < 0 || span_hi > k_max + 1) return fail(SLAM_ERR_INVALID, "spans must lie in 0..k_max + 1 = %d (got %d..%d)", k_max + 1, span_lo, span_hi);
+    if (capacity < 0) return fail(SLAM_ERR_INVALID, "capacity < 0");
+    if (!n_selected || (capacity > 0 && !indices_out)) return fail(SLAM_ERR_INVALID, "n_selected / indices_out is NULL");
+    *n_selected = 0;
+    if (n_candidates == 0) return SLAM_OK;
+    static_assert(kSelBins == SLAM_MAX_SPAN_EVAL + 2, "one histogram bin per span, local and out of reach");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t n_blocks = (n_candidates + kSelBlock - 1) / kSelBlock;
+    const int64_t cap = capacity < n_candidates ? capacity : n_candidates;
+    // sel_blocks: votes per block [n_blocks], their exclusive scan [n_blocks] (32 bits each), then the total (64 bits, 8-byte aligned)
+    const size_t tot_b = 0, off_b = (size_t)n_blocks * sizeof(uint32_t), sum_b = (2 * off_b + 7) & ~(size_t)7;
+    HIP_TRY(ctx->sel_masks.reserve((size_t)n_blocks * kSelWaves * sizeof(unsigned long long)));
+    HIP_TRY(ctx->sel_blocks.reserve(sum_b + sizeof(unsigned long long)));
+    HIP_TRY(ctx->sel_counts.reserve(kSelBins * sizeof(unsigned long long)));
+    if (cap > 0) HIP_TRY(ctx->sel_indices.reserve((size_t)cap * sizeof(int64_t)));
+    char* bl = ctx->sel_blocks.as<char>();
+    HIP_TRY(hipMemsetAsync(ctx->sel_counts.p, 0, kSelBins * sizeof(unsigned long long), ctx->stream));
+    const SpanRegions r = span_regions(k_max, point, bounds, tol);
+    SelArgs a{};
+    a.seed = seed;
+    a.first_index = first_index;
+    a.n = n_candidates;
+    a.margin = margin;
+    a.span_lo = span_lo;
+    a.span_hi = span_hi;
+    hipLaunchKernelGGL(haar_span_select_kernel, dim3((unsigned)n_blocks), dim3(kSelBlock), 0, ctx->stream, r, a,
+                       ctx->sel_masks.as<unsigned long long>(), reinterpret_cast<uint32_t*>(bl + tot_b), ctx->sel_counts.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, reinterpret_cast<const uint32_t*>(bl + tot_b), n_blocks,
+                       reinterpret_cast<uint32_t*>(bl + off_b), reinterpret_cast<unsigned long long*>(bl + sum_b));
+    HIP_TRY(hipGetLastError());
+    if (cap > 0) {
+        hipLaunchKernelGGL(span_scatter_kernel, dim3((unsigned)n_blocks), dim3(kSelBlock), 0, ctx->stream, ctx->sel_masks.as<unsigned long long>(),
+                           reinterpret_cast<const uint32_t*>(bl + off_b), first_index, cap, ctx->sel_indices.as<int64_t>());
+        HIP_TRY(hipGetLastError());
+    }
+    unsigned long long total = 0, counts[kSelBins] = {0};
+    HIP_TRY(hipMemcpyAsync(&total, bl + sum_b, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(counts, ctx->sel_counts.p, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *n_selected = (int64_t)total;
+    const int64_t copy = (int64_t)total < cap ? (int64_t)total : cap;
+    if (copy > 0) {
+        HIP_TRY(hipMemcpyAsync(indices_out, ctx->sel_indices.p, (size_t)copy * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (span_counts)
+        for (int b = 0; b < k_max + 2; ++b) span_counts[b] += (int64_t)counts[b];
     return SLAM_OK;
 }
 

@@ -196,6 +196,9 @@ struct slam_ctx {
     // slam_pd_* / slam_region_lookup (slam_pd.hpp): resident sample coordinates [pd_n][3], per-call staging, region tables
     DevBuf pd_coords, pd_stage, pd_out, reg_table, reg_counts;
     int64_t pd_n = 0;
+    // slam_haar_select_spans (slam_span_sampler.hpp): ballot masks per wavefront; votes per block, their scan, the total; selected
+    // indices (also the staged index list of slam_sample_haar_indexed); span histogram
+    DevBuf sel_masks, sel_blocks, sel_indices, sel_counts;
 };
 
 // The one place a kernel with dynamic LDS is prepared.  First call for `fn` on this context: sets MaxDynamicSharedMemorySize = lds and

@@ -28,12 +28,10 @@ __device__ __forceinline__ void philox_normal_pair(uint64_t seed, uint64_t idx, 
     n1 = r * s;
 }
 
-__global__ void __launch_bounds__(128) haar_targets_kernel(double* targets, int64_t first_index, int64_t n, uint64_t seed) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    const uint64_t idx = (uint64_t)(first_index + t);
+// Haar unitary `idx` of the stream `seed` in registers: entry (r, c) = zr[r][c] + i zi[r][c].  The one generator: haar_targets_kernel,
+// haar_indexed_kernel and haar_span_select_kernel (slam_span_sampler.hpp) all draw their unitaries here.
+__device__ __forceinline__ void haar_unitary(uint64_t seed, uint64_t idx, double (&zr)[4][4], double (&zi)[4][4]) {
     // Ginibre matrix, entry (r, c) = normals (2e, 2e + 1), e = 4r + c (scale is irrelevant for Q)
-    double zr[4][4], zi[4][4];
 #pragma unroll
     for (int e = 0; e < 16; ++e) philox_normal_pair(seed, idx, (uint32_t)e, zr[e >> 2][e & 3], zi[e >> 2][e & 3]);
     // Gram-Schmidt on the columns, two passes per column (CGS2: orthogonal to rounding even for ill-conditioned Z)
@@ -63,9 +61,29 @@ __global__ void __launch_bounds__(128) haar_targets_kernel(double* targets, int6
 #pragma unroll
         for (int r = 0; r < 4; ++r) { zr[r][c] *= inv; zi[r][c] *= inv; }
     }
-    double2* out = reinterpret_cast<double2*>(targets + t * 32);
+}
+
+__device__ __forceinline__ void store_unitary(double* dst, const double (&zr)[4][4], const double (&zi)[4][4]) {
+    double2* out = reinterpret_cast<double2*>(dst);
 #pragma unroll
     for (int e = 0; e < 16; ++e) out[e] = make_double2(zr[e >> 2][e & 3], zi[e >> 2][e & 3]);
+}
+
+__global__ void __launch_bounds__(128) haar_targets_kernel(double* targets, int64_t first_index, int64_t n, uint64_t seed) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    double zr[4][4], zi[4][4];
+    haar_unitary(seed, (uint64_t)(first_index + t), zr, zi);
+    store_unitary(targets + t * 32, zr, zi);
+}
+
+// slam_sample_haar_indexed: T_t = Haar(seed, indices[t]) -- any order, repeats allowed
+__global__ void __launch_bounds__(128) haar_indexed_kernel(double* targets, const int64_t* __restrict__ indices, int64_t n, uint64_t seed) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    double zr[4][4], zi[4][4];
+    haar_unitary(seed, (uint64_t)indices[t], zr, zi);
+    store_unitary(targets + t * 32, zr, zi);
 }
 
 }  // namespace slamdev

@@ -191,11 +191,9 @@ __device__ inline void alcove_point(double c1, double c2, double c3, double shif
     for (int j = 0; j < 4; ++j) a[j] = e[j + s];
 }
 
-__global__ void span_predict_kernel(const double* __restrict__ U, int64_t M, SpanRegions r, int32_t* __restrict__ spans) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    double c[3];
-    weyl_c1c2c3(U + i * 32, 8, c);
+// template size of the class with Weyl coordinates c (weyl_c1c2c3, 8 digits) for the regions r widened by tol: 0 local, 1 .. k_max,
+// k_max + 1 out of reach.  The one classifier: span_predict_kernel and haar_span_select_kernel (slam_span_sampler.hpp) both ask here.
+__device__ __forceinline__ int span_classify(const double (&c)[3], const SpanRegions& r, double tol) {
     int best = r.k_max + 1;
     bool local = false;
     for (int sh = 0; sh < 2; ++sh) {
@@ -206,16 +204,24 @@ __global__ void span_predict_kernel(const double* __restrict__ U, int64_t M, Spa
         const double g1 = a[3], g2 = a[2], g3 = a[1], g4 = a[0];  // g_k = gamma_{5 - k}
         const double sums[kSpanPatterns] = {g1, g2, g3, g4, g1 + g2, g1 + g3, g1 + g4, g2 + g3, g2 + g4, g3 + g4,
                                             g1 + g2 + g3, g1 + g2 + g4, g1 + g3 + g4, g2 + g3 + g4};
-        const double t1 = (r.tol > 0.0 ? r.tol : 0.0) + 1e-12;
+        const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
         if (fabs(a[0] - r.point[0]) <= t1 && fabs(a[1] - r.point[1]) <= t1 && fabs(a[2] - r.point[2]) <= t1 && fabs(a[3] - r.point[3]) <= t1)
             best = 1;
         for (int k = 2; k <= r.k_max && k < best; ++k) {
             bool ok = true;
-            for (int p = 0; p < kSpanPatterns; ++p) ok = ok && (sums[p] >= r.bounds[k - 1][p] - r.tol);
+            for (int p = 0; p < kSpanPatterns; ++p) ok = ok && (sums[p] >= r.bounds[k - 1][p] - tol);
             if (ok) best = k;
         }
     }
-    spans[i] = local ? 0 : best;
+    return local ? 0 : best;
+}
+
+__global__ void span_predict_kernel(const double* __restrict__ U, int64_t M, SpanRegions r, int32_t* __restrict__ spans) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    double c[3];
+    weyl_c1c2c3(U + i * 32, 8, c);
+    spans[i] = span_classify(c, r, r.tol);
 }
 
 // ---------------------------------------------------------------------------------

@@ -45,6 +45,8 @@ int main() {
     EXPECT(slam_set_targets(nullptr, d, 1) == SLAM_ERR_INVALID);
     EXPECT(slam_sample_haar(nullptr, 1, 0, 1) == SLAM_ERR_INVALID);
     EXPECT(slam_get_targets(nullptr, 0, 1, d) == SLAM_ERR_INVALID);
+    EXPECT(slam_sample_haar_indexed(nullptr, 1, &i64, 1) == SLAM_ERR_INVALID);
+    EXPECT(slam_haar_select_spans(nullptr, 1, 0, 1, 3, d, d, 0.0, 0.0, 2, 3, 1, &i64, &i64, nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_c1c2c3(nullptr, d, 1, 8, d) == SLAM_ERR_INVALID);
     EXPECT(slam_targets_c1c2c3(nullptr, 0, 1, 8, d) == SLAM_ERR_INVALID);
     EXPECT(slam_kak(nullptr, d, 1, d, d, d, d, d, d) == SLAM_ERR_INVALID);
