@@ -227,6 +227,24 @@ int slam_complete_locals(slam_ctx* ctx, int k, const int32_t* gate_seq, const do
                          double* loss_out, double* gap_out);
 
 /*
+ * Closed-form decomposition into sqrt(iSWAP) gates on the device, one thread per resident target (csrc/slam_analytic.hpp; Huang et
+ * al., arXiv:2105.06074; the reference's RootiSwapWeylDecomposition.riswapWeylDecomp,
+ * src/slam/utils/transpiler_pass/weyl_decompose.py:343-449): no optimiser, no restarts, no gate table -- the basis gate is
+ * S = RiSwapGate(1/2) = exp(i pi/8 (XX + YY)).  For the resident targets [first, first + count) (nothing is uploaded):
+ *   x_out   double[count][24]  the 6 (k + 1) template angles in the index order of slam_eval_unitary in the front of the row, zeros
+ *                              behind; layers 0 and k are the exterior: template(x, [S] * k) = e^{i phi} T
+ *   cycles  int32[count]       k: 2 iff |z| <= x - y + 2e-8 on the coordinates rounded to 8 digits and folded to c1 <= 1/2
+ *                              (span_rules.minimal_span; what slam_predict_spans says with tol = 2e-8), else 3
+ *   loss    double[count]      1 - |Tr(T^+ template(x_out))| / 4, from a forward pass of the written row
+ *   gap     double[count]      max-norm distance (units of pi) that remains between the chamber points when the interior two-gate
+ *                              circuit is aligned with the class it was built for, as slam_complete_locals' gap_out:
+ *                              loss <= 1 - cos(1.5 pi gap)
+ * Like the reference's pass the function returns 2 or 3 gates only: a local target and a target of S's own class get a valid
+ * two-gate circuit.  Any output pointer may be NULL.  SLAM_ERR_INVALID for a window outside the resident batch.
+ */
+int slam_sqiswap_decompose(slam_ctx* ctx, int64_t first, int64_t count, double* x_out, int32_t* cycles, double* loss, double* gap);
+
+/*
  * Span predictor on the device: for every resident target of [first, first + count) the smallest number k of leading gates of a
  * template whose coverage set contains the target -- the lookup CircuitTemplate.get_spanning_range makes with use_polytopes=True
  * (src/slam/basis.py:95-100 -> monodromy_range_from_target, src/slam/utils/polytopes/polytope_wrap.py:39-94).  The coverage sets
@@ -709,7 +727,8 @@ const char* slam_version(void);
  *      later: slam_hw_queues_requested (a new symbol only);
  *      later: slam_kak, slam_targets_kak and slam_complete_locals (new symbols only);
  *      later: slam_metric_update_check (a new symbol only);
- *      later: slam_haar_select_spans and slam_sample_haar_indexed (new symbols only).
+ *      later: slam_haar_select_spans and slam_sample_haar_indexed (new symbols only);
+ *      later: slam_sqiswap_decompose (a new symbol only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "slam_kak",
     "slam_targets_kak",
     "slam_complete_locals",
+    "slam_sqiswap_decompose",
     "slam_predict_spans",
     "slam_coverage_lookup",
     "slam_eval_c1c2c3",
@@ -226,6 +227,8 @@ def load_library() -> C.CDLL:
         lib.slam_kak.argtypes = [P, P, C.c_int64] + [P] * 6
         lib.slam_targets_kak.argtypes = [P, C.c_int64, C.c_int64] + [P] * 6
         lib.slam_complete_locals.argtypes = [P, C.c_int, P, P, P, C.c_int64, P, P, P]
+    if hasattr(lib, "slam_sqiswap_decompose"):
+        lib.slam_sqiswap_decompose.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P]
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
     if hasattr(lib, "slam_coverage_lookup"):
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
@@ -548,6 +551,20 @@ class Context:
         gap = np.zeros(M)
         _check(self._lib.slam_complete_locals(self._h, k, _ptr(gs), _ptr(x), _ptr(tof), M, _ptr(x_out), _ptr(loss), _ptr(gap)))
         return x_out, loss, gap
+
+    def sqiswap_decompose(self, first: int = 0, count: Optional[int] = None):
+        """Closed-form circuits of two or three sqrt(iSWAP) gates for the resident targets [first, first + count)
+        (slam_sqiswap_decompose; nothing is uploaded, no gate table is needed) -> ``(x [count, 24], cycles [count], loss [count],
+        gap [count])``: row i holds the 6 (cycles[i] + 1) template angles of a circuit that equals target first + i up to a phase,
+        zeros behind; loss is its BasicCost loss, gap the coordinate gap left by the interior formula (units of pi)."""
+        count = self.n_targets - first if count is None else int(count)
+        n = max(count, 0)
+        x = np.zeros((n, 24))
+        cycles = np.zeros(n, dtype=np.int32)
+        loss = np.zeros(n)
+        gap = np.zeros(n)
+        _check(self._lib.slam_sqiswap_decompose(self._h, int(first), count, _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
+        return x, cycles, loss, gap
 
     def metric_update_check(self, h: np.ndarray, s: np.ndarray, w: np.ndarray, v: np.ndarray):
         """Device check of the metric's rank-2 update ``H += s w^T + v s^T`` (slam_metric_update_check): ``h[n, na (na + 1) / 2, 4, 4]``

@@ -1,0 +1,68 @@
+"""Closed-form decomposition into sqrt(iSWAP) gates (reference: ``RootiSwapWeylDecomposition.riswapWeylDecomp``,
+src/slam/utils/transpiler_pass/weyl_decompose.py:343-449, after Huang et al., arXiv:2105.06074).
+
+For ``RiSwapGate(1/2)`` a circuit that equals a two-qubit target is a formula: two gates where |z| <= x - y in the folded Weyl chamber,
+three otherwise -- no optimiser, no restarts, no failures.  The whole pass runs on the GPU, one thread per target
+(``slam_sqiswap_decompose``, csrc/slam_analytic.hpp); there is no CPU path.  Like the reference's pass it returns two or three gates
+only: a local target and a target in sqrt(iSWAP)'s own class get a valid two-gate circuit.
+
+    res = sqiswap_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20))
+    res.cycles, res.Xk, res.loss, res.gap
+    e = res.entries()[0]
+    basis = CircuitTemplate(base_gates=[RiSwapGate(1 / 2)]); basis.build(e.cycles); basis.eval(e.Xk)   # the target, up to a phase
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List
+
+import numpy as np
+
+from . import runtime
+from .basis_abc import DataDictEntry
+
+
+@dataclass
+class SqiswapDecomposition:
+    """``cycles`` int32[N] (2 or 3), ``Xk`` float64[N, 24] (the 6 (cycles + 1) template angles in the front of each row, zeros
+    behind), ``loss`` float64[N] (BasicCost of the circuit against its target), ``gap`` float64[N] (coordinate gap left by the interior
+    formula, units of pi; loss <= 1 - cos(1.5 pi gap))."""
+
+    cycles: np.ndarray
+    Xk: np.ndarray
+    loss: np.ndarray
+    gap: np.ndarray
+    success_threshold: float = 1e-10
+
+    def __len__(self) -> int:
+        return len(self.cycles)
+
+    def entries(self) -> List[DataDictEntry]:
+        """One ``DataDictEntry`` per target, as ``TemplateOptimizer.approximate_from_distribution`` returns them: ``Xk`` is the list
+        of the 6 (cycles + 1) angles of ``CircuitTemplate(base_gates=[RiSwapGate(1/2)]).build(cycles)``."""
+        return [DataDictEntry(int(self.loss[i] <= self.success_threshold), float(self.loss[i]), self.Xk[i, : 6 * (int(k) + 1)].tolist(), int(k))
+                for i, k in enumerate(self.cycles)]
+
+
+def sqiswap_decompose(targets, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:
+    """Circuits of two or three sqrt(iSWAP) gates that equal ``targets``: an ``[N, 4, 4]`` array, a list of 4x4 matrices, any
+    ``SampleFunction``, or a device sampler (``DeviceHaarBatch``, ``DeviceHaarSpanBatch``: anything with ``fill(ctx)``), whose targets
+    are generated on the device and stay there."""
+    ctx = runtime.get_context(device)
+    if hasattr(targets, "fill") and hasattr(targets, "n_samples"):  # a device sampler (an ndarray has a fill of its own)
+        n = int(targets.n_samples)
+        if n > 0:
+            targets.fill(ctx)
+    else:
+        T = np.asarray(targets if isinstance(targets, np.ndarray) else [np.asarray(t) for t in targets], dtype=np.complex128)
+        if T.size == 0:
+            T = T.reshape(0, 4, 4)
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("targets must have shape [N, 4, 4]")
+        n = len(T)
+        if n > 0:
+            ctx.set_targets(T)
+    if n == 0:
+        return SqiswapDecomposition(np.zeros(0, dtype=np.int32), np.zeros((0, 24)), np.zeros(0), np.zeros(0), success_threshold)
+    x, cycles, loss, gap = ctx.sqiswap_decompose(0, n)
+    return SqiswapDecomposition(cycles, x, loss, gap, success_threshold)

@@ -5,6 +5,8 @@ from typing import Dict
 
 from . import _ffi
 
+Context = _ffi.Context  # what get_context returns
+
 _contexts: Dict[tuple, "_ffi.Context"] = {}
 
 

@@ -52,6 +52,7 @@ int main() {
     EXPECT(slam_kak(nullptr, d, 1, d, d, d, d, d, d) == SLAM_ERR_INVALID);
     EXPECT(slam_targets_kak(nullptr, 0, 1, d, d, d, d, d, d) == SLAM_ERR_INVALID);
     EXPECT(slam_complete_locals(nullptr, 1, i32, d, i32, 1, d, d, d) == SLAM_ERR_INVALID);
+    EXPECT(slam_sqiswap_decompose(nullptr, 0, 1, d, i32, d, d) == SLAM_ERR_INVALID);
     EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
