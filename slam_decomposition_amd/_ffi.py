@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "slam_targets_kak",
     "slam_complete_locals",
     "slam_sqiswap_decompose",
+    "slam_cx_decompose",
     "slam_predict_spans",
     "slam_coverage_lookup",
     "slam_eval_c1c2c3",
@@ -229,6 +230,8 @@ def load_library() -> C.CDLL:
         lib.slam_complete_locals.argtypes = [P, C.c_int, P, P, P, C.c_int64, P, P, P]
     if hasattr(lib, "slam_sqiswap_decompose"):
         lib.slam_sqiswap_decompose.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P]
+    if hasattr(lib, "slam_cx_decompose"):
+        lib.slam_cx_decompose.argtypes = [P, C.c_int64, C.c_int64, C.c_int, P, P, P, P, P, P]
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
     if hasattr(lib, "slam_coverage_lookup"):
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
@@ -453,6 +456,51 @@ def _span_half_spaces(gate_coords_seq, k_max: int):
     return point, bounds
 
 
+CX_DRESS = 99  # SLAM_CX_DRESS
+_CX12 = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, 1], [0, 0, 1, 0]], dtype=np.complex128)  # control on the high bit
+_CX21 = np.array([[1, 0, 0, 0], [0, 0, 0, 1], [0, 0, 1, 0], [0, 1, 0, 0]], dtype=np.complex128)
+_SWAP = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], dtype=np.complex128)
+_CX_CLASSES = ((0.5, 0.0, 0.0), (0.5, 0.5, 0.0))
+
+
+def cx_family(gate) -> int:
+    """0 for a 4x4 gate of the CNOT class, 1 for one of the iSWAP class, judged on the 8-digit Weyl coordinates with
+    ``span_rules._TOL``; ``ValueError`` (naming the coordinates) for any other gate."""
+    from . import span_rules, weyl
+
+    c = weyl.c1c2c3(np.asarray(gate, dtype=np.complex128))
+    f = np.abs(span_rules._fold(c)[0])
+    for family, ref in enumerate(_CX_CLASSES):
+        if np.max(np.abs(f - np.array(ref))) < span_rules._TOL:
+            return family
+    raise ValueError(f"the gate is neither of the CNOT class nor of the iSWAP class (Weyl coordinates {tuple(float(v) for v in c)})")
+
+
+def cx_dress(gate):
+    """The host's reduction of a basis gate for slam_cx_decompose (include/slam_hip.h): ``(family, gate [4, 4] complex128,
+    dress float64[CX_DRESS])`` from three ``weyl.kak`` calls -- G = e^{i .} (l1 (x) l0) CAN(c) (r1 (x) r0), and CX12, CX21 written
+    through D = CAN(class point) (family 0) or SWAP CAN(class point) (family 1), a gate of the CNOT class in both."""
+    from . import weyl
+    from .gates import canonical_matrix
+
+    g = np.ascontiguousarray(gate, dtype=np.complex128)
+    if g.shape != (4, 4):
+        raise ValueError("the basis gate must be a 4x4 matrix")
+    family = cx_family(g)
+    _, l1, l0, c, r1, r0 = weyl.kak(g)
+    D = canonical_matrix(*_CX_CLASSES[family])
+    if family:
+        D = _SWAP @ D
+    _, u1, u0, _, v1, v0 = weyl.kak(D)  # D = e^{i .} (u1 (x) u0) CAN(1/2, 0, 0) (v1 (x) v0)
+    factors = [l1, l0, r1, r0]
+    for cx in (_CX12, _CX21):
+        _, a1, a0, _, b1, b0 = weyl.kak(cx)
+        factors += [a1 @ u1.conj().T, a0 @ u0.conj().T, v1.conj().T @ b1, v0.conj().T @ b0]
+    dress = np.concatenate([np.ascontiguousarray(np.stack(factors), dtype=np.complex128).view(np.float64).ravel(), np.asarray(c, dtype=np.float64)])
+    assert dress.shape == (CX_DRESS,)
+    return family, g, dress
+
+
 class Context:
     """One GPU: resident targets + gate table + work buffers (``slam_ctx``)."""
 
@@ -564,6 +612,22 @@ class Context:
         loss = np.zeros(n)
         gap = np.zeros(n)
         _check(self._lib.slam_sqiswap_decompose(self._h, int(first), count, _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
+        return x, cycles, loss, gap
+
+    def cx_decompose(self, gate, first: int = 0, count: Optional[int] = None):
+        """Closed-form circuits of one, two or three gates ``gate`` -- a 4x4 matrix of the CNOT class or of the iSWAP class -- for the
+        resident targets [first, first + count) (slam_cx_decompose; nothing is uploaded, no gate table is needed) -> ``(x [count, 24],
+        cycles [count], loss [count], gap [count])``: row i holds the 6 (cycles[i] + 1) template angles of a circuit of ``gate`` that
+        equals target first + i up to a phase, zeros behind; loss is its BasicCost loss, gap the coordinate gap left by the alignment
+        of the interior circuit (units of pi).  ``ValueError`` for a gate outside both classes (``span_rules._TOL``)."""
+        family, g, dress = cx_dress(gate)
+        count = self.n_targets - first if count is None else int(count)
+        n = max(count, 0)
+        x = np.zeros((n, 24))
+        cycles = np.zeros(n, dtype=np.int32)
+        loss = np.zeros(n)
+        gap = np.zeros(n)
+        _check(self._lib.slam_cx_decompose(self._h, int(first), count, family, _ptr(g), _ptr(dress), _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
         return x, cycles, loss, gap
 
     def metric_update_check(self, h: np.ndarray, s: np.ndarray, w: np.ndarray, v: np.ndarray):

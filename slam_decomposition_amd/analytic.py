@@ -1,4 +1,9 @@
-"""Closed-form decomposition into sqrt(iSWAP) gates (reference: ``RootiSwapWeylDecomposition.riswapWeylDecomp``,
+"""Closed-form decompositions: circuits that equal their two-qubit targets from a formula -- no optimiser, no restarts, no failures.
+``decompose`` dispatches on the basis gate as the reference's ``RootiSwapWeylDecomposition.run`` does
+(src/slam/utils/transpiler_pass/weyl_decompose.py:475-480): ``RiSwapGate(1/2)`` to ``sqiswap_decompose``, a gate of the CNOT class or of
+the iSWAP class (the reference's ``TwoQubitBasisDecomposer`` branch, what ``pass_manager_basic(gate="cx")`` runs) to ``cx_decompose``.
+
+sqrt(iSWAP) gates (reference: ``RootiSwapWeylDecomposition.riswapWeylDecomp``,
 src/slam/utils/transpiler_pass/weyl_decompose.py:343-449, after Huang et al., arXiv:2105.06074).
 
 For ``RiSwapGate(1/2)`` a circuit that equals a two-qubit target is a formula: two gates where |z| <= x - y in the folded Weyl chamber,
@@ -10,6 +15,13 @@ only: a local target and a target in sqrt(iSWAP)'s own class get a valid two-gat
     res.cycles, res.Xk, res.loss, res.gap
     e = res.entries()[0]
     basis = CircuitTemplate(base_gates=[RiSwapGate(1 / 2)]); basis.build(e.cycles); basis.eval(e.Xk)   # the target, up to a phase
+
+Gates of the CNOT class (CX, CZ, ...) and of the iSWAP class: one gate for a target of the gate's own class, two where c3 = 0, three
+otherwise (``span_rules.minimal_span``; a local target gets two), with interior angles that are linear in the target's KAK coordinates
+(Vatan and Williams, quant-ph/0308006; ``slam_cx_decompose``, csrc/slam_cx.hpp):
+
+    res = cx_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20), CXGate())
+    basis = CircuitTemplate(base_gates=[CXGate()]); basis.build(e.cycles); basis.eval(e.Xk)            # likewise
 """
 from __future__ import annotations
 
@@ -20,6 +32,7 @@ import numpy as np
 
 from . import runtime
 from .basis_abc import DataDictEntry
+from .gates import CXGate, gate_matrix
 
 
 @dataclass
@@ -44,11 +57,16 @@ class SqiswapDecomposition:
                 for i, k in enumerate(self.cycles)]
 
 
-def sqiswap_decompose(targets, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:
-    """Circuits of two or three sqrt(iSWAP) gates that equal ``targets``: an ``[N, 4, 4]`` array, a list of 4x4 matrices, any
-    ``SampleFunction``, or a device sampler (``DeviceHaarBatch``, ``DeviceHaarSpanBatch``: anything with ``fill(ctx)``), whose targets
-    are generated on the device and stay there."""
-    ctx = runtime.get_context(device)
+@dataclass
+class CxDecomposition(SqiswapDecomposition):
+    """The same fields for circuits of ``basis_gate`` (``cycles`` 1, 2 or 3; ``gap`` is the coordinate gap left by the alignment of the
+    interior circuit): ``entries()`` rows are those of ``CircuitTemplate(base_gates=[basis_gate]).build(cycles)``."""
+
+    basis_gate: object = None
+
+
+def _resident(ctx, targets) -> int:
+    """Makes ``targets`` the resident batch of ``ctx``; their number."""
     if hasattr(targets, "fill") and hasattr(targets, "n_samples"):  # a device sampler (an ndarray has a fill of its own)
         n = int(targets.n_samples)
         if n > 0:
@@ -62,7 +80,52 @@ def sqiswap_decompose(targets, device: int = 0, success_threshold: float = 1e-10
         n = len(T)
         if n > 0:
             ctx.set_targets(T)
+    return n
+
+
+def sqiswap_decompose(targets, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:
+    """Circuits of two or three sqrt(iSWAP) gates that equal ``targets``: an ``[N, 4, 4]`` array, a list of 4x4 matrices, any
+    ``SampleFunction``, or a device sampler (``DeviceHaarBatch``, ``DeviceHaarSpanBatch``: anything with ``fill(ctx)``), whose targets
+    are generated on the device and stay there."""
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
     if n == 0:
         return SqiswapDecomposition(np.zeros(0, dtype=np.int32), np.zeros((0, 24)), np.zeros(0), np.zeros(0), success_threshold)
     x, cycles, loss, gap = ctx.sqiswap_decompose(0, n)
     return SqiswapDecomposition(cycles, x, loss, gap, success_threshold)
+
+
+def cx_decompose(targets, basis_gate=None, device: int = 0, success_threshold: float = 1e-10) -> CxDecomposition:
+    """Circuits of one, two or three gates ``basis_gate`` (default ``CXGate()``; any gate object or 4x4 matrix of the CNOT class or of
+    the iSWAP class: ``CZGate``, ``iSwapGate``, a ``CanonicalGate``, ``UnitaryGate`` or ``ConversionGainGate`` at those points) that
+    equal ``targets``, which are given as for ``sqiswap_decompose``.  ``ValueError`` for a gate outside both classes."""
+    from . import _ffi
+
+    basis_gate = CXGate() if basis_gate is None else basis_gate
+    g = gate_matrix(basis_gate)
+    _ffi.cx_family(g)  # before any context is made
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
+    if n == 0:
+        return CxDecomposition(np.zeros(0, dtype=np.int32), np.zeros((0, 24)), np.zeros(0), np.zeros(0), success_threshold, basis_gate)
+    x, cycles, loss, gap = ctx.cx_decompose(g, 0, n)
+    return CxDecomposition(cycles, x, loss, gap, success_threshold, basis_gate)
+
+
+def decompose(targets, basis_gate, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:
+    """The closed-form decomposition that exists for ``basis_gate``, chosen as the reference's pass chooses it: ``RiSwapGate(1/2)`` (any
+    gate whose matrix is that gate's) goes to ``sqiswap_decompose``, a gate of the CNOT class or of the iSWAP class to
+    ``cx_decompose``; ``NotImplementedError`` naming the gate's Weyl coordinates for anything else."""
+    from . import _ffi, weyl
+    from .gates import RiSwapGate
+
+    g = gate_matrix(basis_gate)
+    if np.max(np.abs(g - gate_matrix(RiSwapGate(1 / 2)))) <= 1e-12:
+        return sqiswap_decompose(targets, device, success_threshold)
+    try:
+        _ffi.cx_family(g)
+    except ValueError:
+        raise NotImplementedError(
+            "closed-form decompositions exist for RiSwapGate(1/2) and for basis gates of the CNOT class (0.5, 0, 0) and of the iSWAP "
+            f"class (0.5, 0.5, 0) only (got {basis_gate} with Weyl coordinates {tuple(float(v) for v in weyl.c1c2c3(g))})") from None
+    return cx_decompose(targets, basis_gate, device, success_threshold)

@@ -1,6 +1,8 @@
-// slam_analytic.hip -- host side of libslamhip.so, analytic unit: the closed-form decomposition into sqrt(iSWAP) gates
-// (slam_analytic.hpp).
+// slam_analytic.hip -- host side of libslamhip.so, analytic unit: the closed-form decompositions into sqrt(iSWAP) gates
+// (slam_analytic.hpp) and into gates of the CNOT or the iSWAP class (slam_cx.hpp).
 #include "slam_host.hpp"
+
+#include <complex>
 
 // slam_kak.hpp and the headers under it define their __global__ kernels where they are included, and slam_geometry.hip is the unit that
 // emits them (slam_host.hpp).  This unit calls their __device__ functions only: here those kernels are read as function templates
@@ -11,8 +13,181 @@
 #include "slam_kak.hpp"
 #pragma pop_macro("__global__")
 #include "slam_analytic.hpp"
+#include "slam_cx.hpp"
+
+// ---- slam_cx_decompose: the host's share (plain C++) -------------------------------------------------------------------
+namespace {
+
+using cd = std::complex<double>;
+struct M2 { cd m[2][2]; };
+struct M4 { cd m[4][4]; };
+
+M2 load2(const double* p) { return {{{cd(p[0], p[1]), cd(p[2], p[3])}, {cd(p[4], p[5]), cd(p[6], p[7])}}}; }
+M2 mul(const M2& a, const M2& b) {
+    M2 z;
+    for (int r = 0; r < 2; ++r)
+        for (int c = 0; c < 2; ++c) z.m[r][c] = a.m[r][0] * b.m[0][c] + a.m[r][1] * b.m[1][c];
+    return z;
+}
+M2 dag(const M2& a) { return {{{std::conj(a.m[0][0]), std::conj(a.m[1][0])}, {std::conj(a.m[0][1]), std::conj(a.m[1][1])}}}; }
+M4 kron(const M2& a, const M2& b) {  // a on the high bit
+    M4 z;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) z.m[i][j] = a.m[i >> 1][j >> 1] * b.m[i & 1][j & 1];
+    return z;
+}
+M4 mul(const M4& a, const M4& b) {
+    M4 z;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            cd s = 0.0;
+            for (int k = 0; k < 4; ++k) s += a.m[r][k] * b.m[k][c];
+            z.m[r][c] = s;
+        }
+    return z;
+}
+// CAN(c): (c1 - c2) sigma_x on span(00, 11) with phase pi/2 c3, (c1 + c2) sigma_x on span(01, 10) with phase -pi/2 c3
+M4 can(const double* c) {
+    const double hp = 1.57079632679489661923;
+    M4 z{};
+    const cd e = std::polar(1.0, hp * c[2]), ec = std::conj(e), i1(0.0, 1.0);
+    const double am = hp * (c[0] - c[1]), ap = hp * (c[0] + c[1]);
+    z.m[0][0] = z.m[3][3] = e * std::cos(am);
+    z.m[0][3] = z.m[3][0] = e * i1 * std::sin(am);
+    z.m[1][1] = z.m[2][2] = ec * std::cos(ap);
+    z.m[1][2] = z.m[2][1] = ec * i1 * std::sin(ap);
+    return z;
+}
+M4 swap_rows(const M4& a) {  // SWAP a
+    M4 z = a;
+    for (int c = 0; c < 4; ++c) std::swap(z.m[1][c], z.m[2][c]);
+    return z;
+}
+// max |want - e^{i g} got| with the phase that brings them closest; +inf for anything not finite
+double phase_distance(const M4& want, const M4& got) {
+    cd tr = 0.0;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) tr += std::conj(got.m[r][c]) * want.m[r][c];
+    const double n = std::abs(tr);
+    if (!(n > 0.0) || !std::isfinite(n)) return INFINITY;
+    const cd ph = tr / n;
+    double worst = 0.0;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            const double d = std::abs(want.m[r][c] - ph * got.m[r][c]);
+            if (!(d <= worst)) worst = d;  // a NaN sticks
+        }
+    return worst;
+}
+void put_entry(double* e, const M2& L, const M2& R, int axis, int src) {
+    for (int r = 0; r < 2; ++r)
+        for (int c = 0; c < 2; ++c) {
+            e[2 * (2 * r + c)] = L.m[r][c].real();
+            e[2 * (2 * r + c) + 1] = L.m[r][c].imag();
+            e[8 + 2 * (2 * r + c)] = R.m[r][c].real();
+            e[8 + 2 * (2 * r + c) + 1] = R.m[r][c].imag();
+        }
+    e[16] = axis;
+    e[17] = src;
+}
+
+// Checks gate against dress and folds dress into the kernel's table (slam_cx.hpp).  dress: the twelve 2x2 factors l1, l0, r1, r0,
+// a12_1, a12_0, b12_1, b12_0, a21_1, a21_0, b21_1, b21_0 (row-major re, im), then the gate's KAK coordinates c[3].
+int cx_fold_dress(int family, const double* gate, const double* dress, double* table) {
+    M2 f[12];
+    for (int j = 0; j < 12; ++j) f[j] = load2(dress + 8 * j);
+    const double* c = dress + 96;
+    const double own[3] = {0.5, family ? 0.5 : 0.0, 0.0};
+    double fc[3] = {c[0], c[1], c[2]};
+    if (fc[0] > 0.5) {
+        fc[0] = 1.0 - fc[0];
+        fc[2] = -fc[2];
+    }
+    for (int j = 0; j < 3; ++j)
+        if (!(std::fabs(std::fabs(fc[j]) - own[j]) < 4e-8))
+            return fail(SLAM_ERR_INVALID, "the dress coordinates (%g, %g, %g) are not those of family %d", c[0], c[1], c[2], family);
+    M4 G;
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) G.m[r][k] = cd(gate[2 * (4 * r + k)], gate[2 * (4 * r + k) + 1]);
+    const double tol = 1e-12;
+    double d = phase_distance(G, mul(mul(kron(f[0], f[1]), can(c)), kron(f[2], f[3])));
+    if (!(d <= tol)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild the gate (max deviation %g)", d);
+    // D = C or SWAP C with the class point itself; CX12 and CX21 through it
+    const M4 C = can(own), D = family ? swap_rows(C) : C;
+    M4 cx12{}, cx21{};
+    cx12.m[0][0] = cx12.m[1][1] = cx12.m[2][3] = cx12.m[3][2] = 1.0;
+    cx21.m[0][0] = cx21.m[2][2] = cx21.m[1][3] = cx21.m[3][1] = 1.0;
+    d = phase_distance(cx12, mul(mul(kron(f[4], f[5]), D), kron(f[6], f[7])));
+    if (!(d <= tol)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild CX12 (max deviation %g)", d);
+    d = phase_distance(cx21, mul(mul(kron(f[8], f[9]), D), kron(f[10], f[11])));
+    if (!(d <= tol)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild CX21 (max deviation %g)", d);
+    for (int j = 0; j < 32; ++j) table[j] = gate[j];
+    // an interior layer K of the D-circuit, qubits (K1, K0): family 1 exchanges the qubits of the first interior layer; then r^+ on the
+    // left, l^+ on the right.  Entry order: [slot][qubit 0, qubit 1].
+    const M2 l1d = dag(f[0]), l0d = dag(f[1]), r1d = dag(f[2]), r0d = dag(f[3]);
+    const M2 &a12_1 = f[4], &a12_0 = f[5], &b12_1 = f[6], &b12_0 = f[7], &a21_1 = f[8], &a21_0 = f[9], &b21_1 = f[10], &b21_0 = f[11];
+    double* e = table + 32;
+    const int AX = 1, AY = 2, AZ = 3;
+    if (!family) {
+        // two gates: b12 (RX(a) (x) RZ(b)) a12
+        put_entry(e + 0, mul(r0d, b12_0), mul(a12_0, l0d), AZ, 1);
+        put_entry(e + 18, mul(r1d, b12_1), mul(a12_1, l1d), AX, 0);
+        // three gates, first layer: b12 (RZ(t1) (x) RY(t2)) a21
+        put_entry(e + 36, mul(r0d, b12_0), mul(a21_0, l0d), AY, 1);
+        put_entry(e + 54, mul(r1d, b12_1), mul(a21_1, l1d), AZ, 0);
+    } else {
+        put_entry(e + 0, mul(r0d, b12_1), mul(a12_1, l0d), AX, 0);
+        put_entry(e + 18, mul(r1d, b12_0), mul(a12_0, l1d), AZ, 1);
+        put_entry(e + 36, mul(r0d, b12_1), mul(a21_1, l0d), AZ, 0);
+        put_entry(e + 54, mul(r1d, b12_0), mul(a21_0, l1d), AY, 1);
+    }
+    // three gates, second layer: b21 (1 (x) RY(t3)) a12
+    put_entry(e + 72, mul(r0d, b21_0), mul(a12_0, l0d), AY, 2);
+    put_entry(e + 90, mul(r1d, b21_1), mul(a12_1, l1d), 0, 0);
+    return SLAM_OK;
+}
+
+}  // namespace
 
 extern "C" {
+
+int slam_cx_decompose(slam_ctx* ctx, int64_t first, int64_t count, int family, const double* gate, const double* dress, double* x_out,
+                      int32_t* cycles, double* loss, double* gap) {
+    // what needs no context first: the host's share runs, and is checked, on a machine without a device too
+    if (family != 0 && family != 1) return fail(SLAM_ERR_INVALID, "family must be 0 (CNOT class) or 1 (iSWAP class), got %d", family);
+    if (!gate || !dress) return fail(SLAM_ERR_INVALID, "gate and dress are required");
+    double table[kCxTable];
+    const int rc = cx_fold_dress(family, gate, dress, table);
+    if (rc) return rc;
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_grad.reserve((size_t)count * 24 * sizeof(double)));  // the rows
+    HIP_TRY(ctx->ev_loss.reserve((size_t)count * 2 * sizeof(double)));   // losses, then gaps
+    HIP_TRY(ctx->ev_tof.reserve((size_t)count * sizeof(int32_t)));       // sizes
+    HIP_TRY(ctx->ev_x.reserve(sizeof(table)));                           // the gate and the interior table
+    HIP_TRY(hipMemcpy(ctx->ev_x.p, table, sizeof(table), hipMemcpyHostToDevice));  // from the stack: done before the call goes on
+    CxArgs a{};
+    a.targets = ctx->targets.as<double>() + first * 32;
+    a.table = ctx->ev_x.as<double>();
+    a.M = count;
+    a.family = family;
+    a.x_out = ctx->ev_grad.as<double>();
+    a.cycles = ctx->ev_tof.as<int32_t>();
+    a.loss = ctx->ev_loss.as<double>();
+    a.gap = ctx->ev_loss.as<double>() + count;
+    hipLaunchKernelGGL(cx_decompose_kernel, dim3((unsigned)((count + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (x_out) HIP_TRY(hipMemcpyAsync(x_out, a.x_out, (size_t)count * 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (cycles) HIP_TRY(hipMemcpyAsync(cycles, a.cycles, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (loss) HIP_TRY(hipMemcpyAsync(loss, a.loss, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (gap) HIP_TRY(hipMemcpyAsync(gap, a.gap, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
 
 int slam_sqiswap_decompose(slam_ctx* ctx, int64_t first, int64_t count, double* x_out, int32_t* cycles, double* loss, double* gap) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");

@@ -1,0 +1,251 @@
+"""Test-side restatement of the closed-form decomposition into one, two or three gates of the CNOT or the iSWAP class
+(``slam_cx_decompose``, csrc/slam_cx.hpp), in NumPy.  Nothing is shared with csrc/; the alignments use
+``slam_decomposition_amd.weyl.kak``.
+
+Conventions: kron(a, b) puts a on the high bit; CAN(c) = exp(i pi/2 (c1 XX + c2 YY + c3 ZZ)); RP(t) = exp(-i t P / 2);
+CX12 = |0><0| (x) 1 + |1><1| (x) X (control on the high bit), CX21 = 1 (x) |0><0| + X (x) |1><1| (the package's ``CXGate``).  A template
+row holds six angles per layer: U3(theta, phi, lam) of qubit 0 (the low bit), then of qubit 1.
+
+Circuits with fixed gates and linear angles (Vatan and Williams, quant-ph/0308006):
+
+    V3(t)    = CX21 (1 (x) RY(t3)) CX12 (RZ(t1) (x) RY(t2)) CX21    ~  CAN(1/2 + t1/pi, 1/2 + t2/pi, 1/2 + t3/pi)    for every real t,
+    V2(a, b) = CX12 (RX(a) (x) RZ(b)) CX12                          ~  CAN(a/pi, b/pi, 0),
+
+so a target with KAK coordinates c takes t_j = pi (c_j - 1/2), or a = pi c1, b = pi c2 where c3 = 0; a target of the gate's own class
+takes the gate itself.  The exterior layers come from aligning the interior circuit with the target (``align``).
+
+Any basis gate G of the CNOT class: CX12 ~ A G B and CX21 ~ A' G B' by aligning G with them; the fixed local factors go into the
+neighbouring layers.  A gate G of the iSWAP class: D = SWAP G is of the CNOT class; the circuit is built from D-gates -- for SWAP T where
+the number of gates is odd, for T where it is even -- and the SWAPs are taken out again: with sw(K) = SWAP K SWAP (the two qubits of K
+exchanged) and sw(G) ~ M G N (one class, aligned once),
+
+    k = 3:  SWAP T = K3 D K2 D K1 D K0   ->   T = sw(K3) G (K2 M) G (N sw(K1)) G K0
+    k = 2:       T = K2 D K1 D K0        ->   T = K2 M G (N sw(K1)) G K0
+    k = 1:  SWAP T = K1 D K0             ->   T = sw(K1) G K0.
+
+``conditioning`` is not needed: the angles are linear in the coordinates, nothing here is ill conditioned (tests/test_cx_analytic_host.py
+holds every Haar target to the matrix-level bound).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from slam_decomposition_amd import weyl
+
+_I = np.eye(2, dtype=np.complex128)
+_X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
+_Y = np.array([[0, -1j], [1j, 0]], dtype=np.complex128)
+_Z = np.array([[1, 0], [0, -1]], dtype=np.complex128)
+_PP = [np.kron(p, p) for p in (_X, _Y, _Z)]
+_P0 = np.diag([1.0, 0.0]).astype(np.complex128)
+_P1 = np.diag([0.0, 1.0]).astype(np.complex128)
+CX12 = np.kron(_P0, _I) + np.kron(_P1, _X)
+CX21 = np.kron(_I, _P0) + np.kron(_X, _P1)
+CZ = np.diag([1, 1, 1, -1]).astype(np.complex128)
+SWAP = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], dtype=np.complex128)
+ISWAP = np.array([[1, 0, 0, 0], [0, 0, 1j, 0], [0, 1j, 0, 0], [0, 0, 0, 1]], dtype=np.complex128)
+SQISWAP = np.array([[1, 0, 0, 0], [0, np.sqrt(0.5), 1j * np.sqrt(0.5), 0], [0, 1j * np.sqrt(0.5), np.sqrt(0.5), 0], [0, 0, 0, 1]], dtype=np.complex128)
+SIZE_TOL = 2e-8  # span_rules._TOL: the size rule is evaluated on coordinates rounded to 8 digits
+CLASSES = ((0.5, 0.0, 0.0), (0.5, 0.5, 0.0))  # family 0: CNOT, family 1: iSWAP
+
+
+def rot(p, t) -> np.ndarray:
+    return np.cos(0.5 * t) * _I - 1j * np.sin(0.5 * t) * p
+
+
+def can(c) -> np.ndarray:
+    out = np.eye(4, dtype=np.complex128)
+    for j in range(3):
+        a = 0.5 * np.pi * c[j]
+        out = out @ (np.cos(a) * np.eye(4) + 1j * np.sin(a) * _PP[j])
+    return out
+
+
+def V3(t) -> np.ndarray:
+    return CX21 @ np.kron(_I, rot(_Y, t[2])) @ CX12 @ np.kron(rot(_Z, t[0]), rot(_Y, t[1])) @ CX21
+
+
+def V2(a, b) -> np.ndarray:
+    return CX12 @ np.kron(rot(_X, a), rot(_Z, b)) @ CX12
+
+
+def sw(K) -> np.ndarray:
+    return SWAP @ K @ SWAP
+
+
+def u3(t, p, l) -> np.ndarray:
+    c, s = np.cos(0.5 * t), np.sin(0.5 * t)
+    return np.array([[c, -np.exp(1j * l) * s], [np.exp(1j * p) * s, np.exp(1j * (p + l)) * c]])
+
+
+def u3_angles(m):
+    """(theta, phi, lam) with m = e^{i g} U3(theta, phi, lam)."""
+    c, s = abs(m[0, 0]), abs(m[1, 0])
+    g = np.angle(m[0, 0]) if c > 0 else 0.0
+    phi = (np.angle(m[1, 0]) if s > 0 else 0.0) - g
+    lam = np.angle(m[1, 1]) - g - phi if c >= s else np.angle(-m[0, 1]) - g
+    return 2.0 * np.arctan2(s, c), phi, lam
+
+
+def template(x, G, k) -> np.ndarray:
+    """K_k G K_{k-1} ... G K_0 of a row of 6 (k + 1) angles, K = U3(qubit 1) (x) U3(qubit 0)."""
+    x = np.asarray(x, dtype=np.float64)
+    W = np.eye(4, dtype=np.complex128)
+    for j in range(k + 1):
+        if j:
+            W = G @ W
+        p = x[6 * j:6 * j + 6]
+        W = np.kron(u3(*p[3:6]), u3(*p[0:3])) @ W
+    return W
+
+
+def fold_chamber(c) -> np.ndarray:
+    """(c1, c2, c3) with c3 >= 0 (as c1c2c3 returns them) -> c1 <= 1/2, c3 of either sign."""
+    c = np.array(c, dtype=np.float64, copy=True)
+    m = c[..., 0] > 0.5
+    c[..., 0] = np.where(m, 1.0 - c[..., 0], c[..., 0])
+    c[..., 2] = np.where(m, -c[..., 2], c[..., 2])
+    return c
+
+
+def family_of(G) -> int:
+    """0 for a gate of the CNOT class, 1 for one of the iSWAP class (8-digit coordinates, SIZE_TOL)."""
+    f = np.abs(fold_chamber(np.array(weyl.c1c2c3(G))))
+    for fam, ref in enumerate(CLASSES):
+        if np.max(np.abs(f - np.array(ref))) < SIZE_TOL:
+            return fam
+    raise ValueError("the gate is in neither class")
+
+
+def size(c8, family) -> np.ndarray:
+    """1, 2 or 3 from coordinates rounded to 8 digits: span_rules.minimal_span for the family, never below 1 -- and a local target
+    takes two gates (one gate cannot be local)."""
+    f = fold_chamber(c8)
+    same = np.max(np.abs(np.abs(f) - np.array(CLASSES[family])), axis=-1) < SIZE_TOL
+    return np.where(same, 1, np.where(np.abs(f[..., 2]) < SIZE_TOL, 2, 3))
+
+
+def expected_size(T, family) -> np.ndarray:
+    """Per matrix of T[N, 4, 4]: span_rules.minimal_span on the 8-digit coordinates, local targets at two gates."""
+    from slam_decomposition_amd import span_rules
+
+    k = span_rules.minimal_span(weyl.c1c2c3_batch(np.asarray(T)), CLASSES[family])
+    return np.where(k == 0, 2, k)
+
+
+def align(W, T):
+    """(L, R, gap): 4x4 local gates with T ~ L W R up to a phase for W, T of (nearly) one class: KAK of both, W's mirrored where that
+    brings its chamber point closer to T's."""
+    kw, kt = weyl.kak(W), weyl.kak(T)
+    cw, ct = np.asarray(kw[3]), np.asarray(kt[3])
+    d0 = np.max(np.abs(cw - ct))
+    d1 = np.max(np.abs(np.array([1 - cw[0], cw[1], -cw[2]]) - ct))
+    if d1 < d0:
+        kw = weyl.mirror_kak(*kw)
+    L = np.kron(kt[1] @ kw[1].conj().T, kt[2] @ kw[2].conj().T)
+    R = np.kron(kw[4].conj().T @ kt[4], kw[5].conj().T @ kt[5])
+    return L, R, float(min(d0, d1))
+
+
+def split(K):
+    """(q1, q0) with K ~ kron(q1, q0) for a local 4x4 K."""
+    return weyl._split_local(K)
+
+
+def _layer(K):
+    q1, q0 = split(K)
+    return list(u3_angles(q0)) + list(u3_angles(q1))
+
+
+_GATE_CACHE = {}
+
+
+def gate_factors(G):
+    """What depends on the basis gate alone: (family, D, (A12, B12), (A21, B21), (M, N)) with CX12 ~ A12 D B12, CX21 ~ A21 D B21 and,
+    for the iSWAP class, sw(G) ~ M G N."""
+    key = np.asarray(G, dtype=np.complex128).tobytes()
+    if key not in _GATE_CACHE:
+        fam = family_of(G)
+        D = SWAP @ G if fam else G
+        A12, B12, g12 = align(D, CX12)
+        A21, B21, g21 = align(D, CX21)
+        M, N, gs = align(G, sw(G)) if fam else (None, None, 0.0)
+        assert max(g12, g21, gs) < 4 * SIZE_TOL
+        _GATE_CACHE[key] = (fam, D, (A12, B12), (A21, B21), (M, N))
+    return _GATE_CACHE[key]
+
+
+def decompose(T, G):
+    """(k, x, W, gap): the 6 (k + 1) angles of a circuit of k gates G for the 4x4 unitary T, its unitary W = template(x, G, k) and the
+    chamber distance left by the alignment of the interior circuit."""
+    T = np.asarray(T, dtype=np.complex128)
+    G = np.asarray(G, dtype=np.complex128)
+    fam, D, (A12, B12), (A21, B21), (M, N) = gate_factors(G)
+    c = np.asarray(weyl.kak(T)[3])
+    k = int(size(np.round(c, 8), fam))
+    Tt = T
+    if fam and k % 2:
+        Tt = SWAP @ T
+        c = np.asarray(weyl.kak(Tt)[3])  # the D-circuit is built for Tt
+    # interior circuit in D-gates: layers K_1 .. K_{k-1} between them (the exterior ones are the alignment's)
+    if k == 3:
+        t = np.pi * (c - 0.5)
+        inner = [B12 @ np.kron(rot(_Z, t[0]), rot(_Y, t[1])) @ A21, B21 @ np.kron(_I, rot(_Y, t[2])) @ A12]
+    elif k == 2:
+        inner = [B12 @ np.kron(rot(_X, np.pi * c[0]), rot(_Z, np.pi * c[1])) @ A12]
+    else:
+        inner = []
+    V = D
+    for K in inner:
+        V = D @ K @ V
+    L, R, gap = align(V, Tt)
+    Ks = [R] + inner + [L]
+    if fam:
+        if k == 3:
+            Ks = [Ks[0], N @ sw(Ks[1]), Ks[2] @ M, sw(Ks[3])]
+        elif k == 2:
+            Ks = [Ks[0], N @ sw(Ks[1]), Ks[2] @ M]
+        else:
+            Ks = [Ks[0], sw(Ks[1])]
+    x = np.array([a for K in Ks for a in _layer(K)])
+    return k, x, template(x, G, k), gap
+
+
+def loss(T, W) -> float:
+    return float(1.0 - abs(np.trace(np.conj(T).T @ W)) / 4.0)
+
+
+def up_to_phase(T, W) -> float:
+    tr = np.trace(np.conj(W).T @ T)
+    return float(np.max(np.abs(T - tr / abs(tr) * W)))
+
+
+def dress(rng, W, n=None):
+    """e^{i phi} (L1 (x) L2) W (R1 (x) R2) with random SU(2) factors and phases: n matrices (or one)."""
+    import kak_ref as kr
+
+    m = 1 if n is None else n
+    ph = np.exp(1j * rng.uniform(0, 2 * np.pi, m))[:, None, None]
+    out = ph * (kr.kron2(kr.random_su2(rng, m), kr.random_su2(rng, m)) @ W @ kr.kron2(kr.random_su2(rng, m), kr.random_su2(rng, m)))
+    return out[0] if n is None else out
+
+
+def _named():
+    out = [("identity", np.eye(4, dtype=np.complex128)), ("CX", CX21), ("CZ", CZ), ("iSWAP", ISWAP), ("SWAP", SWAP),
+           ("B", can((0.5, 0.25, 0.0))), ("sqrt(iSWAP)", SQISWAP)]
+    for c in ((0.3, 0.2, 0.0), (0.3, 0.2, 1e-9), (0.3, 0.2, 1e-6), (1e-9, 0.0, 0.0), (0.5, 0.5, 0.5 - 1e-9), (0.7, 0.2, 0.1), (0.3, 0.2, 2e-8)):
+        out.append(("CAN(%g, %g, %.10g)" % c, can(c)))
+    return out
+
+
+# the named and hard inputs: (name, gate).  "CAN(0.7, 0.2, 0.1)" is the mirror-side point; "CAN(0.3, 0.2, 2e-08)" lies on the size
+# rule's tolerance, where either size is right
+NAMED = _named()
+ON_BOUNDARY = ("CAN(0.3, 0.2, 2e-08)",)
+TWO_GATES = ("CAN(0.3, 0.2, 0)", "CAN(0.3, 0.2, 1e-09)", "CAN(1e-09, 0, 0)")
+THREE_GATES = ("CAN(0.3, 0.2, 1e-06)",)
+
+
+def basis_gates(rng):
+    """(name, matrix) of the basis gates the tests run: CX, CZ, iSWAP and a randomly dressed member of each class."""
+    return [("CX", CX21), ("CZ", CZ), ("iSWAP", ISWAP), ("dressed CX", dress(rng, CX12)), ("dressed iSWAP", dress(rng, ISWAP))]

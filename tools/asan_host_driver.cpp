@@ -54,6 +54,53 @@ int main() {
     EXPECT(slam_complete_locals(nullptr, 1, i32, d, i32, 1, d, d, d) == SLAM_ERR_INVALID);
     EXPECT(slam_sqiswap_decompose(nullptr, 0, 1, d, i32, d, d) == SLAM_ERR_INVALID);
     EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+    {  // slam_cx_decompose checks its gate and folds the host's factors before it needs a context: CXGate and its reduction as
+       // Context.cx_decompose computes it (_ffi.cx_dress), so the whole of the host's share runs here
+    const double cx_gate[32] = {
+        1.0, 0.0, 0.0, 0.0, 0.0, 0.0,
+        0.0, 0.0, 0.0, 0.0, 0.0, 0.0,
+        0.0, 0.0, 1.0, 0.0, 0.0, 0.0,
+        0.0, 0.0, 1.0, 0.0, 0.0, 0.0,
+        0.0, 0.0, 1.0, 0.0, 0.0, 0.0,
+        0.0, 0.0};
+    const double cx_dress[99] = {
+        5.5511151231257815e-17, -0.7071067811865476, 0.7071067811865476, -5.5511151231257815e-17, -0.7071067811865476, -5.5511151231257815e-17,
+        5.5511151231257815e-17, 0.7071067811865476, 0.5, -0.5, -0.5, 0.5,
+        0.5, 0.5, 0.5, 0.5, 6.312253112239643e-33, -1.0,
+        0.0, 0.0, 0.0, 0.0, 6.312253112239643e-33, 1.0,
+        -0.7071067811865476, -1.848816132009102e-33, -0.7071067811865476, -1.848816132009102e-33, 0.7071067811865476, -1.848816132009102e-33,
+        -0.7071067811865476, 1.848816132009102e-33, -0.6532814824381884, 0.27059805007309845, -0.6532814824381883, 0.2705980500730985,
+        0.6532814824381883, 0.2705980500730985, -0.6532814824381884, -0.27059805007309845, -0.9238795325112868, 0.0,
+        0.0, -0.3826834323650897, 0.0, -0.3826834323650897, -0.9238795325112868, 0.0,
+        0.6532814824381883, -0.27059805007309856, -0.6532814824381883, -0.27059805007309856, 0.6532814824381883, -0.27059805007309856,
+        0.6532814824381883, 0.27059805007309856, 0.38268343236508995, 0.0, 0.0, -0.9238795325112868,
+        0.0, -0.9238795325112868, 0.38268343236508995, 0.0, 0.7071067811865476, -5.5511151231257815e-17,
+        -5.5511151231257815e-17, 0.7071067811865476, 5.5511151231257815e-17, 0.7071067811865476, 0.7071067811865476, 5.5511151231257815e-17,
+        0.5, 0.5, 0.5, 0.5, -0.5, 0.5,
+        0.5, -0.5, 0.0, 0.0, -6.312253112239643e-33, -1.0,
+        6.312253112239643e-33, -1.0, 0.0, 0.0, 1.848816132009102e-33, -0.7071067811865476,
+        1.848816132009102e-33, -0.7071067811865476, -1.848816132009102e-33, -0.7071067811865476, 1.848816132009102e-33, 0.7071067811865476,
+        0.5000000000000001, 5.551115123125783e-17, 5.551115123125783e-17};
+        EXPECT(slam_cx_decompose(nullptr, 0, 1, 0, cx_gate, cx_dress, d, i32, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_cx_decompose(nullptr, 0, 1, 2, cx_gate, cx_dress, d, i32, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "family") != nullptr);
+        EXPECT(slam_cx_decompose(nullptr, 0, 1, 1, cx_gate, cx_dress, d, i32, d, d) == SLAM_ERR_INVALID);  // the other family's class
+        EXPECT(std::strstr(slam_last_error(), "coordinates") != nullptr);
+        EXPECT(slam_cx_decompose(nullptr, 0, 1, 0, nullptr, cx_dress, d, i32, d, d) == SLAM_ERR_INVALID);
+        double bad[SLAM_CX_DRESS];
+        std::memcpy(bad, cx_dress, sizeof(bad));
+        bad[3] += 1e-9;  // one factor off: the gate is not rebuilt
+        EXPECT(slam_cx_decompose(nullptr, 0, 1, 0, cx_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "rebuild the gate") != nullptr);
+        std::memcpy(bad, cx_dress, sizeof(bad));
+        bad[8 * 9 + 2] += 1e-9;  // a factor of CX21 off
+        EXPECT(slam_cx_decompose(nullptr, 0, 1, 0, cx_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "CX21") != nullptr);
+        for (double& v : bad) v = 0.0;
+        bad[96] = 0.5;
+        EXPECT(slam_cx_decompose(nullptr, 0, 1, 0, cx_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);  // all-zero factors
+    }
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_pd_sample(nullptr, 1.0, 0.0, 1.0, 4, 1, 1.0, 0, 0, 1, nullptr, 8, d, nullptr, nullptr) == SLAM_ERR_INVALID);
