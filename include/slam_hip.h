@@ -271,6 +271,28 @@ int slam_cx_decompose(slam_ctx* ctx, int64_t first, int64_t count, int family, c
                       int32_t* cycles, double* loss, double* gap);
 
 /*
+ * Closed-form decomposition into one or two gates G of the B class, CAN(1/2, 1/4, 0), on the device, one thread per resident target
+ * (csrc/slam_b.hpp; Zhang, Vala, Sastry, Whaley, PRL 93, 020502: two B gates reach every two-qubit unitary).  For the resident targets
+ * [first, first + count) (nothing is uploaded, no gate table is needed):
+ *   gate    double[32]         G, row-major (re, im)
+ *   dress   double[SLAM_B_DRESS]  the host's reduction of G: four 2x2 factors (row-major re, im; in a pair the factor of the qubit of
+ *                              the high bit comes first) l1, l0, r1, r0, then c[3], with  G = e^{i .} (l1 (x) l0) CAN(c) (r1 (x) r0),
+ *                              c the KAK coordinates of G (within 4e-8 of (1/2, 1/4, 0) once folded to c1 <= 1/2)
+ *   x_out   double[count][24]  the 6 (k + 1) template angles in the index order of slam_eval_unitary in the front of the row, zeros
+ *                              behind: template(x, [G] * k) = e^{i phi} T
+ *   cycles  int32[count]       k: on the coordinates rounded to 8 digits and folded to c1 <= 1/2 (span_rules.minimal_span, tolerance
+ *                              2e-8) 1 in G's own class, else 2; a local target gets two gates
+ *   loss    double[count]      1 - |Tr(T^+ template(x_out))| / 4, from a forward pass of the written row
+ *   gap     double[count]      max-norm distance (units of pi) that remains between the chamber points when the interior circuit is
+ *                              aligned with the target, as slam_complete_locals' gap_out: rounding only for two gates
+ * Any output pointer may be NULL.  SLAM_ERR_INVALID for a NULL context, a window outside the resident batch, a gate outside the class
+ * and a gate that the dress factors do not rebuild to 1e-12 (up to a phase; checked on the host before anything is written).
+ */
+#define SLAM_B_DRESS 35
+int slam_b_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* gate, const double* dress, double* x_out, int32_t* cycles,
+                     double* loss, double* gap);
+
+/*
  * Span predictor on the device: for every resident target of [first, first + count) the smallest number k of leading gates of a
  * template whose coverage set contains the target -- the lookup CircuitTemplate.get_spanning_range makes with use_polytopes=True
  * (src/slam/basis.py:95-100 -> monodromy_range_from_target, src/slam/utils/polytopes/polytope_wrap.py:39-94).  The coverage sets
@@ -755,7 +777,8 @@ const char* slam_version(void);
  *      later: slam_metric_update_check (a new symbol only);
  *      later: slam_haar_select_spans and slam_sample_haar_indexed (new symbols only);
  *      later: slam_sqiswap_decompose (a new symbol only);
- *      later: slam_cx_decompose (a new symbol only).
+ *      later: slam_cx_decompose (a new symbol only);
+ *      later: slam_b_decompose (a new symbol only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

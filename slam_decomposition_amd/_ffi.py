@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "slam_complete_locals",
     "slam_sqiswap_decompose",
     "slam_cx_decompose",
+    "slam_b_decompose",
     "slam_predict_spans",
     "slam_coverage_lookup",
     "slam_eval_c1c2c3",
@@ -232,6 +233,8 @@ def load_library() -> C.CDLL:
         lib.slam_sqiswap_decompose.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P]
     if hasattr(lib, "slam_cx_decompose"):
         lib.slam_cx_decompose.argtypes = [P, C.c_int64, C.c_int64, C.c_int, P, P, P, P, P, P]
+    if hasattr(lib, "slam_b_decompose"):
+        lib.slam_b_decompose.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P, P, P]
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
     if hasattr(lib, "slam_coverage_lookup"):
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
@@ -501,6 +504,37 @@ def cx_dress(gate):
     return family, g, dress
 
 
+B_DRESS = 35  # SLAM_B_DRESS
+_B_CLASS = (0.5, 0.25, 0.0)
+
+
+def b_class(gate) -> None:
+    """Passes for a 4x4 gate of the B class, judged on the 8-digit Weyl coordinates with ``span_rules._TOL``; ``ValueError`` (naming
+    the coordinates) for any other gate."""
+    from . import span_rules, weyl
+
+    c = weyl.c1c2c3(np.asarray(gate, dtype=np.complex128))
+    f = np.abs(span_rules._fold(c)[0])
+    if not np.max(np.abs(f - np.array(_B_CLASS))) < span_rules._TOL:
+        raise ValueError(f"the gate is not of the B class (0.5, 0.25, 0) (Weyl coordinates {tuple(float(v) for v in c)})")
+
+
+def b_dress(gate):
+    """The host's reduction of a basis gate for slam_b_decompose (include/slam_hip.h): ``(gate [4, 4] complex128,
+    dress float64[B_DRESS])`` from one ``weyl.kak`` call -- G = e^{i .} (l1 (x) l0) CAN(c) (r1 (x) r0)."""
+    from . import weyl
+
+    g = np.ascontiguousarray(gate, dtype=np.complex128)
+    if g.shape != (4, 4):
+        raise ValueError("the basis gate must be a 4x4 matrix")
+    b_class(g)
+    _, l1, l0, c, r1, r0 = weyl.kak(g)
+    dress = np.concatenate([np.ascontiguousarray(np.stack([l1, l0, r1, r0]), dtype=np.complex128).view(np.float64).ravel(),
+                            np.asarray(c, dtype=np.float64)])
+    assert dress.shape == (B_DRESS,)
+    return g, dress
+
+
 class Context:
     """One GPU: resident targets + gate table + work buffers (``slam_ctx``)."""
 
@@ -628,6 +662,21 @@ class Context:
         loss = np.zeros(n)
         gap = np.zeros(n)
         _check(self._lib.slam_cx_decompose(self._h, int(first), count, family, _ptr(g), _ptr(dress), _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
+        return x, cycles, loss, gap
+
+    def b_decompose(self, gate, first: int = 0, count: Optional[int] = None):
+        """Closed-form circuits of one or two gates ``gate`` -- a 4x4 matrix of the B class -- for the resident targets
+        [first, first + count) (slam_b_decompose; nothing is uploaded, no gate table is needed) -> ``(x [count, 24], cycles [count],
+        loss [count], gap [count])`` as ``cx_decompose`` returns them.  ``ValueError`` for a gate outside the class
+        (``span_rules._TOL``)."""
+        g, dress = b_dress(gate)
+        count = self.n_targets - first if count is None else int(count)
+        n = max(count, 0)
+        x = np.zeros((n, 24))
+        cycles = np.zeros(n, dtype=np.int32)
+        loss = np.zeros(n)
+        gap = np.zeros(n)
+        _check(self._lib.slam_b_decompose(self._h, int(first), count, _ptr(g), _ptr(dress), _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
         return x, cycles, loss, gap
 
     def metric_update_check(self, h: np.ndarray, s: np.ndarray, w: np.ndarray, v: np.ndarray):

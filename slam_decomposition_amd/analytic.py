@@ -22,6 +22,11 @@ otherwise (``span_rules.minimal_span``; a local target gets two), with interior 
 
     res = cx_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20), CXGate())
     basis = CircuitTemplate(base_gates=[CXGate()]); basis.build(e.cycles); basis.eval(e.Xk)            # likewise
+
+Gates of the B class, CAN(1/2, 1/4, 0): one gate for a target of that class, two for EVERY other target (Zhang, Vala, Sastry, Whaley,
+PRL 93, 020502; ``slam_b_decompose``, csrc/slam_b.hpp).  ``decompose`` does not dispatch to it yet:
+
+    res = b_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20), BerkeleyGate())
 """
 from __future__ import annotations
 
@@ -112,10 +117,30 @@ def cx_decompose(targets, basis_gate=None, device: int = 0, success_threshold: f
     return CxDecomposition(cycles, x, loss, gap, success_threshold, basis_gate)
 
 
+def b_decompose(targets, basis_gate=None, device: int = 0, success_threshold: float = 1e-10) -> CxDecomposition:
+    """Circuits of one or two gates ``basis_gate`` (default ``BerkeleyGate()``; any gate object or 4x4 matrix of the B class: a
+    ``CanonicalGate`` or ``UnitaryGate`` at that point, dressed with local gates or not) that equal ``targets``, which are given as for
+    ``sqiswap_decompose``: one gate for a target of the gate's own class, two for every other one (a local target included).
+    ``ValueError`` for a gate outside the class."""
+    from . import _ffi
+    from .gates import BerkeleyGate
+
+    basis_gate = BerkeleyGate() if basis_gate is None else basis_gate
+    g = gate_matrix(basis_gate)
+    _ffi.b_class(g)  # before any context is made
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
+    if n == 0:
+        return CxDecomposition(np.zeros(0, dtype=np.int32), np.zeros((0, 24)), np.zeros(0), np.zeros(0), success_threshold, basis_gate)
+    x, cycles, loss, gap = ctx.b_decompose(g, 0, n)
+    return CxDecomposition(cycles, x, loss, gap, success_threshold, basis_gate)
+
+
 def decompose(targets, basis_gate, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:
     """The closed-form decomposition that exists for ``basis_gate``, chosen as the reference's pass chooses it: ``RiSwapGate(1/2)`` (any
     gate whose matrix is that gate's) goes to ``sqiswap_decompose``, a gate of the CNOT class or of the iSWAP class to
-    ``cx_decompose``; ``NotImplementedError`` naming the gate's Weyl coordinates for anything else."""
+    ``cx_decompose``; ``NotImplementedError`` naming the gate's Weyl coordinates for anything else -- a gate of the B class included,
+    which ``b_decompose`` takes when it is called by name."""
     from . import _ffi, weyl
     from .gates import RiSwapGate
 
@@ -127,5 +152,6 @@ def decompose(targets, basis_gate, device: int = 0, success_threshold: float = 1
     except ValueError:
         raise NotImplementedError(
             "closed-form decompositions exist for RiSwapGate(1/2) and for basis gates of the CNOT class (0.5, 0, 0) and of the iSWAP "
-            f"class (0.5, 0.5, 0) only (got {basis_gate} with Weyl coordinates {tuple(float(v) for v in weyl.c1c2c3(g))})") from None
+            f"class (0.5, 0.5, 0) only (got {basis_gate} with Weyl coordinates {tuple(float(v) for v in weyl.c1c2c3(g))}); a gate of "
+            "the B class (0.5, 0.25, 0) is not dispatched here: call b_decompose") from None
     return cx_decompose(targets, basis_gate, device, success_threshold)

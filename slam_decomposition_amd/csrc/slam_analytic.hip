@@ -1,5 +1,5 @@
 // slam_analytic.hip -- host side of libslamhip.so, analytic unit: the closed-form decompositions into sqrt(iSWAP) gates
-// (slam_analytic.hpp) and into gates of the CNOT or the iSWAP class (slam_cx.hpp).
+// (slam_analytic.hpp), into gates of the CNOT or the iSWAP class (slam_cx.hpp) and into gates of the B class (slam_b.hpp).
 #include "slam_host.hpp"
 
 #include <complex>
@@ -14,8 +14,9 @@
 #pragma pop_macro("__global__")
 #include "slam_analytic.hpp"
 #include "slam_cx.hpp"
+#include "slam_b.hpp"
 
-// ---- slam_cx_decompose: the host's share (plain C++) -------------------------------------------------------------------
+// ---- slam_cx_decompose, slam_b_decompose: the host's share (plain C++) -------------------------------------------------------------------
 namespace {
 
 using cd = std::complex<double>;
@@ -147,9 +148,77 @@ int cx_fold_dress(int family, const double* gate, const double* dress, double* t
     return SLAM_OK;
 }
 
+// Checks gate against dress and folds dress into the kernel's table (slam_b.hpp).  dress: the four 2x2 factors l1, l0, r1, r0
+// (row-major re, im), then the gate's KAK coordinates c[3].
+int b_fold_dress(const double* gate, const double* dress, double* table) {
+    M2 f[4];
+    for (int j = 0; j < 4; ++j) f[j] = load2(dress + 8 * j);
+    const double* c = dress + 32;
+    const double own[3] = {0.5, 0.25, 0.0};
+    double fc[3] = {c[0], c[1], c[2]};
+    if (fc[0] > 0.5) {
+        fc[0] = 1.0 - fc[0];
+        fc[2] = -fc[2];
+    }
+    for (int j = 0; j < 3; ++j)
+        if (!(std::fabs(std::fabs(fc[j]) - own[j]) < 4e-8))
+            return fail(SLAM_ERR_INVALID, "the dress coordinates (%g, %g, %g) are not those of the B class (0.5, 0.25, 0)", c[0], c[1], c[2]);
+    M4 G;
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) G.m[r][k] = cd(gate[2 * (4 * r + k)], gate[2 * (4 * r + k) + 1]);
+    const double d = phase_distance(G, mul(mul(kron(f[0], f[1]), can(c)), kron(f[2], f[3])));
+    if (!(d <= 1e-12)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild the gate (max deviation %g)", d);
+    for (int j = 0; j < 32; ++j) table[j] = gate[j];
+    // the interior layer of the G-circuit is r^+ K l^+: qubit 0 first, as the rows hold it
+    const M2 order[4] = {dag(f[3]), dag(f[1]), dag(f[2]), dag(f[0])};
+    for (int j = 0; j < 4; ++j)
+        for (int r = 0; r < 2; ++r)
+            for (int k = 0; k < 2; ++k) {
+                table[32 + 8 * j + 2 * (2 * r + k)] = order[j].m[r][k].real();
+                table[32 + 8 * j + 2 * (2 * r + k) + 1] = order[j].m[r][k].imag();
+            }
+    return SLAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int slam_b_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* gate, const double* dress, double* x_out, int32_t* cycles,
+                     double* loss, double* gap) {
+    // what needs no context first, as in slam_cx_decompose
+    if (!gate || !dress) return fail(SLAM_ERR_INVALID, "gate and dress are required");
+    double table[kBTable];
+    const int rc = b_fold_dress(gate, dress, table);
+    if (rc) return rc;
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_grad.reserve((size_t)count * 24 * sizeof(double)));  // the rows
+    HIP_TRY(ctx->ev_loss.reserve((size_t)count * 2 * sizeof(double)));   // losses, then gaps
+    HIP_TRY(ctx->ev_tof.reserve((size_t)count * sizeof(int32_t)));       // sizes
+    HIP_TRY(ctx->ev_x.reserve(sizeof(table)));                           // the gate and the interior factors
+    HIP_TRY(hipMemcpy(ctx->ev_x.p, table, sizeof(table), hipMemcpyHostToDevice));  // from the stack: done before the call goes on
+    BArgs a{};
+    a.targets = ctx->targets.as<double>() + first * 32;
+    a.table = ctx->ev_x.as<double>();
+    a.M = count;
+    a.x_out = ctx->ev_grad.as<double>();
+    a.cycles = ctx->ev_tof.as<int32_t>();
+    a.loss = ctx->ev_loss.as<double>();
+    a.gap = ctx->ev_loss.as<double>() + count;
+    hipLaunchKernelGGL(b_decompose_kernel, dim3((unsigned)((count + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (x_out) HIP_TRY(hipMemcpyAsync(x_out, a.x_out, (size_t)count * 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (cycles) HIP_TRY(hipMemcpyAsync(cycles, a.cycles, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (loss) HIP_TRY(hipMemcpyAsync(loss, a.loss, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (gap) HIP_TRY(hipMemcpyAsync(gap, a.gap, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
 
 int slam_cx_decompose(slam_ctx* ctx, int64_t first, int64_t count, int family, const double* gate, const double* dress, double* x_out,
                       int32_t* cycles, double* loss, double* gap) {

@@ -101,6 +101,37 @@ int main() {
         bad[96] = 0.5;
         EXPECT(slam_cx_decompose(nullptr, 0, 1, 0, cx_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);  // all-zero factors
     }
+    {  // slam_b_decompose likewise: BerkeleyGate and its reduction as Context.b_decompose computes it (_ffi.b_dress)
+        const double s = 0.38268343236508984, c = 0.9238795325112867;
+        const double b_gate[32] = {
+            c, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, s,
+            0.0, 0.0, s, 0.0, 0.0, c, 0.0, 0.0,
+            0.0, 0.0, 0.0, c, s, 0.0, 0.0, 0.0,
+            0.0, s, 0.0, 0.0, 0.0, 0.0, c, 0.0};
+        const double b_dress[SLAM_B_DRESS] = {
+            1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0,
+            1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0,
+            1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0,
+            1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0,
+            0.5, 0.25, 0.0};
+        EXPECT(slam_b_decompose(nullptr, 0, 1, b_gate, b_dress, d, i32, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_b_decompose(nullptr, 0, 1, nullptr, b_dress, d, i32, d, d) == SLAM_ERR_INVALID);
+        EXPECT(slam_b_decompose(nullptr, 0, 1, b_gate, nullptr, d, i32, d, d) == SLAM_ERR_INVALID);
+        double bad[SLAM_B_DRESS];
+        std::memcpy(bad, b_dress, sizeof(bad));
+        bad[33] = 0.0;  // the CNOT class
+        EXPECT(slam_b_decompose(nullptr, 0, 1, b_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "coordinates") != nullptr);
+        std::memcpy(bad, b_dress, sizeof(bad));
+        bad[3] += 1e-9;  // one factor off: the gate is not rebuilt
+        EXPECT(slam_b_decompose(nullptr, 0, 1, b_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "rebuild the gate") != nullptr);
+        for (double& v : bad) v = 0.0;
+        bad[32] = 0.5;
+        bad[33] = 0.25;
+        EXPECT(slam_b_decompose(nullptr, 0, 1, b_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);  // all-zero factors
+    }
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_pd_sample(nullptr, 1.0, 0.0, 1.0, 4, 1, 1.0, 0, 0, 1, nullptr, 8, d, nullptr, nullptr) == SLAM_ERR_INVALID);
