@@ -330,6 +330,30 @@ int slam_coverage_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_
                          const double* points, const double* bounds, double tol, int64_t* counts_out, int32_t* entry_out);
 
 /*
+ * Family-extended lookup on the device (recursive_sibling_check, src/slam/utils/gates/family_extend.py:17-117, for every resident
+ * target of [first, first + count)): a gate family is a base pulse (member 0) and the same pulse run 2^a 3^b times as long.  Member m
+ * has the rows [table_offsets[m], table_offsets[m + 1]) of one concatenated table laid out as for slam_coverage_lookup, row j of a
+ * member = j + 1 applications of it, at the cost (j + 2) cost_1q + (j + 1) durations[m].
+ *   policy 0  the reference's walk: k = the first row of the member that contains the target; stop at k = 1; else go on to
+ *             child_even[m] (k even) or child_odd[m] (k odd), stop if that is -1 or does not contain the target; unwinding, a level
+ *             keeps its child's result only where that is strictly cheaper;
+ *   policy 1  the cheapest over ALL members that contain the target (ties: the smaller member index).
+ * A local target takes no gate (cost 0); a target that member 0 does not contain is unreachable, under both policies.
+ *   n_members                1 .. SLAM_FAMILY_MAX_MEMBERS, every member with at least one row, E + E_0 + 4 <= 8192
+ *   child_even, child_odd    int32[n_members]: -1, or an index GREATER than the member's own
+ *   durations                double[n_members], finite
+ * counts_out       int64[E + 2]: targets that ended on each row, then local targets, then unreachable ones.
+ * base_counts_out  int64[E_0 + 2], E_0 = table_offsets[1]: the same for member 0 alone (no family), from the same pass.
+ * member_out, gates_out  int32[count] or NULL: member index and number of gates per target; -1 / 0 local, -1 / -1 unreachable.
+ * Integer counts: the result does not depend on the order in which the device adds them up.
+ */
+#define SLAM_FAMILY_MAX_MEMBERS 32
+int slam_family_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_members, const int32_t* table_offsets, const int32_t* kinds,
+                       const double* points, const double* bounds, const int32_t* child_even, const int32_t* child_odd,
+                       const double* durations, double cost_1q, double tol, int32_t policy, int64_t* counts_out,
+                       int64_t* base_counts_out, int32_t* member_out, int32_t* gates_out);
+
+/*
  * Parallel-drive coverage (the sampling half of src/slam/utils/gates/parallel_drive_volume.py:176-256; csrc/slam_pd.hpp).
  *
  * slam_pd_sample: n_samples random templates of k ConversionGainSmushGate(pc, pg, gc, gg, gx[0:N], gy[0:N], t), N = n_slices, with a
@@ -778,7 +802,8 @@ const char* slam_version(void);
  *      later: slam_haar_select_spans and slam_sample_haar_indexed (new symbols only);
  *      later: slam_sqiswap_decompose (a new symbol only);
  *      later: slam_cx_decompose (a new symbol only);
- *      later: slam_b_decompose (a new symbol only).
+ *      later: slam_b_decompose (a new symbol only);
+ *      later: slam_family_lookup (a new symbol only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -41,6 +41,9 @@ PD_MAX_SPAN = 8  # SLAM_PD_MAX_SPAN
 PD_MAX_SLICES = 16  # SLAM_PD_MAX_SLICES
 PD_MAX_DIRS = 1024  # SLAM_PD_MAX_DIRS
 REGION_MAX = 256  # SLAM_REGION_MAX
+FAMILY_MAX_MEMBERS = 32  # SLAM_FAMILY_MAX_MEMBERS
+FAMILY_MAX_BINS = 8192  # slam_family_lookup: E + E_0 + 4 histogram bins at most
+POLICY_REFERENCE, POLICY_BEST = 0, 1  # slam_family_lookup: the reference's walk / the cheapest member
 
 # every symbol include/slam_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = (
@@ -64,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "slam_b_decompose",
     "slam_predict_spans",
     "slam_coverage_lookup",
+    "slam_family_lookup",
     "slam_eval_c1c2c3",
     "slam_sample_haar",
     "slam_sample_haar_indexed",
@@ -238,6 +242,8 @@ def load_library() -> C.CDLL:
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
     if hasattr(lib, "slam_coverage_lookup"):
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
+    if hasattr(lib, "slam_family_lookup"):
+        lib.slam_family_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32] + [P] * 7 + [C.c_double, C.c_double, C.c_int32] + [P] * 4
     lib.slam_eval_c1c2c3.argtypes = [P, C.c_int32, P, P, C.c_int64, C.c_int32, P]
     lib.slam_sample_haar.argtypes = [P, C.c_uint64, C.c_int64, C.c_int64]
     if hasattr(lib, "slam_haar_select_spans"):
@@ -457,6 +463,52 @@ def _span_half_spaces(gate_coords_seq, k_max: int):
     for k in range(2, k_max + 1):
         bounds[k - 1] = coverage.region(g[:k])
     return point, bounds
+
+
+_POLICIES = {"reference": POLICY_REFERENCE, "best": POLICY_BEST, POLICY_REFERENCE: POLICY_REFERENCE, POLICY_BEST: POLICY_BEST}
+
+
+def family_arguments(tables, child_even, child_odd, durations, cost_1q, policy):
+    """What slam_family_lookup takes for a gate family, checked here as the library checks it (no device is needed to be told of a
+    malformed family): ``(offsets, kinds, points, bounds, child_even, child_odd, durations, cost_1q, policy)``.  ``tables``: one object
+    per member with ``kinds`` / ``points`` / ``bounds`` as ``Context.coverage_lookup`` reads them, row j = j + 1 applications."""
+    tables = list(tables)
+    n = len(tables)
+    if not 1 <= n <= FAMILY_MAX_MEMBERS:
+        raise ValueError(f"a family has 1..{FAMILY_MAX_MEMBERS} members (got {n})")
+    if policy not in _POLICIES:
+        raise ValueError(f"policy must be 'reference' or 'best' (got {policy!r})")
+    sizes = [len(np.asarray(t.kinds).reshape(-1)) for t in tables]
+    if min(sizes) < 1:
+        raise ValueError("every member needs at least one row")
+    offsets = np.zeros(n + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(sizes)
+    if int(offsets[-1]) + sizes[0] + 4 > FAMILY_MAX_BINS:
+        raise ValueError(f"too many coverage rows ({int(offsets[-1])})")
+    kinds = np.ascontiguousarray(np.concatenate([np.asarray(t.kinds, dtype=np.int32).reshape(-1) for t in tables]))
+    points = [np.asarray(t.points, dtype=np.float64) for t in tables]
+    bounds = [np.asarray(t.bounds, dtype=np.float64) for t in tables]
+    for m, (s, p, b) in enumerate(zip(sizes, points, bounds)):
+        if p.shape != (s, 4) or b.shape != (s, 14):
+            raise ValueError(f"member {m}: points must have shape [{s}, 4] and bounds [{s}, 14] (got {p.shape}, {b.shape})")
+    if np.any((kinds != 0) & (kinds != 1)):
+        raise ValueError("kinds must be 0 (one gate) or 1 (half-spaces)")
+    links = []
+    for name, child in (("child_even", child_even), ("child_odd", child_odd)):
+        c = np.ascontiguousarray(child, dtype=np.int32).reshape(-1)
+        if c.shape != (n,):
+            raise ValueError(f"{name} must have one entry per member ({n}), got {c.shape[0]}")
+        bad = np.nonzero((c != -1) & ((c <= np.arange(n)) | (c >= n)))[0]
+        if len(bad):
+            raise ValueError(f"{name}[{int(bad[0])}] = {int(c[bad[0]])}: a child is -1 or a member behind its parent")
+        links.append(c)
+    d = np.ascontiguousarray(durations, dtype=np.float64).reshape(-1)
+    if d.shape != (n,):
+        raise ValueError(f"durations must have one entry per member ({n}), got {d.shape[0]}")
+    if not np.all(np.isfinite(d)) or not np.isfinite(cost_1q):
+        raise ValueError("durations and cost_1q must be finite")
+    return (offsets, kinds, np.ascontiguousarray(np.concatenate(points)), np.ascontiguousarray(np.concatenate(bounds)), links[0], links[1],
+            d, float(cost_1q), _POLICIES[policy])
 
 
 CX_DRESS = 99  # SLAM_CX_DRESS
@@ -731,6 +783,26 @@ class Context:
                                               _ptr(bounds), float(tol), _ptr(counts), _ptr(entries)))
         per_table = [counts[int(offsets[t]) + 2 * t : int(offsets[t + 1]) + 2 * (t + 1)] for t in range(len(tables))]
         return per_table, entries
+
+    def family_lookup(self, tables, child_even, child_odd, durations, cost_1q: float = 0.1, policy="reference", first: int = 0,
+                      count: Optional[int] = None, want_targets: bool = False, tol: float = 1e-7):
+        """The cheapest family member and gate count for each resident target of [first, first + count) (slam_family_lookup; the
+        targets stay on the device).  ``tables``: one per member, rows k = 1, 2, ... applications as ``coverage_lookup`` reads them;
+        ``child_even`` / ``child_odd`` [n_members]: where the walk goes from a member at an even / odd k (-1: nowhere);
+        ``durations`` [n_members]; ``policy``: "reference" (the walk of recursive_sibling_check) or "best" (the cheapest member).
+        Returns ``(counts int64[E + 2], base_counts int64[E_0 + 2], members, gates)``: targets per (member, k) row, then local, then
+        unreachable ones; the same for member 0 alone; and -- with ``want_targets`` -- int32[count] each (-1 / 0 local, -1 / -1
+        unreachable), else None.  Malformed families raise ``ValueError`` before the library is called."""
+        offsets, kinds, points, bounds, ce, co, d, c1q, pol = family_arguments(tables, child_even, child_odd, durations, cost_1q, policy)
+        count = self.n_targets - first if count is None else int(count)
+        counts = np.zeros(int(offsets[-1]) + 2, dtype=np.int64)
+        base_counts = np.zeros(int(offsets[1]) + 2, dtype=np.int64)
+        members = np.zeros(max(count, 0), dtype=np.int32) if want_targets else None
+        gates = np.zeros(max(count, 0), dtype=np.int32) if want_targets else None
+        _check(self._lib.slam_family_lookup(self._h, int(first), int(count), len(offsets) - 1, _ptr(offsets), _ptr(kinds), _ptr(points),
+                                            _ptr(bounds), _ptr(ce), _ptr(co), _ptr(d), c1q, float(tol), pol, _ptr(counts), _ptr(base_counts),
+                                            _ptr(members), _ptr(gates)))
+        return counts, base_counts, members, gates
 
     # -- parallel-drive coverage (slam_pd_*, slam_region_lookup) --------------------------------------------------------------------------
     def pd_sample(self, gc: float, gg: float, t: float, n_slices: int, k: int, n_samples: int, seed: int = 0, bound: float = 4 * np.pi,

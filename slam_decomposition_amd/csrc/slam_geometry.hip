@@ -1,4 +1,4 @@
-// slam_geometry.hip -- host side of libslamhip.so, geometry unit: Weyl coordinates, span prediction and coverage lookups, the Haar
+// slam_geometry.hip -- host side of libslamhip.so, geometry unit: Weyl coordinates, span prediction, coverage and family lookups, the Haar
 // sampler and its selection by template size, parallel-drive coverage samples and region lookups, the KAK decomposition and
 // local-gate completion (slam_weyl.hpp, slam_sampler.hpp, slam_span_sampler.hpp, slam_pd.hpp, slam_kak.hpp).
 #include "slam_host.hpp"
@@ -234,6 +234,91 @@ int slam_coverage_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_
     if (entry_out)
         HIP_TRY(hipMemcpyAsync(entry_out, ctx->cov_entries.p, (size_t)n_tables * (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost,
                                ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+int slam_family_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_members, const int32_t* table_offsets, const int32_t* kinds,
+                       const double* points, const double* bounds, const int32_t* child_even, const int32_t* child_odd,
+                       const double* durations, double cost_1q, double tol, int32_t policy, int64_t* counts_out, int64_t* base_counts_out,
+                       int32_t* member_out, int32_t* gates_out) {
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    static_assert(SLAM_FAMILY_MAX_MEMBERS == kFamilyMaxMembers, "family size");
+    if (n_members < 1 || n_members > SLAM_FAMILY_MAX_MEMBERS)
+        return fail(SLAM_ERR_INVALID, "n_members must be in 1..%d (got %d)", SLAM_FAMILY_MAX_MEMBERS, n_members);
+    if (!table_offsets || !kinds || !points || !bounds) return fail(SLAM_ERR_INVALID, "table_offsets / kinds / points / bounds is NULL");
+    if (!child_even || !child_odd || !durations) return fail(SLAM_ERR_INVALID, "child_even / child_odd / durations is NULL");
+    if (table_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "table_offsets[0] must be 0 (got %d)", table_offsets[0]);
+    for (int32_t m = 0; m < n_members; ++m)
+        if (table_offsets[m + 1] <= table_offsets[m])
+            return fail(SLAM_ERR_INVALID, "every member needs at least one row (offsets[%d] = %d, offsets[%d] = %d)", m, table_offsets[m], m + 1,
+                        table_offsets[m + 1]);
+    const int64_t E = table_offsets[n_members], E0 = table_offsets[1];
+    if (E + E0 + 4 > kFamilyMaxBins) return fail(SLAM_ERR_INVALID, "too many coverage rows (%lld; at most %d bins)", (long long)E, kFamilyMaxBins);
+    for (int64_t e = 0; e < E; ++e)
+        if (kinds[e] != 0 && kinds[e] != 1) return fail(SLAM_ERR_INVALID, "kinds[%lld] = %d (0 = one gate, 1 = half-spaces)", (long long)e, kinds[e]);
+    for (int32_t m = 0; m < n_members; ++m) {
+        // a child has a larger index than its parent: the kernel's one ascending pass over the members relies on it
+        if (child_even[m] != -1 && (child_even[m] <= m || child_even[m] >= n_members))
+            return fail(SLAM_ERR_INVALID, "child_even[%d] = %d must be -1 or in (%d, %d)", m, child_even[m], m, n_members);
+        if (child_odd[m] != -1 && (child_odd[m] <= m || child_odd[m] >= n_members))
+            return fail(SLAM_ERR_INVALID, "child_odd[%d] = %d must be -1 or in (%d, %d)", m, child_odd[m], m, n_members);
+        if (!std::isfinite(durations[m])) return fail(SLAM_ERR_INVALID, "durations[%d] is not finite", m);
+    }
+    if (!std::isfinite(cost_1q) || !std::isfinite(tol)) return fail(SLAM_ERR_INVALID, "cost_1q and tol must be finite");
+    if (policy != 0 && policy != 1) return fail(SLAM_ERR_INVALID, "policy must be 0 (the reference's walk) or 1 (best member), got %d", policy);
+    if (!counts_out || !base_counts_out) return fail(SLAM_ERR_INVALID, "counts_out / base_counts_out is NULL");
+    std::memset(counts_out, 0, (size_t)(E + 2) * sizeof(int64_t));
+    std::memset(base_counts_out, 0, (size_t)(E0 + 2) * sizeof(int64_t));
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one upload: offsets, kinds, both child lists (int32), then points [E][4], bounds [E][14] and the rows' costs [E] (doubles, 8-byte
+    // aligned).  The costs are computed here, once per row, so that the device compares the very doubles the caller sums.
+    const size_t off_b = 0, kind_b = (size_t)(n_members + 1) * sizeof(int32_t), ce_b = kind_b + (size_t)E * sizeof(int32_t);
+    const size_t co_b = ce_b + (size_t)n_members * sizeof(int32_t);
+    const size_t pt_b = ((co_b + (size_t)n_members * sizeof(int32_t)) + 7) & ~(size_t)7;
+    const size_t bd_b = pt_b + (size_t)E * 4 * sizeof(double);
+    const size_t cs_b = bd_b + (size_t)E * kSpanPatterns * sizeof(double);
+    const size_t total_b = cs_b + (size_t)E * sizeof(double);
+    std::vector<char> host(total_b, 0);
+    std::memcpy(host.data() + off_b, table_offsets, kind_b);
+    std::memcpy(host.data() + kind_b, kinds, (size_t)E * sizeof(int32_t));
+    std::memcpy(host.data() + ce_b, child_even, (size_t)n_members * sizeof(int32_t));
+    std::memcpy(host.data() + co_b, child_odd, (size_t)n_members * sizeof(int32_t));
+    std::memcpy(host.data() + pt_b, points, (size_t)E * 4 * sizeof(double));
+    std::memcpy(host.data() + bd_b, bounds, (size_t)E * kSpanPatterns * sizeof(double));
+    double* row_cost = reinterpret_cast<double*>(host.data() + cs_b);
+    for (int32_t m = 0; m < n_members; ++m)
+        for (int32_t e = table_offsets[m]; e < table_offsets[m + 1]; ++e) {
+            const double k = (double)(e - table_offsets[m] + 1);
+            const double c1 = (k + 1.0) * cost_1q, c2 = k * durations[m];
+            row_cost[e] = c1 + c2;  // (k + 1) cost_1q + k duration_m: two products and a sum, each rounded
+        }
+    const int64_t n_counts = E + 2 + E0 + 2;
+    HIP_TRY(ctx->cov_table.reserve(total_b));
+    HIP_TRY(ctx->cov_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
+    const bool want = member_out || gates_out;
+    if (want) HIP_TRY(ctx->cov_entries.reserve(2 * (size_t)count * sizeof(int32_t)));
+    char* tb = ctx->cov_table.as<char>();
+    HIP_TRY(hipMemcpyAsync(tb, host.data(), total_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->cov_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
+    unsigned long long* d_counts = ctx->cov_counts.as<unsigned long long>();
+    int32_t* d_member = want ? ctx->cov_entries.as<int32_t>() : nullptr;
+    hipLaunchKernelGGL(family_lookup_kernel, dim3((unsigned)((count + kCoverageBlock - 1) / kCoverageBlock)), dim3(kCoverageBlock),
+                       (size_t)n_counts * sizeof(unsigned int), ctx->stream, ctx->targets.as<double>() + first * 32, count, n_members,
+                       reinterpret_cast<const int32_t*>(tb + off_b), reinterpret_cast<const int32_t*>(tb + kind_b),
+                       reinterpret_cast<const double*>(tb + pt_b), reinterpret_cast<const double*>(tb + bd_b),
+                       reinterpret_cast<const double*>(tb + cs_b), reinterpret_cast<const int32_t*>(tb + ce_b),
+                       reinterpret_cast<const int32_t*>(tb + co_b), tol, policy, d_counts, d_counts + (E + 2), d_member,
+                       want ? d_member + count : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counts_out, d_counts, (size_t)(E + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base_counts_out, d_counts + (E + 2), (size_t)(E0 + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (member_out) HIP_TRY(hipMemcpyAsync(member_out, d_member, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (gates_out) HIP_TRY(hipMemcpyAsync(gates_out, d_member + count, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return SLAM_OK;
 }

@@ -106,6 +106,9 @@ class TemplateOptimizer:
                                       "templates without callback; host-driven, device objective), L-BFGS-B / SLSQP for V2 templates")
         if getattr(basis, "mixed_order", False) and (use_callback or self._host_method is not None):
             raise NotImplementedError("MixedOrderBasisCircuitTemplate: use_callback / override_method are not implemented")
+        if getattr(basis, "family_extended", False) and (use_callback or self._host_method is not None
+                                                          or self._cost_kind == _ffi.COST_MAKHLIN):
+            raise NotImplementedError("FamilyExtendedTemplate: use_callback / override_method / MakhlinFunctionalCost are not implemented")
         self._no_exterior = bool(getattr(basis, "no_exterior_1q", False)) and not self._v2
         if self._no_exterior and (use_callback or self._host_method is not None or getattr(basis, "mixed_order", False)):
             raise NotImplementedError("CircuitTemplate(no_exterior_1q=True): use_callback / override_method / mixed-order templates "
@@ -556,6 +559,44 @@ class TemplateOptimizer:
         self._set_stats([ctx.stats()])
         return best_loss, best_x, best_cycles  # (padded rows [n, 6 (k_top + 1)]: cut at 6 (cycles + 1) on access)
 
+    family_members = None  # after a FamilyExtendedTemplate run: per target the multiplier r of the sibling it was fitted with
+    family_costs = None  # ... and its cost (k + 1) cost_1q + k duration
+
+    def _run_batch_family(self, targets, n: int):
+        """``FamilyExtendedTemplate``: (member, k) per target from the device's family lookup (family_extend.py:17-117 for the whole
+        batch, ``slam_family_lookup``), then one ``slam_decompose_list`` per distinct (member, k) over its targets with the gate
+        sequence ``[m] * k`` -- the gate table holds the members' matrices.  The batch is resident once.  Local targets raise as
+        ``_run_batch_mixed_order`` does, unreachable ones as the cost lookup does."""
+        fam = self.basis.family
+        ctx = runtime.get_context(self.devices[0])
+        if self._device_sampler is not None:
+            self._device_sampler.fill(ctx)
+        else:
+            ctx.set_targets(targets)
+        _, _, members, gates = fam.device_lookup(ctx, self.basis.policy, 0, n, want_targets=True)
+        if np.any(gates < 0):
+            raise fam.unreachable_error()
+        if np.any(gates == 0):
+            raise ValueError()  # range(0, 1) -> CircuitTemplate.build(0), polytope_wrap.py:53-54, basis.py:127-128
+        k_top = int(gates.max())
+        if k_top > _ffi.MAX_SPAN_MINIMIZE:
+            raise NotImplementedError(f"template spans up to {_ffi.MAX_SPAN_MINIMIZE} are implemented on the HIP path (got {k_top})")
+        prm = self._opt_params()
+        ctx.set_gates(self.basis.gate_matrices)
+        ctx.set_cost(self._cost_kind)
+        ctx.reset_stats()
+        pair = members.astype(np.int64) * (k_top + 1) + gates
+        for p in np.unique(pair):
+            m, k = int(p) // (k_top + 1), int(p) % (k_top + 1)
+            ctx.decompose_list(np.nonzero(pair == p)[0], k, k, [[m] * k], prm, self.success_threshold, k_layout=k_top)
+        best_loss, best_x, best_cycles = ctx.fetch_results_range(k_top, 0, n)
+        self._span_losses = ctx.fetch_span_losses(0, n) if self._want_span_losses else None
+        self._set_stats([ctx.stats()])
+        self._family_member_index = members
+        self.family_members = fam.multipliers[members]
+        self.family_costs = (gates + 1) * fam.cost_1q + gates * fam.durations[members]
+        return best_loss, best_x, best_cycles  # (padded rows [n, 6 (k_top + 1)]: cut at 6 (cycles + 1) on access)
+
     def _run_batch_predicted(self, ctx, n: int):
         """Polytope mode for targets that were generated on the device (exact coverage regions): lookup, per-size lists and the span
         loop in one chain of kernels (``slam_decompose_predicted``) -- no index list is built on the host (round 4: ``np.nonzero`` per
@@ -866,6 +907,12 @@ class TemplateOptimizer:
                 idx = np.nonzero(ids == v)[0]
                 found[idx] = ctx.eval_c1c2c3(self.circuit_polytopes[idx[0]].gate_indices, np.stack([best_xs[i] for i in idx]))
             return found
+        if getattr(self.basis, "family_extended", False):
+            for m in np.unique(self._family_member_index):
+                for k in np.unique(best_cycles[self._family_member_index == m]):
+                    idx = np.nonzero((self._family_member_index == m) & (best_cycles == k))[0]
+                    found[idx] = ctx.eval_c1c2c3([int(m)] * int(k), np.stack([best_xs[i] for i in idx]))
+            return found
         for k in np.unique(best_cycles):
             idx = np.nonzero(best_cycles == k)[0]
             X = self.basis.device_vector(np.stack([best_xs[i] for i in idx]), int(k))
@@ -1062,6 +1109,9 @@ class TemplateOptimizer:
             else:
                 spans_of = [list(self.basis.get_spanning_range(stacked[0]))] * n
             best_loss, best_xs, best_cycles = self._run_batch_callback(stacked, spans_of)
+        elif getattr(self.basis, "family_extended", False):
+            best_loss, best_xs, best_cycles = self._run_batch_family(stacked, n)
+            spans_of = [[int(k)] for k in best_cycles]
         elif poly_resident:
             best_loss, best_xs, best_cycles = self._run_batch_predicted(ctx0, n)
         elif getattr(self.basis, "mixed_order", False):
@@ -1085,6 +1135,8 @@ class TemplateOptimizer:
         best_cycles = np.asarray(best_cycles)
         if getattr(self.basis, "mixed_order", False):
             self.basis.set_polytope(self.circuit_polytopes[-1])
+        if getattr(self.basis, "family_extended", False):
+            self.basis.bind_member(int(self._family_member_index[-1]))
         self.basis.build(n_repetitions=int(best_cycles[-1]))  # the reference leaves the template at the last size
         if isinstance(best_xs, RowBlocks) and (log_on or self.use_callback):
             best_xs = best_xs.as_array()

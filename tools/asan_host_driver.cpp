@@ -134,6 +134,7 @@ int main() {
     }
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
+    EXPECT(slam_family_lookup(nullptr, 0, 1, 1, i32, i32, d, d, i32, i32, d, 0.1, 1e-7, 0, &i64, &i64, i32, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_pd_sample(nullptr, 1.0, 0.0, 1.0, 4, 1, 1.0, 0, 0, 1, nullptr, 8, d, nullptr, nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_pd_extremes(nullptr, d, 1, &i64, d) == SLAM_ERR_INVALID);
     EXPECT(slam_pd_filter(nullptr, d, 1, 0.0, 0, &i64, nullptr, nullptr) == SLAM_ERR_INVALID);
