@@ -34,18 +34,55 @@ WOLFE_C2 = 0.7     # an accepted step whose slope along p fell by less than (1 -
 GROW_FACTOR = 8.0  # ... the next first trial step is this much longer (compounding while it keeps happening)
 GROW_MAX = 1048576.0
 RESTART_PERIOD = 128  # every so many accepted iterations the quasi-Newton metric starts over from the identity (see below)
+BACKTRACK_MIN = 0.1      # a back-track shortens the trial step to no less than this fraction of it ...
+BACKTRACK_MAX = 0.5      # ... and to no more than this one
+FIRST_SCALING = True     # the first update of a metric scales the identity by s.y / y.y first
+SKIP_SHORT_UPDATES = True  # no metric update from a too-short step
+
+# which criterion ended a run (the ``end`` entry of ``record``); the first three are ST_CONVERGED
+END_STOP_LOSS, END_GTOL, END_FAR, END_MAXITER, END_STALL, END_BACKTRACK, END_NONFINITE = (
+    "stop_loss", "gtol", "far", "maxiter", "stall", "backtrack", "nonfinite")
+
+
+def pinned_exterior(loss_and_grad, k):
+    """``loss_and_grad`` for a template whose layers 0 and k stay at the identity (SLAM_FLAG_NO_EXTERIOR): their parameters are
+    zeroed before the evaluation and their gradient components after it, as the kernel does."""
+    def fn(x, gate_seq, target):
+        x = np.array(x, dtype=np.float64)
+        x[:6] = 0.0
+        x[6 * k:] = 0.0
+        f, g = loss_and_grad(x, gate_seq, target)
+        g = np.array(g, dtype=np.float64)
+        g[:6] = 0.0
+        g[6 * k:] = 0.0
+        return f, g
+    return fn
 
 
 def minimize_port(
     x0, gate_seq, target, maxiter=2500, gtol=1e-9, stop_loss=1e-13, gtol_far=1e-5, far_loss=1e-6, trace=None,
-    h_dtype=np.float32,
+    h_dtype=np.float32, loss_and_grad=None, xs=None, record=None,
 ):
-    """Returns (loss, x, iters, status, n_evals)."""
+    """Returns (loss, x, iters, status, n_evals).
+
+    ``loss_and_grad(x, gate_seq, target)``: another objective or template than BasicCost on the free template.  ``xs``: a list that
+    receives the point after every accepted step.  ``record``: a list that receives one dict per accepted step with the decisions
+    taken -- ``trials`` [(step length, Armijo margin ft - f - c1 alpha g.p)] with the accepted trial last, ``short``, ``updated``,
+    ``first_scaling``, ``nondescent``, ``periodic``, ``grow`` (the factor in force after the step) -- and a last dict
+    {"end": criterion, "trials": the trailing failed trials}.  None of them changes a result."""
+    lg = o.loss_and_grad if loss_and_grad is None else loss_and_grad
     n = len(x0)
     x = np.array(x0, dtype=np.float64)
-    f, g = o.loss_and_grad(x, gate_seq, target)
+    f, g = lg(x, gate_seq, target)
     nev = 1
+    trials = []
+
+    def end(criterion):
+        if record is not None:
+            record.append({"end": criterion, "trials": trials})
+
     if not np.isfinite(f):
+        end(END_NONFINITE)
         return f, x, 0, 3, nev
     H = np.eye(n, dtype=h_dtype)
     hs1 = 0.0  # the effective inverse Hessian is H + hs1 I: the one-off scaling of the initial one is a scalar (as in the kernel)
@@ -55,9 +92,14 @@ def minimize_port(
     def converged():
         return f < stop_loss or gnorm < gtol or (gnorm < gtol_far and f > far_loss)
 
+    def criterion():
+        return END_STOP_LOSS if f < stop_loss else END_GTOL if gnorm < gtol else END_FAR
+
     if converged():
+        end(criterion())
         return f, x, 0, 0, nev
     if maxiter <= 0:
+        end(END_MAXITER)
         return f, x, 0, 1, nev
     alpha = min(1.0, STEP_MAX / max(np.sqrt(p @ p), 1e-300))
     grow = 1.0
@@ -66,9 +108,12 @@ def minimize_port(
     nstall = 0
     scaled = False
     status = 1
+    crit = END_MAXITER
+    nondescent = False
     while it < maxiter:
         gp = g @ p
         if not (gp < 0):
+            nondescent = True
             # not a descent direction (H lost positive-definiteness numerically): reset
             H = np.eye(n, dtype=h_dtype)
             hs1 = 0.0
@@ -76,10 +121,12 @@ def minimize_port(
             gp = g @ p
         s = alpha * p
         xt = x + s
-        ft, gt = o.loss_and_grad(xt, gate_seq, target)
+        ft, gt = lg(xt, gate_seq, target)
         nev += 1
         if not np.isfinite(ft):
             ft = np.inf
+        if record is not None:
+            trials.append((alpha, ft - f - ARMIJO_C1 * alpha * gp))
         if ft <= f + ARMIJO_C1 * alpha * gp:
             y = gt - g
             # s = alpha p: the products with s come from p.g' and the direction's own p.g, p.p (the kernel's formulas)
@@ -91,15 +138,17 @@ def minimize_port(
             # update below is skipped and H never learns to take longer steps): lengthen the next trial step
             short = sy < (1.0 - WOLFE_C2) * alpha * (-gp)
             q = (H @ gt.astype(h_dtype)).astype(np.float64)
-            if (not short) and sy > CURV_EPS * np.sqrt(ss * (y @ y)):
+            updated = (not (short and SKIP_SHORT_UPDATES)) and sy > CURV_EPS * np.sqrt(ss * (y @ y))
+            first = updated and not scaled
+            if updated:
                 rho = 1.0 / sy
                 fac = 1.0
-                if not scaled:
+                if not scaled and FIRST_SCALING:
                     # scale the initial inverse Hessian (the identity) before its first update (Nocedal & Wright
                     # eq. 6.20): H_eff = H + hs1 I with hs1 = fac - 1
                     fac = sy / (y @ y)
                     hs1 = fac - 1.0
-                    scaled = True
+                scaled = True
                 q = q + hs1 * gt
                 u = q + fac * p  # H_eff y = H_eff g' - H_eff g,  p = -H_eff g before this round's scaling
                 c = rho * (1.0 + rho * (y @ u))
@@ -115,17 +164,28 @@ def minimize_port(
             nback = 0
             if trace is not None:
                 trace.append(f)
+            if xs is not None:
+                xs.append(x.copy())
             gnorm = np.abs(g).max()
+            grow = min(grow * GROW_FACTOR, GROW_MAX) if short else 1.0
+            if record is not None:
+                record.append({"trials": trials, "short": bool(short), "updated": bool(updated), "first_scaling": bool(first),
+                               "nondescent": nondescent, "periodic": False, "grow": grow})
+                trials = []
+            nondescent = False
             if converged():
                 status = 0
+                crit = criterion()
                 break
             if nstall >= 2:
                 status = 4
+                crit = END_STALL
                 break
             p = pn
-            grow = min(grow * GROW_FACTOR, GROW_MAX) if short else 1.0
             alpha = min(grow, STEP_MAX / max(np.sqrt(p @ p), 1e-300))
-            if it % RESTART_PERIOD == 0:
+            if it % RESTART_PERIOD == 0 and it < maxiter:
+                if record is not None:
+                    record[-1]["periodic"] = True
                 # Periodic restart.  One item in 1e3..1e5 ends up with a metric that has stopped learning (steps nearly
                 # orthogonal to the gradient on a plateau: 400..1300 iterations where SciPy's BFGS needs 50..170 from the
                 # same start); restarted from the identity it is through in ~40 more.  Items this long are past the 99th
@@ -139,10 +199,12 @@ def minimize_port(
             # safeguarded quadratic interpolation backtrack
             denom = 2.0 * (ft - f - gp * alpha)
             a_new = -gp * alpha * alpha / denom if denom > 0 and np.isfinite(denom) else 0.5 * alpha
-            alpha = min(max(a_new, 0.1 * alpha), 0.5 * alpha)
+            alpha = min(max(a_new, BACKTRACK_MIN * alpha), BACKTRACK_MAX * alpha)
             grow = 1.0
             nback += 1
             if nback > MAX_BACKTRACK:
                 status = 4 if gnorm < STALL_GNORM else 2
+                crit = END_BACKTRACK
                 break
+    end(crit)
     return f, x, it, status, nev
