@@ -518,15 +518,33 @@ _SWAP = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], dtype
 _CX_CLASSES = ((0.5, 0.0, 0.0), (0.5, 0.5, 0.0))
 
 
-def cx_family(gate) -> int:
-    """0 for a 4x4 gate of the CNOT class, 1 for one of the iSWAP class, judged on the 8-digit Weyl coordinates with
-    ``span_rules._TOL``; ``ValueError`` (naming the coordinates) for any other gate."""
+def _in_class(gate, point):
+    """``(is the 4x4 gate of the class of CAN(point)?, its Weyl coordinates)``, judged on the 8-digit coordinates with
+    ``span_rules._TOL``."""
     from . import span_rules, weyl
 
     c = weyl.c1c2c3(np.asarray(gate, dtype=np.complex128))
     f = np.abs(span_rules._fold(c)[0])
+    return bool(np.max(np.abs(f - np.array(point))) < span_rules._TOL), c
+
+
+def _dress_head(gate, check):
+    """What ``cx_dress`` and ``b_dress`` start with: the gate as a 4x4 complex128 array, what ``check`` (``cx_family``, ``b_class``)
+    says of it, and its ``weyl.kak``."""
+    from . import weyl
+
+    g = np.ascontiguousarray(gate, dtype=np.complex128)
+    if g.shape != (4, 4):
+        raise ValueError("the basis gate must be a 4x4 matrix")
+    return g, check(g), weyl.kak(g)
+
+
+def cx_family(gate) -> int:
+    """0 for a 4x4 gate of the CNOT class, 1 for one of the iSWAP class, judged on the 8-digit Weyl coordinates with
+    ``span_rules._TOL``; ``ValueError`` (naming the coordinates) for any other gate."""
     for family, ref in enumerate(_CX_CLASSES):
-        if np.max(np.abs(f - np.array(ref))) < span_rules._TOL:
+        inside, c = _in_class(gate, ref)
+        if inside:
             return family
     raise ValueError(f"the gate is neither of the CNOT class nor of the iSWAP class (Weyl coordinates {tuple(float(v) for v in c)})")
 
@@ -538,11 +556,7 @@ def cx_dress(gate):
     from . import weyl
     from .gates import canonical_matrix
 
-    g = np.ascontiguousarray(gate, dtype=np.complex128)
-    if g.shape != (4, 4):
-        raise ValueError("the basis gate must be a 4x4 matrix")
-    family = cx_family(g)
-    _, l1, l0, c, r1, r0 = weyl.kak(g)
+    g, family, (_, l1, l0, c, r1, r0) = _dress_head(gate, cx_family)
     D = canonical_matrix(*_CX_CLASSES[family])
     if family:
         D = _SWAP @ D
@@ -563,24 +577,15 @@ _B_CLASS = (0.5, 0.25, 0.0)
 def b_class(gate) -> None:
     """Passes for a 4x4 gate of the B class, judged on the 8-digit Weyl coordinates with ``span_rules._TOL``; ``ValueError`` (naming
     the coordinates) for any other gate."""
-    from . import span_rules, weyl
-
-    c = weyl.c1c2c3(np.asarray(gate, dtype=np.complex128))
-    f = np.abs(span_rules._fold(c)[0])
-    if not np.max(np.abs(f - np.array(_B_CLASS))) < span_rules._TOL:
+    inside, c = _in_class(gate, _B_CLASS)
+    if not inside:
         raise ValueError(f"the gate is not of the B class (0.5, 0.25, 0) (Weyl coordinates {tuple(float(v) for v in c)})")
 
 
 def b_dress(gate):
     """The host's reduction of a basis gate for slam_b_decompose (include/slam_hip.h): ``(gate [4, 4] complex128,
     dress float64[B_DRESS])`` from one ``weyl.kak`` call -- G = e^{i .} (l1 (x) l0) CAN(c) (r1 (x) r0)."""
-    from . import weyl
-
-    g = np.ascontiguousarray(gate, dtype=np.complex128)
-    if g.shape != (4, 4):
-        raise ValueError("the basis gate must be a 4x4 matrix")
-    b_class(g)
-    _, l1, l0, c, r1, r0 = weyl.kak(g)
+    g, _, (_, l1, l0, c, r1, r0) = _dress_head(gate, b_class)
     dress = np.concatenate([np.ascontiguousarray(np.stack([l1, l0, r1, r0]), dtype=np.complex128).view(np.float64).ravel(),
                             np.asarray(c, dtype=np.float64)])
     assert dress.shape == (B_DRESS,)
@@ -686,19 +691,23 @@ class Context:
         _check(self._lib.slam_complete_locals(self._h, k, _ptr(gs), _ptr(x), _ptr(tof), M, _ptr(x_out), _ptr(loss), _ptr(gap)))
         return x_out, loss, gap
 
-    def sqiswap_decompose(self, first: int = 0, count: Optional[int] = None):
-        """Closed-form circuits of two or three sqrt(iSWAP) gates for the resident targets [first, first + count)
-        (slam_sqiswap_decompose; nothing is uploaded, no gate table is needed) -> ``(x [count, 24], cycles [count], loss [count],
-        gap [count])``: row i holds the 6 (cycles[i] + 1) template angles of a circuit that equals target first + i up to a phase,
-        zeros behind; loss is its BasicCost loss, gap the coordinate gap left by the interior formula (units of pi)."""
+    def _closed_form_call(self, fn, head_args, first: int, count: Optional[int]):
+        """``fn(ctx, first, count, *head_args, x, cycles, loss, gap)`` of a closed-form entry point with its four outputs allocated."""
         count = self.n_targets - first if count is None else int(count)
         n = max(count, 0)
         x = np.zeros((n, 24))
         cycles = np.zeros(n, dtype=np.int32)
         loss = np.zeros(n)
         gap = np.zeros(n)
-        _check(self._lib.slam_sqiswap_decompose(self._h, int(first), count, _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
+        _check(fn(self._h, int(first), count, *head_args, _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
         return x, cycles, loss, gap
+
+    def sqiswap_decompose(self, first: int = 0, count: Optional[int] = None):
+        """Closed-form circuits of two or three sqrt(iSWAP) gates for the resident targets [first, first + count)
+        (slam_sqiswap_decompose; nothing is uploaded, no gate table is needed) -> ``(x [count, 24], cycles [count], loss [count],
+        gap [count])``: row i holds the 6 (cycles[i] + 1) template angles of a circuit that equals target first + i up to a phase,
+        zeros behind; loss is its BasicCost loss, gap the coordinate gap left by the interior formula (units of pi)."""
+        return self._closed_form_call(self._lib.slam_sqiswap_decompose, (), first, count)
 
     def cx_decompose(self, gate, first: int = 0, count: Optional[int] = None):
         """Closed-form circuits of one, two or three gates ``gate`` -- a 4x4 matrix of the CNOT class or of the iSWAP class -- for the
@@ -707,14 +716,7 @@ class Context:
         equals target first + i up to a phase, zeros behind; loss is its BasicCost loss, gap the coordinate gap left by the alignment
         of the interior circuit (units of pi).  ``ValueError`` for a gate outside both classes (``span_rules._TOL``)."""
         family, g, dress = cx_dress(gate)
-        count = self.n_targets - first if count is None else int(count)
-        n = max(count, 0)
-        x = np.zeros((n, 24))
-        cycles = np.zeros(n, dtype=np.int32)
-        loss = np.zeros(n)
-        gap = np.zeros(n)
-        _check(self._lib.slam_cx_decompose(self._h, int(first), count, family, _ptr(g), _ptr(dress), _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
-        return x, cycles, loss, gap
+        return self._closed_form_call(self._lib.slam_cx_decompose, (family, _ptr(g), _ptr(dress)), first, count)
 
     def b_decompose(self, gate, first: int = 0, count: Optional[int] = None):
         """Closed-form circuits of one or two gates ``gate`` -- a 4x4 matrix of the B class -- for the resident targets
@@ -722,14 +724,7 @@ class Context:
         loss [count], gap [count])`` as ``cx_decompose`` returns them.  ``ValueError`` for a gate outside the class
         (``span_rules._TOL``)."""
         g, dress = b_dress(gate)
-        count = self.n_targets - first if count is None else int(count)
-        n = max(count, 0)
-        x = np.zeros((n, 24))
-        cycles = np.zeros(n, dtype=np.int32)
-        loss = np.zeros(n)
-        gap = np.zeros(n)
-        _check(self._lib.slam_b_decompose(self._h, int(first), count, _ptr(g), _ptr(dress), _ptr(x), _ptr(cycles), _ptr(loss), _ptr(gap)))
-        return x, cycles, loss, gap
+        return self._closed_form_call(self._lib.slam_b_decompose, (_ptr(g), _ptr(dress)), first, count)
 
     def metric_update_check(self, h: np.ndarray, s: np.ndarray, w: np.ndarray, v: np.ndarray):
         """Device check of the metric's rank-2 update ``H += s w^T + v s^T`` (slam_metric_update_check): ``h[n, na (na + 1) / 2, 4, 4]``

@@ -88,6 +88,11 @@ def _resident(ctx, targets) -> int:
     return n
 
 
+def _empty(cls, *tail):
+    """The result of class ``cls`` for no targets; ``tail`` are the fields behind the four arrays."""
+    return cls(np.zeros(0, dtype=np.int32), np.zeros((0, 24)), np.zeros(0), np.zeros(0), *tail)
+
+
 def sqiswap_decompose(targets, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:
     """Circuits of two or three sqrt(iSWAP) gates that equal ``targets``: an ``[N, 4, 4]`` array, a list of 4x4 matrices, any
     ``SampleFunction``, or a device sampler (``DeviceHaarBatch``, ``DeviceHaarSpanBatch``: anything with ``fill(ctx)``), whose targets
@@ -95,9 +100,22 @@ def sqiswap_decompose(targets, device: int = 0, success_threshold: float = 1e-10
     ctx = runtime.get_context(device)
     n = _resident(ctx, targets)
     if n == 0:
-        return SqiswapDecomposition(np.zeros(0, dtype=np.int32), np.zeros((0, 24)), np.zeros(0), np.zeros(0), success_threshold)
+        return _empty(SqiswapDecomposition, success_threshold)
     x, cycles, loss, gap = ctx.sqiswap_decompose(0, n)
     return SqiswapDecomposition(cycles, x, loss, gap, success_threshold)
+
+
+def _gate_decompose(targets, basis_gate, check, call, device: int, success_threshold: float) -> CxDecomposition:
+    """``cx_decompose`` and ``b_decompose``: ``check`` (of ``_ffi``) raises for a gate outside the class before any context is made,
+    ``call`` names the ``Context`` method."""
+    g = gate_matrix(basis_gate)
+    check(g)
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
+    if n == 0:
+        return _empty(CxDecomposition, success_threshold, basis_gate)
+    x, cycles, loss, gap = getattr(ctx, call)(g, 0, n)
+    return CxDecomposition(cycles, x, loss, gap, success_threshold, basis_gate)
 
 
 def cx_decompose(targets, basis_gate=None, device: int = 0, success_threshold: float = 1e-10) -> CxDecomposition:
@@ -106,15 +124,7 @@ def cx_decompose(targets, basis_gate=None, device: int = 0, success_threshold: f
     equal ``targets``, which are given as for ``sqiswap_decompose``.  ``ValueError`` for a gate outside both classes."""
     from . import _ffi
 
-    basis_gate = CXGate() if basis_gate is None else basis_gate
-    g = gate_matrix(basis_gate)
-    _ffi.cx_family(g)  # before any context is made
-    ctx = runtime.get_context(device)
-    n = _resident(ctx, targets)
-    if n == 0:
-        return CxDecomposition(np.zeros(0, dtype=np.int32), np.zeros((0, 24)), np.zeros(0), np.zeros(0), success_threshold, basis_gate)
-    x, cycles, loss, gap = ctx.cx_decompose(g, 0, n)
-    return CxDecomposition(cycles, x, loss, gap, success_threshold, basis_gate)
+    return _gate_decompose(targets, CXGate() if basis_gate is None else basis_gate, _ffi.cx_family, "cx_decompose", device, success_threshold)
 
 
 def b_decompose(targets, basis_gate=None, device: int = 0, success_threshold: float = 1e-10) -> CxDecomposition:
@@ -125,15 +135,7 @@ def b_decompose(targets, basis_gate=None, device: int = 0, success_threshold: fl
     from . import _ffi
     from .gates import BerkeleyGate
 
-    basis_gate = BerkeleyGate() if basis_gate is None else basis_gate
-    g = gate_matrix(basis_gate)
-    _ffi.b_class(g)  # before any context is made
-    ctx = runtime.get_context(device)
-    n = _resident(ctx, targets)
-    if n == 0:
-        return CxDecomposition(np.zeros(0, dtype=np.int32), np.zeros((0, 24)), np.zeros(0), np.zeros(0), success_threshold, basis_gate)
-    x, cycles, loss, gap = ctx.b_decompose(g, 0, n)
-    return CxDecomposition(cycles, x, loss, gap, success_threshold, basis_gate)
+    return _gate_decompose(targets, BerkeleyGate() if basis_gate is None else basis_gate, _ffi.b_class, "b_decompose", device, success_threshold)
 
 
 def decompose(targets, basis_gate, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:

@@ -4,14 +4,6 @@
 
 #include <complex>
 
-// slam_kak.hpp and the headers under it define their __global__ kernels where they are included, and slam_geometry.hip is the unit that
-// emits them (slam_host.hpp).  This unit calls their __device__ functions only: here those kernels are read as function templates
-// that nothing instantiates, so no second copy of them is emitted, on the host or on the device.
-#pragma push_macro("__global__")
-#undef __global__
-#define __global__ template <int = 0> __attribute__((global))
-#include "slam_kak.hpp"
-#pragma pop_macro("__global__")
 #include "slam_analytic.hpp"
 #include "slam_cx.hpp"
 #include "slam_b.hpp"
@@ -92,13 +84,12 @@ void put_entry(double* e, const M2& L, const M2& R, int axis, int src) {
     e[17] = src;
 }
 
-// Checks gate against dress and folds dress into the kernel's table (slam_cx.hpp).  dress: the twelve 2x2 factors l1, l0, r1, r0,
-// a12_1, a12_0, b12_1, b12_0, a21_1, a21_0, b21_1, b21_0 (row-major re, im), then the gate's KAK coordinates c[3].
-int cx_fold_dress(int family, const double* gate, const double* dress, double* table) {
-    M2 f[12];
-    for (int j = 0; j < 12; ++j) f[j] = load2(dress + 8 * j);
-    const double* c = dress + 96;
-    const double own[3] = {0.5, family ? 0.5 : 0.0, 0.0};
+// The head of both dress checks.  dress: n 2x2 factors, the first four l1, l0, r1, r0 (row-major re, im), then the gate's KAK
+// coordinates c[3].  Loads the factors into f, checks that c folds onto the class point `own` (`what` names the class in the message)
+// and that the first four factors rebuild the gate around CAN(c).
+int fold_dress_head(int n, const double* own, const char* what, const double* gate, const double* dress, M2* f) {
+    for (int j = 0; j < n; ++j) f[j] = load2(dress + 8 * j);
+    const double* c = dress + 8 * n;
     double fc[3] = {c[0], c[1], c[2]};
     if (fc[0] > 0.5) {
         fc[0] = 1.0 - fc[0];
@@ -106,19 +97,29 @@ int cx_fold_dress(int family, const double* gate, const double* dress, double* t
     }
     for (int j = 0; j < 3; ++j)
         if (!(std::fabs(std::fabs(fc[j]) - own[j]) < 4e-8))
-            return fail(SLAM_ERR_INVALID, "the dress coordinates (%g, %g, %g) are not those of family %d", c[0], c[1], c[2], family);
+            return fail(SLAM_ERR_INVALID, "the dress coordinates (%g, %g, %g) are not those of %s", c[0], c[1], c[2], what);
     M4 G;
     for (int r = 0; r < 4; ++r)
         for (int k = 0; k < 4; ++k) G.m[r][k] = cd(gate[2 * (4 * r + k)], gate[2 * (4 * r + k) + 1]);
-    const double tol = 1e-12;
-    double d = phase_distance(G, mul(mul(kron(f[0], f[1]), can(c)), kron(f[2], f[3])));
-    if (!(d <= tol)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild the gate (max deviation %g)", d);
+    const double d = phase_distance(G, mul(mul(kron(f[0], f[1]), can(c)), kron(f[2], f[3])));
+    if (!(d <= 1e-12)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild the gate (max deviation %g)", d);
+    return SLAM_OK;
+}
+
+// Checks gate against dress and folds dress into the kernel's table (slam_cx.hpp).  dress: the twelve 2x2 factors l1, l0, r1, r0,
+// a12_1, a12_0, b12_1, b12_0, a21_1, a21_0, b21_1, b21_0 (row-major re, im), then the gate's KAK coordinates c[3].
+int cx_fold_dress(int family, const double* gate, const double* dress, double* table) {
+    M2 f[12];
+    const double own[3] = {0.5, family ? 0.5 : 0.0, 0.0};
+    const int rc = fold_dress_head(12, own, family ? "family 1" : "family 0", gate, dress, f);
+    if (rc) return rc;
     // D = C or SWAP C with the class point itself; CX12 and CX21 through it
     const M4 C = can(own), D = family ? swap_rows(C) : C;
     M4 cx12{}, cx21{};
     cx12.m[0][0] = cx12.m[1][1] = cx12.m[2][3] = cx12.m[3][2] = 1.0;
     cx21.m[0][0] = cx21.m[2][2] = cx21.m[1][3] = cx21.m[3][1] = 1.0;
-    d = phase_distance(cx12, mul(mul(kron(f[4], f[5]), D), kron(f[6], f[7])));
+    const double tol = 1e-12;
+    double d = phase_distance(cx12, mul(mul(kron(f[4], f[5]), D), kron(f[6], f[7])));
     if (!(d <= tol)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild CX12 (max deviation %g)", d);
     d = phase_distance(cx21, mul(mul(kron(f[8], f[9]), D), kron(f[10], f[11])));
     if (!(d <= tol)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild CX21 (max deviation %g)", d);
@@ -152,22 +153,9 @@ int cx_fold_dress(int family, const double* gate, const double* dress, double* t
 // (row-major re, im), then the gate's KAK coordinates c[3].
 int b_fold_dress(const double* gate, const double* dress, double* table) {
     M2 f[4];
-    for (int j = 0; j < 4; ++j) f[j] = load2(dress + 8 * j);
-    const double* c = dress + 32;
     const double own[3] = {0.5, 0.25, 0.0};
-    double fc[3] = {c[0], c[1], c[2]};
-    if (fc[0] > 0.5) {
-        fc[0] = 1.0 - fc[0];
-        fc[2] = -fc[2];
-    }
-    for (int j = 0; j < 3; ++j)
-        if (!(std::fabs(std::fabs(fc[j]) - own[j]) < 4e-8))
-            return fail(SLAM_ERR_INVALID, "the dress coordinates (%g, %g, %g) are not those of the B class (0.5, 0.25, 0)", c[0], c[1], c[2]);
-    M4 G;
-    for (int r = 0; r < 4; ++r)
-        for (int k = 0; k < 4; ++k) G.m[r][k] = cd(gate[2 * (4 * r + k)], gate[2 * (4 * r + k) + 1]);
-    const double d = phase_distance(G, mul(mul(kron(f[0], f[1]), can(c)), kron(f[2], f[3])));
-    if (!(d <= 1e-12)) return fail(SLAM_ERR_INVALID, "the dress factors do not rebuild the gate (max deviation %g)", d);
+    const int rc = fold_dress_head(4, own, "the B class (0.5, 0.25, 0)", gate, dress, f);
+    if (rc) return rc;
     for (int j = 0; j < 32; ++j) table[j] = gate[j];
     // the interior layer of the G-circuit is r^+ K l^+: qubit 0 first, as the rows hold it
     const M2 order[4] = {dag(f[3]), dag(f[1]), dag(f[2]), dag(f[0])};
@@ -180,17 +168,12 @@ int b_fold_dress(const double* gate, const double* dress, double* table) {
     return SLAM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int slam_b_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* gate, const double* dress, double* x_out, int32_t* cycles,
-                     double* loss, double* gap) {
-    // what needs no context first, as in slam_cx_decompose
-    if (!gate || !dress) return fail(SLAM_ERR_INVALID, "gate and dress are required");
-    double table[kBTable];
-    const int rc = b_fold_dress(gate, dress, table);
-    if (rc) return rc;
+// What the three entry points do once their own arguments are checked: the context and the window, the buffers, the kernel's table
+// (n_table doubles, the gate and the interior factors; none for sqrt(iSWAP)) into ev_x, the launch and the read-backs, any of which
+// may be NULL.  `own` fills the fields that only this family's argument block has, given the table's device address.
+template <class Args, class Own>
+int run_closed_form(slam_ctx* ctx, int64_t first, int64_t count, void (*kernel)(Args), const double* table, size_t n_table, Own own,
+                    double* x_out, int32_t* cycles, double* loss, double* gap) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
     if (first < 0 || count < 0 || first + count > ctx->n_targets)
         return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
@@ -200,17 +183,19 @@ int slam_b_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* 
     HIP_TRY(ctx->ev_grad.reserve((size_t)count * 24 * sizeof(double)));  // the rows
     HIP_TRY(ctx->ev_loss.reserve((size_t)count * 2 * sizeof(double)));   // losses, then gaps
     HIP_TRY(ctx->ev_tof.reserve((size_t)count * sizeof(int32_t)));       // sizes
-    HIP_TRY(ctx->ev_x.reserve(sizeof(table)));                           // the gate and the interior factors
-    HIP_TRY(hipMemcpy(ctx->ev_x.p, table, sizeof(table), hipMemcpyHostToDevice));  // from the stack: done before the call goes on
-    BArgs a{};
+    if (table) {
+        HIP_TRY(ctx->ev_x.reserve(n_table * sizeof(double)));
+        HIP_TRY(hipMemcpy(ctx->ev_x.p, table, n_table * sizeof(double), hipMemcpyHostToDevice));  // from the caller's stack: done before the call goes on
+    }
+    Args a{};
+    own(a, ctx->ev_x.as<double>());
     a.targets = ctx->targets.as<double>() + first * 32;
-    a.table = ctx->ev_x.as<double>();
     a.M = count;
     a.x_out = ctx->ev_grad.as<double>();
     a.cycles = ctx->ev_tof.as<int32_t>();
     a.loss = ctx->ev_loss.as<double>();
     a.gap = ctx->ev_loss.as<double>() + count;
-    hipLaunchKernelGGL(b_decompose_kernel, dim3((unsigned)((count + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, a);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((count + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     if (x_out) HIP_TRY(hipMemcpyAsync(x_out, a.x_out, (size_t)count * 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (cycles) HIP_TRY(hipMemcpyAsync(cycles, a.cycles, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -220,69 +205,35 @@ int slam_b_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* 
     return SLAM_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+// Gate, dress and family are checked before the context -- what needs no context first: the host's share runs, and is checked, on a
+// machine without a device too.
+int slam_b_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* gate, const double* dress, double* x_out, int32_t* cycles,
+                     double* loss, double* gap) {
+    if (!gate || !dress) return fail(SLAM_ERR_INVALID, "gate and dress are required");
+    double table[kBTable];
+    const int rc = b_fold_dress(gate, dress, table);
+    if (rc) return rc;
+    return run_closed_form(ctx, first, count, b_decompose_kernel, table, kBTable, [](BArgs& a, const double* t) { a.table = t; }, x_out, cycles, loss, gap);
+}
+
 int slam_cx_decompose(slam_ctx* ctx, int64_t first, int64_t count, int family, const double* gate, const double* dress, double* x_out,
                       int32_t* cycles, double* loss, double* gap) {
-    // what needs no context first: the host's share runs, and is checked, on a machine without a device too
     if (family != 0 && family != 1) return fail(SLAM_ERR_INVALID, "family must be 0 (CNOT class) or 1 (iSWAP class), got %d", family);
     if (!gate || !dress) return fail(SLAM_ERR_INVALID, "gate and dress are required");
     double table[kCxTable];
     const int rc = cx_fold_dress(family, gate, dress, table);
     if (rc) return rc;
-    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
-    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
-    if (count == 0) return SLAM_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->ev_grad.reserve((size_t)count * 24 * sizeof(double)));  // the rows
-    HIP_TRY(ctx->ev_loss.reserve((size_t)count * 2 * sizeof(double)));   // losses, then gaps
-    HIP_TRY(ctx->ev_tof.reserve((size_t)count * sizeof(int32_t)));       // sizes
-    HIP_TRY(ctx->ev_x.reserve(sizeof(table)));                           // the gate and the interior table
-    HIP_TRY(hipMemcpy(ctx->ev_x.p, table, sizeof(table), hipMemcpyHostToDevice));  // from the stack: done before the call goes on
-    CxArgs a{};
-    a.targets = ctx->targets.as<double>() + first * 32;
-    a.table = ctx->ev_x.as<double>();
-    a.M = count;
-    a.family = family;
-    a.x_out = ctx->ev_grad.as<double>();
-    a.cycles = ctx->ev_tof.as<int32_t>();
-    a.loss = ctx->ev_loss.as<double>();
-    a.gap = ctx->ev_loss.as<double>() + count;
-    hipLaunchKernelGGL(cx_decompose_kernel, dim3((unsigned)((count + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, a);
-    HIP_TRY(hipGetLastError());
-    if (x_out) HIP_TRY(hipMemcpyAsync(x_out, a.x_out, (size_t)count * 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (cycles) HIP_TRY(hipMemcpyAsync(cycles, a.cycles, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (loss) HIP_TRY(hipMemcpyAsync(loss, a.loss, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (gap) HIP_TRY(hipMemcpyAsync(gap, a.gap, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SLAM_OK;
+    return run_closed_form(
+        ctx, first, count, cx_decompose_kernel, table, kCxTable, [family](CxArgs& a, const double* t) { a.table = t, a.family = family; }, x_out,
+        cycles, loss, gap);
 }
 
 int slam_sqiswap_decompose(slam_ctx* ctx, int64_t first, int64_t count, double* x_out, int32_t* cycles, double* loss, double* gap) {
-    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
-    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
-    if (count == 0) return SLAM_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->ev_grad.reserve((size_t)count * 24 * sizeof(double)));  // the rows
-    HIP_TRY(ctx->ev_loss.reserve((size_t)count * 2 * sizeof(double)));   // losses, then gaps
-    HIP_TRY(ctx->ev_tof.reserve((size_t)count * sizeof(int32_t)));       // sizes
-    AnalyticArgs a{};
-    a.targets = ctx->targets.as<double>() + first * 32;
-    a.M = count;
-    a.x_out = ctx->ev_grad.as<double>();
-    a.cycles = ctx->ev_tof.as<int32_t>();
-    a.loss = ctx->ev_loss.as<double>();
-    a.gap = ctx->ev_loss.as<double>() + count;
-    hipLaunchKernelGGL(sqiswap_decompose_kernel, dim3((unsigned)((count + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, a);
-    HIP_TRY(hipGetLastError());
-    if (x_out) HIP_TRY(hipMemcpyAsync(x_out, a.x_out, (size_t)count * 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (cycles) HIP_TRY(hipMemcpyAsync(cycles, a.cycles, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (loss) HIP_TRY(hipMemcpyAsync(loss, a.loss, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (gap) HIP_TRY(hipMemcpyAsync(gap, a.gap, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SLAM_OK;
+    return run_closed_form(ctx, first, count, sqiswap_decompose_kernel, nullptr, 0, [](AnalyticArgs&, const double*) {}, x_out, cycles, loss, gap);
 }
 
 }  // extern "C"

@@ -16,16 +16,17 @@
 // f = fold(c - s) has the largest margin (f1 - f2) - |f3| is taken (the lowest index among equals; the margin is never negative), V(f)
 // is built as above and aligned to CAN(c - s) by the KAK forms of both, CAN(c - s) ~ L1 V R1, so that with T = e^{i .} A CAN(c) B
 //     T ~ (A L1) S C S (R1 Ls) S (Rs B).
-// With two gates V(fold(c)) is aligned to T itself: T ~ L V R.  An alignment is that of complete_locals_kernel (slam_kak.hpp): the
-// mirror image of V's chamber point is taken where it is closer; `gap` is the distance that remains -- the error of the interior
-// formula, which is the only inexact step (sqrt(ulp) where an arccos argument reaches +-1: on chamber faces).
+// With two gates V(fold(c)) is aligned to T itself: T ~ L V R.  An alignment is kak_align (slam_kak.hpp): the mirror image of V's
+// chamber point is taken where it is closer; `gap` is the distance that remains -- the error of the interior formula, which is the
+// only inexact step (sqrt(ulp) where an arccos argument reaches +-1: on chamber faces).
 //
 // The size is that of span_rules.minimal_span, never below 2: |z| <= x - y + 2e-8 on coordinates rounded to 8 digits.  Local targets
 // and targets of S's own class get a valid two-gate circuit.
 //
-// One thread per target, fp64.  The KAK decompositions of T, V and CAN(c - s) go through ONE inlined copy of kak_decompose in a loop of
-// at most three steps (the step is wave-uniform); the template rows pass through x_out, read back by template_forward as
-// complete_locals_kernel does.
+// One thread per target, fp64.  kak_decompose is inlined once: the KAK forms of T, V and CAN(c - s) come from a loop of at most three
+// steps (the step is wave-uniform); the template rows pass through x_out, read back by template_forward.  The alignment and the loss
+// are the shared steps of slam_kak.hpp (kak_align, template_loss); the exterior layers are written out here, because those of three
+// gates multiply the placement's local gates into the same four products that two gates use as they are.
 #pragma once
 #include "slam_kak.hpp"
 
@@ -143,14 +144,6 @@ __device__ inline void analytic_can(const double (&c)[3], double (&u)[32]) {
     u[24] = o0.re; u[25] = o0.im; u[30] = d0.re; u[31] = d0.im;   // row 3: columns 0, 3
 }
 
-__device__ __forceinline__ void analytic_put(const cplx (&m)[2][2], double* __restrict__ p) {
-    double ang[3];
-    u3_angles(m, ang);
-    p[0] = ang[0];
-    p[1] = ang[1];
-    p[2] = ang[2];
-}
-
 __global__ __launch_bounds__(kKakBlock) void sqiswap_decompose_kernel(AnalyticArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.M) return;
@@ -225,12 +218,10 @@ __global__ __launch_bounds__(kKakBlock) void sqiswap_decompose_kernel(AnalyticAr
     }
     // align V to T (two gates) or to CAN(c - s) (three): the side to align to is `kr`
     if (k == 2) kr = kt;
-    const double d0 = fmax(fmax(fabs(kv.c[0] - kr.c[0]), fabs(kv.c[1] - kr.c[1])), fabs(kv.c[2] - kr.c[2]));
-    const double d1 = fmax(fmax(fabs(1.0 - kv.c[0] - kr.c[0]), fabs(kv.c[1] - kr.c[1])), fabs(-kv.c[2] - kr.c[2]));
-    if (d1 < d0) kak_mirror(kv);
-    a.gap[i] = fmin(d0, d1);
+    a.gap[i] = kak_align(kv, kr);
     a.cycles[i] = k;
-    // L = A A_V^+, R = B_V^+ B; index 1 of a pair acts on qubit 1 (angles 3..5 of a layer), index 2 on qubit 0
+    // L = A A_V^+, R = B_V^+ B; index 1 of a pair acts on qubit 1 (angles 3..5 of a layer), index 2 on qubit 0.  Both sizes use the four
+    // products, three gates with further factors, so they are formed once here and not through exterior_layers
     cplx dg[2][2], L1[2][2], L2[2][2], R1[2][2], R2[2][2], m[2][2];
     dagger2(kv.a1, dg);
     mul2(kr.a1, dg, L1);
@@ -244,10 +235,10 @@ __global__ __launch_bounds__(kKakBlock) void sqiswap_decompose_kernel(AnalyticAr
 #pragma unroll
     for (int j = 0; j < 6; ++j) mid[j] = xo[6 + j];
     if (k == 2) {
-        analytic_put(R2, xo);
-        analytic_put(R1, xo + 3);
-        analytic_put(L2, xo + 12);
-        analytic_put(L1, xo + 15);
+        put_u3(R2, xo);
+        put_u3(R1, xo + 3);
+        put_u3(L2, xo + 12);
+        put_u3(L1, xo + 15);
 #pragma unroll
         for (int j = 18; j < 24; ++j) xo[j] = 0.0;
     } else {
@@ -256,36 +247,25 @@ __global__ __launch_bounds__(kKakBlock) void sqiswap_decompose_kernel(AnalyticAr
         // layer 0 = Rs B_T = (p^+ g^+ B1) (x) (g^+ B2)
         dagger2(g, dg);
         mul2(dg, kt.b2, m);
-        analytic_put(m, xo);
+        put_u3(m, xo);
         dagger2(gp, dg);
         mul2(dg, kt.b1, m);
-        analytic_put(m, xo + 3);
+        put_u3(m, xo + 3);
         // layer 1 = R1 Ls = (R1 g p) (x) (R2 g)
         mul2(R2, g, m);
-        analytic_put(m, xo + 6);
+        put_u3(m, xo + 6);
         mul2(R1, gp, m);
-        analytic_put(m, xo + 9);
+        put_u3(m, xo + 9);
 #pragma unroll
         for (int j = 0; j < 6; ++j) xo[12 + j] = mid[j];
         // layer 3 = A_T L1
         mul2(kt.a2, L2, m);
-        analytic_put(m, xo + 18);
+        put_u3(m, xo + 18);
         mul2(kt.a1, L1, m);
-        analytic_put(m, xo + 21);
+        put_u3(m, xo + 21);
     }
-    // the loss of the written row, from a forward pass of its own: 1 - |Tr(T^+ W(x_out))| / 4
     fw.k = k;
-    template_forward(fw, xo, wr, wi);
-    double tr = 0.0, ti = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const double t_re = T[(r * 4 + c) * 2], t_im = T[(r * 4 + c) * 2 + 1];
-            tr += t_re * wr[r][c] + t_im * wi[r][c];
-            ti += t_re * wi[r][c] - t_im * wr[r][c];
-        }
-    a.loss[i] = 1.0 - 0.25 * sqrt(tr * tr + ti * ti);
+    a.loss[i] = template_loss(fw, T, xo, wr, wi);
 }
 
 }  // namespace slamdev

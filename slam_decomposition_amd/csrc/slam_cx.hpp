@@ -18,15 +18,16 @@
 // and a circuit of C-gates is one of G-gates with r^+ on the left and l^+ on the right of every interior layer.  Only the INTERIOR
 // layers are computed this way: each is L rot(axis, angle) R on either qubit, with L, R, the axis and the angle's index in a table of
 // six entries that the host folds from the factors above (CxEntry; slam_analytic.hip).  The exterior layers come from aligning the
-// interior circuit W (evaluated through G itself by template_forward) with the target, as complete_locals_kernel does: KAK forms of
-// both, the mirror image of W's chamber point where it is closer; `gap` is the distance that remains -- rounding for three gates, the
-// target's distance from the c3 = 0 face (two gates) or from the gate's class (one gate) otherwise, at most the size rule's tolerance.
+// interior circuit W (evaluated through G itself by template_forward) with the target: KAK forms of both, then kak_align and
+// exterior_layers (slam_kak.hpp); `gap` is the distance that remains -- rounding for three gates, the target's distance from the
+// c3 = 0 face (two gates) or from the gate's class (one gate) otherwise, at most the size rule's tolerance.
 //
 // The size is that of span_rules.minimal_span for the family on coordinates rounded to 8 digits, tolerance 2e-8: 1 in the gate's own
 // class, 2 where |c3| < 2e-8, else 3; a local target gets a valid two-gate circuit.
 //
-// One thread per target, fp64.  The KAK decompositions of T and W go through ONE inlined copy of kak_decompose in a loop of two steps
-// (the step is wave-uniform); the rows pass through x_out, read back by template_forward.
+// One thread per target, fp64.  kak_decompose is inlined once: the KAK forms of T and W come from a loop of two steps (the step is
+// wave-uniform); the rows pass through x_out, read back by template_forward.  Everything after the interior layers and the size rule
+// is the shared epilogue of slam_kak.hpp (kak_align, exterior_layers, template_loss).
 #pragma once
 #include "slam_kak.hpp"
 
@@ -51,18 +52,11 @@ struct CxArgs {
     double* gap;            // [M]
 };
 
-__device__ __forceinline__ void cx_load2(const double* __restrict__ p, cplx (&m)[2][2]) {
-    m[0][0] = {p[0], p[1]};
-    m[0][1] = {p[2], p[3]};
-    m[1][0] = {p[4], p[5]};
-    m[1][1] = {p[6], p[7]};
-}
-
 // the three U3 angles of L rot(axis, t) R
 __device__ inline void cx_interior(const double* __restrict__ e, const double (&ang)[3], double* __restrict__ p) {
     cplx L[2][2], R[2][2], r[2][2], lr[2][2], m[2][2];
-    cx_load2(e, L);
-    cx_load2(e + 8, R);
+    load2(e, L);
+    load2(e + 8, R);
     const int axis = (int)e[16], src = (int)e[17];
     const double t = src == 0 ? ang[0] : (src == 1 ? ang[1] : ang[2]);
     double s, c;
@@ -74,11 +68,7 @@ __device__ inline void cx_interior(const double* __restrict__ e, const double (&
     r[1][0] = {axis == 2 ? s : 0.0, axis == 1 ? -s : 0.0};
     mul2(L, r, lr);
     mul2(lr, R, m);
-    double a3[3];
-    u3_angles(m, a3);
-    p[0] = a3[0];
-    p[1] = a3[1];
-    p[2] = a3[2];
+    put_u3(m, p);
 }
 
 __global__ __launch_bounds__(kKakBlock) void cx_decompose_kernel(CxArgs a) {
@@ -138,43 +128,10 @@ __global__ __launch_bounds__(kKakBlock) void cx_decompose_kernel(CxArgs a) {
                 }
         }
     }
-    const double d0 = fmax(fmax(fabs(kv.c[0] - kt.c[0]), fabs(kv.c[1] - kt.c[1])), fabs(kv.c[2] - kt.c[2]));
-    const double d1 = fmax(fmax(fabs(1.0 - kv.c[0] - kt.c[0]), fabs(kv.c[1] - kt.c[1])), fabs(-kv.c[2] - kt.c[2]));
-    if (d1 < d0) kak_mirror(kv);
-    a.gap[i] = fmin(d0, d1);
+    a.gap[i] = kak_align(kv, kt);
     a.cycles[i] = k;
-    // L = A_T A_W^+ (layer k), R = B_W^+ B_T (layer 0); index 1 of a pair acts on qubit 1 (angles 3..5 of a layer), index 2 on qubit 0
-    cplx dg[2][2], m[2][2];
-    double a3[3];
-    double* top = xo + 6 * k;
-    dagger2(kv.b2, dg);
-    mul2(dg, kt.b2, m);
-    u3_angles(m, a3);
-    xo[0] = a3[0]; xo[1] = a3[1]; xo[2] = a3[2];
-    dagger2(kv.b1, dg);
-    mul2(dg, kt.b1, m);
-    u3_angles(m, a3);
-    xo[3] = a3[0]; xo[4] = a3[1]; xo[5] = a3[2];
-    dagger2(kv.a2, dg);
-    mul2(kt.a2, dg, m);
-    u3_angles(m, a3);
-    top[0] = a3[0]; top[1] = a3[1]; top[2] = a3[2];
-    dagger2(kv.a1, dg);
-    mul2(kt.a1, dg, m);
-    u3_angles(m, a3);
-    top[3] = a3[0]; top[4] = a3[1]; top[5] = a3[2];
-    // the loss of the written row, from a forward pass of its own: 1 - |Tr(T^+ W(x_out))| / 4
-    template_forward(fw, xo, wr, wi);
-    double tr = 0.0, ti = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const double t_re = T[(r * 4 + c) * 2], t_im = T[(r * 4 + c) * 2 + 1];
-            tr += t_re * wr[r][c] + t_im * wi[r][c];
-            ti += t_re * wi[r][c] - t_im * wr[r][c];
-        }
-    a.loss[i] = 1.0 - 0.25 * sqrt(tr * tr + ti * ti);
+    exterior_layers(kv, kt, xo, xo + 6 * k);
+    a.loss[i] = template_loss(fw, T, xo, wr, wi);
 }
 
 }  // namespace slamdev

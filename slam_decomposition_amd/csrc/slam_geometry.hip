@@ -1,12 +1,11 @@
 // slam_geometry.hip -- host side of libslamhip.so, geometry unit: Weyl coordinates, span prediction, coverage and family lookups, the Haar
 // sampler and its selection by template size, parallel-drive coverage samples and region lookups, the KAK decomposition and
-// local-gate completion (slam_weyl.hpp, slam_sampler.hpp, slam_span_sampler.hpp, slam_pd.hpp, slam_kak.hpp).
+// local-gate completion (slam_weyl.hpp, slam_sampler.hpp, slam_span_sampler.hpp, slam_pd.hpp, slam_kak.hpp; their kernels in
+// slam_span_sampler.hpp and slam_geometry_kernels.hpp).
 #include "slam_host.hpp"
 #include "slam_sampler.hpp"
-#include "slam_weyl.hpp"
 #include "slam_span_sampler.hpp"
-#include "slam_pd.hpp"
-#include "slam_kak.hpp"
+#include "slam_geometry_kernels.hpp"
 
 int enqueue_c1c2c3(slam_ctx* c, const double* d_unitaries, int64_t count, int ndigits, double* d_out) {
     hipLaunchKernelGGL(c1c2c3_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_unitaries, count, ndigits, d_out);

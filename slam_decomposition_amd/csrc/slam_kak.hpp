@@ -16,7 +16,8 @@
 //     sum R = 0, hence det O2 = +1 once det O1 = +1 -- no sign is tracked through the fold;
 //   * the mirror c3 < 0 -> (1 - c1, c2, -c3) is a fixed local Clifford on each side:
 //     CAN(c) = -i (iZ (x) iX) CAN(1 - c1, c2, -c3) (iY (x) 1).
-// One thread per matrix, fp64 throughout; bookkeeping like weyl_c1c2c3, not a hot loop.
+// One thread per matrix, fp64 throughout; bookkeeping like weyl_c1c2c3, not a hot loop.  __device__ functions only: kak_kernel and
+// complete_locals_kernel are in slam_geometry_kernels.hpp.
 #pragma once
 #include "slam_weyl.hpp"
 #include "slam_pd.hpp"
@@ -345,14 +346,6 @@ __device__ __forceinline__ void kak_store(const Kak& k, double* __restrict__ o) 
     o[19] = k.c[2];
 }
 
-__global__ __launch_bounds__(kKakBlock) void kak_kernel(const double* __restrict__ U, int64_t M, double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    Kak k;
-    kak_decompose(U + i * 32, k);
-    kak_store(k, out + i * kKakRecord);
-}
-
 // ---------------------------------------------------------------------------------
 // Local-gate completion.  A fit up to single-qubit gates (MakhlinFunctionalCost, or a template without exterior layers) ends at x with
 // W = template(x) = K1 T K2 for unknown local K1, K2.  With the KAK forms of W and T on the same chamber point,
@@ -428,59 +421,58 @@ __device__ inline void u3_angles(const cplx (&m)[2][2], double* __restrict__ p) 
     p[2] = c >= s ? atan2(m[1][1].im, m[1][1].re) - g - p[1] : atan2(-m[0][1].im, -m[0][1].re) - g;
 }
 
-__global__ __launch_bounds__(kKakBlock) void complete_locals_kernel(CompleteArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.M) return;
-    const int n = 6 * (a.k + 1);
-    const double* __restrict__ x = a.x + i * n;
-    double* __restrict__ xo = a.x_out + i * n;
-    const double* __restrict__ T = a.targets + 32 * (int64_t)a.target_of[i];
-    double wr[4][4], wi[4][4], u[32];
-    template_forward(a, x, wr, wi);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            u[(r * 4 + c) * 2] = wr[r][c];
-            u[(r * 4 + c) * 2 + 1] = wi[r][c];
-        }
-    Kak kw, kt;
-    kak_decompose(u, kw);
-    kak_decompose(T, kt);
+// ---------------------------------------------------------------------------------
+// The steps that complete_locals_kernel (slam_geometry_kernels.hpp) and the closed-form kernels (slam_analytic.hpp, slam_cx.hpp,
+// slam_b.hpp) share: a closed-form family computes its interior layers and its size rule, everything after that is here.
+// ---------------------------------------------------------------------------------
+// the three U3 angles of m at p
+__device__ __forceinline__ void put_u3(const cplx (&m)[2][2], double* __restrict__ p) {
+    double ang[3];
+    u3_angles(m, ang);
+    p[0] = ang[0];
+    p[1] = ang[1];
+    p[2] = ang[2];
+}
+
+// a 2x2 complex matrix, row-major (re, im)
+__device__ __forceinline__ void load2(const double* __restrict__ p, cplx (&m)[2][2]) {
+    m[0][0] = {p[0], p[1]};
+    m[0][1] = {p[2], p[3]};
+    m[1][0] = {p[4], p[5]};
+    m[1][1] = {p[6], p[7]};
+}
+
+// Aligns the chamber point of kw with that of kt: the mirror image of kw's is taken where it is closer (max norm).  Returns the
+// distance that remains, the `gap`.
+__device__ __forceinline__ double kak_align(Kak& kw, const Kak& kt) {
     const double d0 = fmax(fmax(fabs(kw.c[0] - kt.c[0]), fabs(kw.c[1] - kt.c[1])), fabs(kw.c[2] - kt.c[2]));
     const double d1 = fmax(fmax(fabs(1.0 - kw.c[0] - kt.c[0]), fabs(kw.c[1] - kt.c[1])), fabs(-kw.c[2] - kt.c[2]));
     if (d1 < d0) kak_mirror(kw);
-    a.gap_out[i] = fmin(d0, d1);
-    // L = A_T A_W^+ (layer k), R = B_W^+ B_T (layer 0); index 1 of a pair acts on qubit 1, index 2 on qubit 0
-    cplx dg[2][2], L1[2][2], L2[2][2], R1[2][2], R2[2][2], u3[2][2], m[2][2];
-    dagger2(kw.a1, dg);
-    mul2(kt.a1, dg, L1);
-    dagger2(kw.a2, dg);
-    mul2(kt.a2, dg, L2);
-    dagger2(kw.b1, dg);
-    mul2(dg, kt.b1, R1);
-    dagger2(kw.b2, dg);
-    mul2(dg, kt.b2, R2);
-    for (int j = 6; j < n - 6; ++j) xo[j] = x[j];
-    double ang[3];
-    u3_matrix(x, u3);
-    mul2(u3, R2, m);
-    u3_angles(m, ang);
-    xo[0] = ang[0]; xo[1] = ang[1]; xo[2] = ang[2];
-    u3_matrix(x + 3, u3);
-    mul2(u3, R1, m);
-    u3_angles(m, ang);
-    xo[3] = ang[0]; xo[4] = ang[1]; xo[5] = ang[2];
-    u3_matrix(x + n - 6, u3);
-    mul2(L2, u3, m);
-    u3_angles(m, ang);
-    xo[n - 6] = ang[0]; xo[n - 5] = ang[1]; xo[n - 4] = ang[2];
-    u3_matrix(x + n - 3, u3);
-    mul2(L1, u3, m);
-    u3_angles(m, ang);
-    xo[n - 3] = ang[0]; xo[n - 2] = ang[1]; xo[n - 1] = ang[2];
-    // the loss of the completed row, from a forward pass of its own: 1 - |Tr(T^+ W(x_out))| / 4
-    template_forward(a, xo, wr, wi);
+    return fmin(d0, d1);
+}
+
+// The exterior layers of a row whose interior circuit W has the KAK form kv, aligned with the target's kt: R = B_W^+ B_T at `bottom`
+// (layer 0), L = A_T A_W^+ at `top` (layer k).  Index 1 of a pair acts on qubit 1 (angles 3..5 of a layer), index 2 on qubit 0.
+__device__ __forceinline__ void exterior_layers(const Kak& kv, const Kak& kt, double* __restrict__ bottom, double* __restrict__ top) {
+    cplx dg[2][2], m[2][2];
+    dagger2(kv.b2, dg);
+    mul2(dg, kt.b2, m);
+    put_u3(m, bottom);
+    dagger2(kv.b1, dg);
+    mul2(dg, kt.b1, m);
+    put_u3(m, bottom + 3);
+    dagger2(kv.a2, dg);
+    mul2(kt.a2, dg, m);
+    put_u3(m, top);
+    dagger2(kv.a1, dg);
+    mul2(kt.a1, dg, m);
+    put_u3(m, top + 3);
+}
+
+// the loss of the row x against the target T, from a forward pass of its own: 1 - |Tr(T^+ W(x))| / 4
+__device__ __forceinline__ double template_loss(const CompleteArgs& fw, const double* __restrict__ T, const double* __restrict__ x,
+                                                double (&wr)[4][4], double (&wi)[4][4]) {
+    template_forward(fw, x, wr, wi);
     double tr = 0.0, ti = 0.0;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -490,7 +482,8 @@ __global__ __launch_bounds__(kKakBlock) void complete_locals_kernel(CompleteArgs
             tr += t_re * wr[r][c] + t_im * wi[r][c];
             ti += t_re * wi[r][c] - t_im * wr[r][c];
         }
-    a.loss_out[i] = 1.0 - 0.25 * sqrt(tr * tr + ti * ti);
+    // tr^2 + ti^2 as the kernels have always formed it: the contraction is spelled out, so that where this is inlined cannot change it
+    return 1.0 - 0.25 * sqrt(fma(tr, tr, ti * ti));
 }
 
 }  // namespace slamdev

@@ -11,6 +11,9 @@
 // (Cardoso-Souloumiac; it degenerates to the classical Jacobi angle for a single matrix) -- robust for the
 // degenerate spectra of CX / iSWAP / SWAP-like gates, where a characteristic-polynomial solver loses half the
 // digits.  Everything is fp64; this is bookkeeping (two calls per target), not a hot loop.
+//
+// __device__ functions only: the kernels over them (c1c2c3_kernel, span_predict_kernel, coverage_lookup_kernel, family_lookup_kernel)
+// are in slam_geometry_kernels.hpp.
 #pragma once
 #include "slam_device.hpp"
 
@@ -157,11 +160,6 @@ __device__ inline void weyl_c1c2c3(const double* __restrict__ Uin, int ndigits, 
     out[2] = c3 + 0.0;
 }
 
-__global__ void c1c2c3_kernel(const double* __restrict__ U, int64_t M, int ndigits, double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < M) weyl_c1c2c3(U + i * 32, ndigits, out + i * 3);
-}
-
 // ---------------------------------------------------------------------------------
 // Span predictor (replaces monodromy_range_from_target, src/slam/utils/polytopes/polytope_wrap.py:39-94, for resident targets): the
 // smallest number of leading gates of a template whose coverage set contains the target.  The host (coverage.py) turns each prefix
@@ -216,14 +214,6 @@ __device__ __forceinline__ int span_classify(const double (&c)[3], const SpanReg
     return local ? 0 : best;
 }
 
-__global__ void span_predict_kernel(const double* __restrict__ U, int64_t M, SpanRegions r, int32_t* __restrict__ spans) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    double c[3];
-    weyl_c1c2c3(U + i * 32, 8, c);
-    spans[i] = span_classify(c, r, r.tol);
-}
-
 // ---------------------------------------------------------------------------------
 // Coverage lookup (the cost side of MixedOrderBasisCircuitTemplate: monodromy_range_from_target over a coverage set sorted by cost,
 // src/slam/utils/polytopes/polytope_wrap.py:39-94, as TemplateOptimizer.cost_from_distribution asks it, src/slam/optimizer.py:156-178):
@@ -237,12 +227,10 @@ __global__ void span_predict_kernel(const double* __restrict__ U, int64_t M, Spa
 // histogram in LDS (bins n_entries + 2: the entries, then local targets, then targets no entry contains) and folds its non-empty
 // bins into `counts` with one 64-bit atomic each; bins beyond the LDS histogram's size go to `counts` directly.
 // ---------------------------------------------------------------------------------
-constexpr int kCoverageBlock = 256;
 // the table is read-only for the whole launch: read through the constant address space, whose loads at a wave-uniform address the
 // compiler issues as scalar loads (a plain global pointer gets vector loads of the same row in every lane)
 template <class T>
 using const_as_ptr = const __attribute__((address_space(4))) T*;
-constexpr int kCoverageLdsBins = 8192;  // 32 KiB of LDS at most: a 26-gate set of three gates (3 653 entries) fits
 
 // the target's side of every row, once per target: Weyl coordinates (8 digits), both alcove points of its class and their 14 subset
 // sums; returns whether the class is local.  Lanes beyond the batch get zeros (they never count).
@@ -300,148 +288,6 @@ __device__ __forceinline__ bool coverage_row_hit(const_as_ptr<int32_t> kkinds, c
         ok1 = ok1 && (sm[1][p] >= lo);
     }
     return ok0 || ok1;
-}
-
-__global__ __launch_bounds__(kCoverageBlock) void coverage_lookup_kernel(
-    const double* __restrict__ U, int64_t M, int32_t n_tables, const int32_t* __restrict__ offsets, const int32_t* __restrict__ kinds,
-    const double* __restrict__ points, const double* __restrict__ bounds, double tol, int32_t lds_bins,
-    unsigned long long* __restrict__ counts, int32_t* __restrict__ entry_out) {
-    extern __shared__ unsigned int hist[];
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < M;
-    double pt[2][4], sm[2][kSpanPatterns];
-    const bool local = coverage_target(U, i, live, pt, sm);
-    const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
-    const const_as_ptr<int32_t> koffsets = (const_as_ptr<int32_t>)offsets;
-    const const_as_ptr<int32_t> kkinds = (const_as_ptr<int32_t>)kinds;
-    const const_as_ptr<double> kpoints = (const_as_ptr<double>)points;
-    const const_as_ptr<double> kbounds = (const_as_ptr<double>)bounds;
-    const int32_t base0 = koffsets[0];
-    for (int32_t t = 0; t < n_tables; ++t) {
-        const int32_t e0 = koffsets[t], e1 = koffsets[t + 1];
-        const int32_t n = e1 - e0;
-        const int32_t nb = n + 2;
-        const int32_t nl = nb < lds_bins ? nb : lds_bins;
-        unsigned long long* __restrict__ cnt = counts + (int64_t)(e0 - base0) + 2 * (int64_t)t;
-        for (int b = threadIdx.x; b < nl; b += blockDim.x) hist[b] = 0u;
-        __syncthreads();
-        bool searching = live && !local;
-        int32_t found = local ? n : n + 1;
-        for (int32_t e = e0; e < e1; ++e) {
-            if (!__any(searching)) break;  // wave-uniform exit: e is the same in every lane
-            const bool hit = coverage_row_hit(kkinds, kpoints, kbounds, e, pt, sm, tol, t1);
-            if (searching && hit) {
-                found = e - e0;
-                searching = false;
-            }
-        }
-        if (live) {
-            if (entry_out) entry_out[(int64_t)t * M + i] = found;
-            if (found < nl)
-                atomicAdd(&hist[found], 1u);
-            else
-                atomicAdd(&cnt[found], 1ull);
-        }
-        __syncthreads();
-        for (int b = threadIdx.x; b < nl; b += blockDim.x) {
-            const unsigned int v = hist[b];
-            if (v) atomicAdd(&cnt[b], (unsigned long long)v);
-        }
-        __syncthreads();  // the next table clears the histogram
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// Family lookup (recursive_sibling_check, src/slam/utils/gates/family_extend.py:17-117, for every resident target): a gate family is
-// a base pulse and the same pulse run r = 2^a 3^b times as long ("older siblings"); member m has one table of rows k = 1, 2, ...
-// (k applications of it, rows as above) and the cost of row k is (k + 1) cost_1q + k duration_m, computed by the host and read here.
-// The walk starts at member 0, finds the first row k of the member that contains the target, and moves on to child_even[m] (k even)
-// or child_odd[m] (k odd) until k = 1, the child is missing or the child does not contain the target; unwinding, a level keeps its
-// child's result only where that is STRICTLY cheaper.  That unwind is a minimum over the visited levels with ties to the shallower
-// one, so one running record (cost, member, k) replaces the per-level records: a level replaces it iff it is strictly cheaper.
-// policy 1 ("best") visits every member instead of one path; ties go to the smaller member index by the same rule.
-// Children have larger indices than their parents (checked by the host), so ONE ascending pass over the members serves every lane's
-// path: lanes whose walk is not at member m idle during m, the row index stays wave-uniform, and the rows arrive by scalar loads as
-// in coverage_lookup_kernel.  Two histograms per block in LDS -- all rows + local + unreachable, and member 0's alone (the cost
-// without the family, from the same pass) -- folded into global memory with one 64-bit atomic per non-empty bin.
-// ---------------------------------------------------------------------------------
-constexpr int kFamilyMaxMembers = 32;
-constexpr int kFamilyMaxBins = 8192;  // E + 2 + E_0 + 2 bins of LDS at most (32 KiB)
-
-__global__ __launch_bounds__(kCoverageBlock) void family_lookup_kernel(
-    const double* __restrict__ U, int64_t M, int32_t n_members, const int32_t* __restrict__ offsets, const int32_t* __restrict__ kinds,
-    const double* __restrict__ points, const double* __restrict__ bounds, const double* __restrict__ costs,
-    const int32_t* __restrict__ child_even, const int32_t* __restrict__ child_odd, double tol, int32_t policy,
-    unsigned long long* __restrict__ counts, unsigned long long* __restrict__ base_counts, int32_t* __restrict__ member_out,
-    int32_t* __restrict__ gates_out) {
-    extern __shared__ unsigned int hist[];
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < M;
-    double pt[2][4], sm[2][kSpanPatterns];
-    const bool local = coverage_target(U, i, live, pt, sm);
-    const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
-    const const_as_ptr<int32_t> koffsets = (const_as_ptr<int32_t>)offsets;
-    const const_as_ptr<int32_t> kkinds = (const_as_ptr<int32_t>)kinds;
-    const const_as_ptr<double> kpoints = (const_as_ptr<double>)points;
-    const const_as_ptr<double> kbounds = (const_as_ptr<double>)bounds;
-    const const_as_ptr<double> kcosts = (const_as_ptr<double>)costs;
-    const const_as_ptr<int32_t> keven = (const_as_ptr<int32_t>)child_even;
-    const const_as_ptr<int32_t> kodd = (const_as_ptr<int32_t>)child_odd;
-    const int32_t E = koffsets[n_members], E0 = koffsets[1];
-    const int32_t n_bins = E + 2 + E0 + 2;  // <= kFamilyMaxBins (host)
-    for (int b = threadIdx.x; b < n_bins; b += blockDim.x) hist[b] = 0u;
-    __syncthreads();
-    int32_t cur = (live && !local) ? 0 : -1;  // reference policy: the member the walk is at (-1: over)
-    bool reachable = live && !local;            // member 0 contains the target (decided at m = 0)
-    double best_cost = __builtin_inf();
-    int32_t best_row = -1, best_m = -1, best_k = -1, base_k = 0;
-    for (int32_t m = 0; m < n_members; ++m) {
-        const int32_t e0 = koffsets[m], e1 = koffsets[m + 1];
-        const bool active = policy ? reachable : (cur == m);
-        bool searching = active;
-        int32_t k = 0;
-        for (int32_t e = e0; e < e1; ++e) {
-            if (!__any(searching)) break;  // wave-uniform exit: e is the same in every lane
-            const bool hit = coverage_row_hit(kkinds, kpoints, kbounds, e, pt, sm, tol, t1);
-            if (searching && hit) {
-                k = e - e0 + 1;
-                searching = false;
-            }
-        }
-        if (!__any(active)) continue;
-        const int32_t ce = keven[m], co = kodd[m];
-        if (active) {
-            if (k > 0) {
-                const double c = kcosts[e0 + k - 1];  // (per-lane row: a vector load of eight bytes)
-                if (c < best_cost) {
-                    best_cost = c;
-                    best_row = e0 + k - 1;
-                    best_m = m;
-                    best_k = k;
-                }
-                cur = k == 1 ? -1 : ((k & 1) ? co : ce);
-            } else {
-                cur = -1;
-            }
-            if (m == 0) {
-                base_k = k;
-                reachable = k > 0;
-            }
-        }
-    }
-    if (live) {
-        const int32_t bin = local ? E : (best_row >= 0 ? best_row : E + 1);
-        const int32_t bin0 = local ? E0 : (base_k > 0 ? base_k - 1 : E0 + 1);
-        atomicAdd(&hist[bin], 1u);
-        atomicAdd(&hist[E + 2 + bin0], 1u);
-        if (member_out) member_out[i] = local ? -1 : best_m;
-        if (gates_out) gates_out[i] = local ? 0 : best_k;
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < n_bins; b += blockDim.x) {
-        const unsigned int v = hist[b];
-        if (v) atomicAdd(b < E + 2 ? &counts[b] : &base_counts[b - (E + 2)], (unsigned long long)v);
-    }
 }
 
 }  // namespace slamdev

@@ -25,14 +25,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from closed_form_ref import SIZE_TOL, _PP, _X, _Y, _Z, can, fold_chamber, loss, u3, u3_angles, up_to_phase  # noqa: F401 (re-exported)
 from slam_decomposition_amd import weyl
 
-_X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
-_Y = np.array([[0, -1j], [1j, 0]], dtype=np.complex128)
-_Z = np.array([[1, 0], [0, -1]], dtype=np.complex128)
-_PP = [np.kron(p, p) for p in (_X, _Y, _Z)]
 S = np.array([[1, 0, 0, 0], [0, np.sqrt(0.5), 1j * np.sqrt(0.5), 0], [0, 1j * np.sqrt(0.5), np.sqrt(0.5), 0], [0, 0, 0, 1]], dtype=np.complex128)
-SIZE_TOL = 2e-8  # span_rules._TOL: the size rule is evaluated on coordinates rounded to 8 digits
 
 # the 12 signed placements of (1/4, 1/4, 0): positions (0, 1), (0, 2), (1, 2) times signs ++, +-, -+, --
 SHIFTS = np.zeros((12, 3))
@@ -40,28 +36,6 @@ for _p, (_i, _j) in enumerate(((0, 1), (0, 2), (1, 2))):
     for _s, (_a, _b) in enumerate(((1, 1), (1, -1), (-1, 1), (-1, -1))):
         SHIFTS[4 * _p + _s, _i] = 0.25 * _a
         SHIFTS[4 * _p + _s, _j] = 0.25 * _b
-
-
-def can(c) -> np.ndarray:
-    out = np.eye(4, dtype=np.complex128)
-    for j in range(3):
-        a = 0.5 * np.pi * c[j]
-        out = out @ (np.cos(a) * np.eye(4) + 1j * np.sin(a) * _PP[j])
-    return out
-
-
-def u3(t, p, l) -> np.ndarray:
-    c, s = np.cos(0.5 * t), np.sin(0.5 * t)
-    return np.array([[c, -np.exp(1j * l) * s], [np.exp(1j * p) * s, np.exp(1j * (p + l)) * c]])
-
-
-def u3_angles(m):
-    """(theta, phi, lam) with m = e^{i g} U3(theta, phi, lam)."""
-    c, s = abs(m[0, 0]), abs(m[1, 0])
-    g = np.angle(m[0, 0]) if c > 0 else 0.0
-    phi = (np.angle(m[1, 0]) if s > 0 else 0.0) - g
-    lam = np.angle(m[1, 1]) - g - phi if c >= s else np.angle(-m[0, 1]) - g
-    return 2.0 * np.arctan2(s, c), phi, lam
 
 
 def template(x, k) -> np.ndarray:
@@ -85,15 +59,6 @@ def fold(c) -> np.ndarray:
     a = -np.sort(-np.abs(r), axis=-1)
     a[..., 2] = np.where(neg, -a[..., 2], a[..., 2])
     return a
-
-
-def fold_chamber(c) -> np.ndarray:
-    """(c1, c2, c3) with c3 >= 0 (as c1c2c3 returns them) -> c1 <= 1/2, c3 of either sign."""
-    c = np.array(c, dtype=np.float64, copy=True)
-    m = c[..., 0] > 0.5
-    c[..., 0] = np.where(m, 1.0 - c[..., 0], c[..., 0])
-    c[..., 2] = np.where(m, -c[..., 2], c[..., 2])
-    return c
 
 
 def size(c8) -> np.ndarray:
@@ -199,15 +164,6 @@ def decompose(T):
         (s1, s2), (t1, t2) = shift_locals(i)
         x = np.r_[_layer_angles(t1 @ kt[4], t2 @ kt[5]), _layer_angles(R1 @ s1, R2 @ s2), mid, _layer_angles(kt[1] @ L1, kt[2] @ L2)]
     return k, x, template(x, k), float(gap), u
-
-
-def loss(T, W) -> float:
-    return float(1.0 - abs(np.trace(np.conj(T).T @ W)) / 4.0)
-
-
-def up_to_phase(T, W) -> float:
-    tr = np.trace(np.conj(W).T @ T)
-    return float(np.max(np.abs(T - tr / abs(tr) * W)))
 
 
 def _named():

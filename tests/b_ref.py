@@ -25,13 +25,10 @@ from __future__ import annotations
 import numpy as np
 
 import kak_ref as kr
+from closed_form_ref import SIZE_TOL, _I, _X, _Y, _Z, dress, template, u3, u3_angles, up_to_phase  # noqa: F401 (re-exported)
+from closed_form_ref import fold_chamber as fold, loss as loss_of  # noqa: F401 (this module's names for them)
 from slam_decomposition_amd import weyl
 
-_I = np.eye(2, dtype=np.complex128)
-_X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
-_Y = np.array([[0, -1j], [1j, 0]], dtype=np.complex128)
-_Z = np.array([[1, 0], [0, -1]], dtype=np.complex128)
-SIZE_TOL = 2e-8  # span_rules._TOL: the size rule is evaluated on coordinates rounded to 8 digits
 POINT = (0.5, 0.25, 0.0)
 
 
@@ -51,15 +48,6 @@ def rp(p, t) -> np.ndarray:
     return np.cos(0.5 * t) * _I + 1j * np.sin(0.5 * t) * p
 
 
-def fold(c) -> np.ndarray:
-    """(c1, c2, c3) with c3 >= 0 (as c1c2c3 returns them) -> c1 <= 1/2, c3 of either sign."""
-    c = np.array(c, dtype=np.float64, copy=True)
-    m = c[..., 0] > 0.5
-    c[..., 0] = np.where(m, 1.0 - c[..., 0], c[..., 0])
-    c[..., 2] = np.where(m, -c[..., 2], c[..., 2])
-    return c
-
-
 def angles(c):
     """(by, bz) for a FOLDED point c (units of pi)."""
     c1, c2 = np.pi * c[0], np.pi * c[1]
@@ -73,32 +61,6 @@ def interior(c):
     """(q1, q0): the interior layer kron(q1, q0) of B K B ~ CAN(c) for a FOLDED point c."""
     by, bz = angles(c)
     return rp(_Y, np.pi * c[2]), rp(_Z, bz) @ rp(_Y, by) @ rp(_Z, bz)
-
-
-def u3(t, p, l) -> np.ndarray:
-    c, s = np.cos(0.5 * t), np.sin(0.5 * t)
-    return np.array([[c, -np.exp(1j * l) * s], [np.exp(1j * p) * s, np.exp(1j * (p + l)) * c]])
-
-
-def u3_angles(m):
-    """(theta, phi, lam) with m = e^{i g} U3(theta, phi, lam)."""
-    c, s = abs(m[0, 0]), abs(m[1, 0])
-    g = np.angle(m[0, 0]) if c > 0 else 0.0
-    phi = (np.angle(m[1, 0]) if s > 0 else 0.0) - g
-    lam = np.angle(m[1, 1]) - g - phi if c >= s else np.angle(-m[0, 1]) - g
-    return 2.0 * np.arctan2(s, c), phi, lam
-
-
-def template(x, G, k) -> np.ndarray:
-    """K_k G K_{k-1} ... G K_0 of a row of 6 (k + 1) angles, K = U3(qubit 1) (x) U3(qubit 0)."""
-    x = np.asarray(x, dtype=np.float64)
-    W = np.eye(4, dtype=np.complex128)
-    for j in range(k + 1):
-        if j:
-            W = G @ W
-        p = x[6 * j:6 * j + 6]
-        W = np.kron(u3(*p[3:6]), u3(*p[0:3])) @ W
-    return W
 
 
 def expected_size(T) -> np.ndarray:
@@ -139,15 +101,6 @@ def gate_factors(G):
     return _GATE_CACHE[key]
 
 
-def loss_of(T, W) -> float:
-    return float(1.0 - abs(np.trace(np.conj(T).T @ W)) / 4.0)
-
-
-def up_to_phase(T, W) -> float:
-    tr = np.trace(np.conj(W).T @ T)
-    return float(np.max(np.abs(T - tr / abs(tr) * W)))
-
-
 def decompose(T, G):
     """(x, cycles, loss, gap) for the 4x4 unitary T and a gate G of the B class: the 6 (cycles + 1) angles of a circuit of G-gates, the
     BasicCost loss of ``template(x, G, cycles)`` against T and the chamber distance left by the alignment of the interior circuit."""
@@ -168,14 +121,6 @@ def decompose(T, G):
     layers = [Rw] + layers + [Lw]
     x = np.array([a for q1, q0 in layers for a in list(u3_angles(q0)) + list(u3_angles(q1))])
     return x, k, loss_of(T, template(x, G, k)), gap
-
-
-def dress(rng, W, n=None):
-    """e^{i phi} (L1 (x) L2) W (R1 (x) R2) with random SU(2) factors and phases: n matrices (or one)."""
-    m = 1 if n is None else n
-    ph = np.exp(1j * rng.uniform(0, 2 * np.pi, m))[:, None, None]
-    out = ph * (kr.kron2(kr.random_su2(rng, m), kr.random_su2(rng, m)) @ W @ kr.kron2(kr.random_su2(rng, m), kr.random_su2(rng, m)))
-    return out[0] if n is None else out
 
 
 def _named():

@@ -30,13 +30,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from closed_form_ref import (SIZE_TOL, _I, _PP, _X, _Y, _Z, can, dress, fold_chamber, loss, template, u3, u3_angles,  # noqa: F401 (re-exported)
+                             up_to_phase)
 from slam_decomposition_amd import weyl
 
-_I = np.eye(2, dtype=np.complex128)
-_X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
-_Y = np.array([[0, -1j], [1j, 0]], dtype=np.complex128)
-_Z = np.array([[1, 0], [0, -1]], dtype=np.complex128)
-_PP = [np.kron(p, p) for p in (_X, _Y, _Z)]
 _P0 = np.diag([1.0, 0.0]).astype(np.complex128)
 _P1 = np.diag([0.0, 1.0]).astype(np.complex128)
 CX12 = np.kron(_P0, _I) + np.kron(_P1, _X)
@@ -45,20 +42,11 @@ CZ = np.diag([1, 1, 1, -1]).astype(np.complex128)
 SWAP = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], dtype=np.complex128)
 ISWAP = np.array([[1, 0, 0, 0], [0, 0, 1j, 0], [0, 1j, 0, 0], [0, 0, 0, 1]], dtype=np.complex128)
 SQISWAP = np.array([[1, 0, 0, 0], [0, np.sqrt(0.5), 1j * np.sqrt(0.5), 0], [0, 1j * np.sqrt(0.5), np.sqrt(0.5), 0], [0, 0, 0, 1]], dtype=np.complex128)
-SIZE_TOL = 2e-8  # span_rules._TOL: the size rule is evaluated on coordinates rounded to 8 digits
 CLASSES = ((0.5, 0.0, 0.0), (0.5, 0.5, 0.0))  # family 0: CNOT, family 1: iSWAP
 
 
 def rot(p, t) -> np.ndarray:
     return np.cos(0.5 * t) * _I - 1j * np.sin(0.5 * t) * p
-
-
-def can(c) -> np.ndarray:
-    out = np.eye(4, dtype=np.complex128)
-    for j in range(3):
-        a = 0.5 * np.pi * c[j]
-        out = out @ (np.cos(a) * np.eye(4) + 1j * np.sin(a) * _PP[j])
-    return out
 
 
 def V3(t) -> np.ndarray:
@@ -71,41 +59,6 @@ def V2(a, b) -> np.ndarray:
 
 def sw(K) -> np.ndarray:
     return SWAP @ K @ SWAP
-
-
-def u3(t, p, l) -> np.ndarray:
-    c, s = np.cos(0.5 * t), np.sin(0.5 * t)
-    return np.array([[c, -np.exp(1j * l) * s], [np.exp(1j * p) * s, np.exp(1j * (p + l)) * c]])
-
-
-def u3_angles(m):
-    """(theta, phi, lam) with m = e^{i g} U3(theta, phi, lam)."""
-    c, s = abs(m[0, 0]), abs(m[1, 0])
-    g = np.angle(m[0, 0]) if c > 0 else 0.0
-    phi = (np.angle(m[1, 0]) if s > 0 else 0.0) - g
-    lam = np.angle(m[1, 1]) - g - phi if c >= s else np.angle(-m[0, 1]) - g
-    return 2.0 * np.arctan2(s, c), phi, lam
-
-
-def template(x, G, k) -> np.ndarray:
-    """K_k G K_{k-1} ... G K_0 of a row of 6 (k + 1) angles, K = U3(qubit 1) (x) U3(qubit 0)."""
-    x = np.asarray(x, dtype=np.float64)
-    W = np.eye(4, dtype=np.complex128)
-    for j in range(k + 1):
-        if j:
-            W = G @ W
-        p = x[6 * j:6 * j + 6]
-        W = np.kron(u3(*p[3:6]), u3(*p[0:3])) @ W
-    return W
-
-
-def fold_chamber(c) -> np.ndarray:
-    """(c1, c2, c3) with c3 >= 0 (as c1c2c3 returns them) -> c1 <= 1/2, c3 of either sign."""
-    c = np.array(c, dtype=np.float64, copy=True)
-    m = c[..., 0] > 0.5
-    c[..., 0] = np.where(m, 1.0 - c[..., 0], c[..., 0])
-    c[..., 2] = np.where(m, -c[..., 2], c[..., 2])
-    return c
 
 
 def family_of(G) -> int:
@@ -209,25 +162,6 @@ def decompose(T, G):
             Ks = [Ks[0], sw(Ks[1])]
     x = np.array([a for K in Ks for a in _layer(K)])
     return k, x, template(x, G, k), gap
-
-
-def loss(T, W) -> float:
-    return float(1.0 - abs(np.trace(np.conj(T).T @ W)) / 4.0)
-
-
-def up_to_phase(T, W) -> float:
-    tr = np.trace(np.conj(W).T @ T)
-    return float(np.max(np.abs(T - tr / abs(tr) * W)))
-
-
-def dress(rng, W, n=None):
-    """e^{i phi} (L1 (x) L2) W (R1 (x) R2) with random SU(2) factors and phases: n matrices (or one)."""
-    import kak_ref as kr
-
-    m = 1 if n is None else n
-    ph = np.exp(1j * rng.uniform(0, 2 * np.pi, m))[:, None, None]
-    out = ph * (kr.kron2(kr.random_su2(rng, m), kr.random_su2(rng, m)) @ W @ kr.kron2(kr.random_su2(rng, m), kr.random_su2(rng, m)))
-    return out[0] if n is None else out
 
 
 def _named():
