@@ -150,6 +150,10 @@ class OptParams(C.Structure):
         super().__init__(int(restarts), int(maxiter), float(gtol), float(stop_loss), int(seed) & 0xFFFFFFFFFFFFFFFF,
                          int(flags), int(items_per_quad), float(gtol_far), float(far_loss), int(target_base))
 
+    def replace(self, **changes) -> "OptParams":
+        """A copy with every field carried over and the named ones changed."""
+        return OptParams(**{**{name: getattr(self, name) for name, _ in self._fields_}, **changes})
+
 
 class V2Gate(C.Structure):
     """``slam_v2_gate``: raw angles (a, phi_c, b, phi_g)[r] = scale[r] * q[sel[r]] + offset[r] of a conversion-gain gate."""
@@ -422,6 +426,12 @@ class ResultPool:
 PinnedPool = ResultPool  # (name of the first version, tests)
 result_pool = ResultPool(pinned=True)      # ONE blocking call alone on the device (``pinned=True`` below)
 pageable_pool = ResultPool(pinned=False)   # everything else
+
+
+def _result_triple(new, count: int, width: int):
+    """``(best_loss [count], best_x [count, width], best_cycles [count])`` of a span loop from the allocator ``new``
+    (``result_pool.empty`` / ``pageable_pool.empty``)."""
+    return new(count, np.float64), new((count, width), np.float64), new(count, np.int32)
 
 
 class KakResult(NamedTuple):
@@ -954,6 +964,47 @@ class Context:
         return w.view(np.complex128).reshape(M, 4, 4), loss
 
     # -- one span stage ----------------------------------------------------
+    def _stage_call(self, fn, qn: int, gate_seq, params: OptParams, active, x0, vecs=(), exit_loss=None, trace_cap=None,
+                    want_items: bool = True) -> dict:
+        """The one marshalling routine of the six stage entry points: ``fn(ctx, k, gate_seq, active, na, x0, *vecs, params,
+        [exit_loss], [trace_cap], outputs...)`` for a template of n = 6 (k + 1) + ``qn`` k parameters.  ``vecs``: the four per-parameter
+        vectors of the V2 / smush forms (each may be None).  The outputs go to the library in the order of the returned dictionary:
+        ``best_loss`` [na], ``best_x`` [na, n], ``best_restart`` [na], the per-item arrays [na, R] (None without ``want_items``;
+        ``item_evals`` only without a trace), then -- with ``trace_cap`` -- ``trace_loss`` [na, R, cap] and ``trace_x`` [na, R, cap, n]."""
+        k = len(gate_seq)
+        n = 6 * (k + 1) + qn * k
+        gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.int32)
+            na = active.shape[0]
+        else:
+            na = self.n_targets
+        R = int(params.restarts)
+        vecs = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in vecs]
+        for v in vecs:
+            if v is not None and v.shape != (n,):
+                raise ValueError(f"per-parameter arrays must have shape [{n}]")
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (na, R, n):
+                raise ValueError(f"x0 must have shape [{na}, {R}, {n}]")
+        out = {"best_loss": np.empty(na, dtype=np.float64), "best_x": np.empty((na, n), dtype=np.float64),
+               "best_restart": np.empty(na, dtype=np.int32)}
+        per_item = {"item_loss": np.float64, "item_iters": np.int32, "item_status": np.int32}
+        if trace_cap is None:
+            per_item["item_evals"] = np.int32
+        for key, dtype in per_item.items():
+            out[key] = np.empty((na, R), dtype=dtype) if want_items else None
+        scalars = [] if exit_loss is None else [float(exit_loss)]
+        if trace_cap is not None:
+            cap = int(trace_cap)
+            scalars.append(cap)
+            out["trace_loss"] = np.empty((na, R, cap), dtype=np.float64)
+            out["trace_x"] = np.empty((na, R, cap, n), dtype=np.float64)
+        _check(fn(self._h, k, _ptr(gs), _ptr(active), na, _ptr(x0), *[_ptr(v) for v in vecs], C.byref(params), *scalars,
+                  *[_ptr(a) for a in out.values()]))
+        return out
+
     def minimize_stage(
         self,
         gate_seq: Sequence[int],
@@ -962,38 +1013,8 @@ class Context:
         x0: Optional[np.ndarray] = None,
         want_items: bool = True,
     ) -> dict:
-        k = len(gate_seq)
-        n = 6 * (k + 1)
-        gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.int32)
-            na = active.shape[0]
-        else:
-            na = self.n_targets
-        R = int(params.restarts)
-        if x0 is not None:
-            x0 = np.ascontiguousarray(x0, dtype=np.float64)
-            if x0.shape != (na, R, n):
-                raise ValueError(f"x0 must have shape [{na}, {R}, {n}]")
-        out = {
-            "best_loss": np.empty(na, dtype=np.float64),
-            "best_x": np.empty((na, n), dtype=np.float64),
-            "best_restart": np.empty(na, dtype=np.int32),
-        }
-        if want_items:
-            out["item_loss"] = np.empty((na, R), dtype=np.float64)
-            out["item_iters"] = np.empty((na, R), dtype=np.int32)
-            out["item_status"] = np.empty((na, R), dtype=np.int32)
-            out["item_evals"] = np.empty((na, R), dtype=np.int32)
-        _check(
-            self._lib.slam_minimize_stage(
-                self._h, k, _ptr(gs), _ptr(active), na, _ptr(x0), C.byref(params),
-                _ptr(out["best_loss"]), _ptr(out["best_x"]), _ptr(out["best_restart"]),
-                _ptr(out.get("item_loss")), _ptr(out.get("item_iters")), _ptr(out.get("item_status")),
-                _ptr(out.get("item_evals")),
-            )
-        )
-        return out
+        out = self._stage_call(self._lib.slam_minimize_stage, 0, gate_seq, params, active, x0, want_items=want_items)
+        return {key: a for key, a in out.items() if a is not None}  # (without items: no item_* keys here, None in the V2 / smush form)
 
     # -- the whole span loop -------------------------------------------------
     @staticmethod
@@ -1028,11 +1049,8 @@ class Context:
         if not fetch or not hasattr(self._lib, "slam_decompose_range_fetch"):
             _check(self._lib.slam_decompose_range(self._h, int(first), int(count), k_min, k_max, _ptr(flat), C.byref(params), float(success_threshold)))
             return self.fetch_results_range(k_max, first, count, pinned=pinned) if fetch else None
-        nmax = 6 * (k_max + 1)
-        new = result_pool.empty if pinned else pageable_pool.empty
-        best_loss = new(count, np.float64)
-        best_x = new((count, nmax), np.float64)  # (every row is written: the resident rows are zero-padded)
-        best_cycles = new(count, np.int32)
+        # (every row of best_x is written: the resident rows are zero-padded)
+        best_loss, best_x, best_cycles = _result_triple(result_pool.empty if pinned else pageable_pool.empty, count, 6 * (k_max + 1))
         _check(self._lib.slam_decompose_range_fetch(self._h, int(first), int(count), k_min, k_max, _ptr(flat), C.byref(params),
                                                      float(success_threshold), _ptr(best_loss), _ptr(best_x), _ptr(best_cycles)))
         return best_loss, best_x, best_cycles
@@ -1067,11 +1085,7 @@ class Context:
         return int(n_loc.value), int(n_unr.value)
 
     def fetch_results_range(self, k_max: int, first: int, count: int, pinned: bool = False):
-        nmax = 6 * (k_max + 1)
-        new = result_pool.empty if pinned else pageable_pool.empty
-        best_loss = new(count, np.float64)
-        best_x = new((count, nmax), np.float64)
-        best_cycles = new(count, np.int32)
+        best_loss, best_x, best_cycles = _result_triple(result_pool.empty if pinned else pageable_pool.empty, count, 6 * (k_max + 1))
         _check(self._lib.slam_fetch_results_range(self._h, k_max, int(first), int(count), _ptr(best_loss), _ptr(best_x), _ptr(best_cycles)))
         return best_loss, best_x, best_cycles
 
@@ -1085,38 +1099,7 @@ class Context:
                              active: Optional[np.ndarray] = None, x0: Optional[np.ndarray] = None) -> dict:
         """``minimize_stage`` plus the per-iteration trajectories of every restart (use_callback, optimizer.py:217-224):
         ``trace_loss[na, R, cap]`` and ``trace_x[na, R, cap, n]`` (NaN beyond ``item_iters``)."""
-        k = len(gate_seq)
-        n = 6 * (k + 1)
-        gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.int32)
-            na = active.shape[0]
-        else:
-            na = self.n_targets
-        R = int(params.restarts)
-        if x0 is not None:
-            x0 = np.ascontiguousarray(x0, dtype=np.float64)
-            if x0.shape != (na, R, n):
-                raise ValueError(f"x0 must have shape [{na}, {R}, {n}]")
-        cap = int(trace_cap)
-        out = {
-            "best_loss": np.empty(na, dtype=np.float64),
-            "best_x": np.empty((na, n), dtype=np.float64),
-            "best_restart": np.empty(na, dtype=np.int32),
-            "item_loss": np.empty((na, R), dtype=np.float64),
-            "item_iters": np.empty((na, R), dtype=np.int32),
-            "item_status": np.empty((na, R), dtype=np.int32),
-            "trace_loss": np.empty((na, R, cap), dtype=np.float64),
-            "trace_x": np.empty((na, R, cap, n), dtype=np.float64),
-        }
-        _check(
-            self._lib.slam_minimize_stage_trace(
-                self._h, k, _ptr(gs), _ptr(active), na, _ptr(x0), C.byref(params), float(exit_loss), cap,
-                _ptr(out["best_loss"]), _ptr(out["best_x"]), _ptr(out["best_restart"]), _ptr(out["item_loss"]),
-                _ptr(out["item_iters"]), _ptr(out["item_status"]), _ptr(out["trace_loss"]), _ptr(out["trace_x"]),
-            )
-        )
-        return out
+        return self._stage_call(self._lib.slam_minimize_stage_trace, 0, gate_seq, params, active, x0, exit_loss=exit_loss, trace_cap=trace_cap)
 
     # -- templates with parametrised 2Q gates (CircuitTemplateV2) ------------------------
     def v2_set_gates(self, gates: Sequence["V2Gate"]) -> None:
@@ -1135,60 +1118,12 @@ class Context:
 
     def v2_eval(self, gate_seq: Sequence[int], x: np.ndarray, target_of: Optional[np.ndarray] = None, want_grad=True, want_unitary=False):
         """Loss, gradient w.r.t. all n = 6 (k + 1) + QN k parameters and (optionally) W(x) for ``x[M, n]``."""
-        k = len(gate_seq)
-        n = 6 * (k + 1) + self.v2_qn * k
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        if x.ndim != 2 or x.shape[1] != n:
-            raise ValueError(f"x must have shape [M, {n}]")
-        M = x.shape[0]
-        tof = np.zeros(M, np.int32) if target_of is None else np.ascontiguousarray(target_of, dtype=np.int32)
-        gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
-        loss = np.empty(M, dtype=np.float64)
-        grad = np.empty((M, n), dtype=np.float64) if want_grad else None
-        w = np.empty((M, 4, 4, 2), dtype=np.float64) if want_unitary else None
-        _check(self._lib.slam_v2_eval_loss_grad(self._h, k, _ptr(gs), _ptr(x), _ptr(tof), M, _ptr(loss), _ptr(grad), _ptr(w)))
-        return loss, grad, (w.view(np.complex128).reshape(M, 4, 4) if want_unitary else None)
+        return self._v2_like_eval(self._lib.slam_v2_eval_loss_grad, self.v2_qn, gate_seq, x, target_of, want_grad, want_unitary)
 
     def v2_minimize_stage(self, gate_seq: Sequence[int], params: OptParams, exit_loss: float, init_lo, init_hi, bound_lo=None,
-                          bound_hi=None, active: Optional[np.ndarray] = None, x0: Optional[np.ndarray] = None, want_items: bool = True,
-                          _fn=None, _qn=None) -> dict:
-        k = len(gate_seq)
-        n = 6 * (k + 1) + (self.v2_qn if _qn is None else _qn) * k
-        gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.int32)
-            na = active.shape[0]
-        else:
-            na = self.n_targets
-        R = int(params.restarts)
-        vecs = []
-        for v in (init_lo, init_hi, bound_lo, bound_hi):
-            if v is not None:
-                v = np.ascontiguousarray(v, dtype=np.float64)
-                if v.shape != (n,):
-                    raise ValueError(f"per-parameter arrays must have shape [{n}]")
-            vecs.append(v)
-        if x0 is not None:
-            x0 = np.ascontiguousarray(x0, dtype=np.float64)
-            if x0.shape != (na, R, n):
-                raise ValueError(f"x0 must have shape [{na}, {R}, {n}]")
-        out = {
-            "best_loss": np.empty(na, dtype=np.float64),
-            "best_x": np.empty((na, n), dtype=np.float64),
-            "best_restart": np.empty(na, dtype=np.int32),
-            "item_loss": np.empty((na, R), dtype=np.float64) if want_items else None,
-            "item_iters": np.empty((na, R), dtype=np.int32) if want_items else None,
-            "item_status": np.empty((na, R), dtype=np.int32) if want_items else None,
-            "item_evals": np.empty((na, R), dtype=np.int32) if want_items else None,
-        }
-        _check(
-            (_fn or self._lib.slam_v2_minimize_stage)(
-                self._h, k, _ptr(gs), _ptr(active), na, _ptr(x0), _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(vecs[3]),
-                C.byref(params), float(exit_loss), _ptr(out["best_loss"]), _ptr(out["best_x"]), _ptr(out["best_restart"]),
-                _ptr(out["item_loss"]), _ptr(out["item_iters"]), _ptr(out["item_status"]), _ptr(out["item_evals"]),
-            )
-        )
-        return out
+                          bound_hi=None, active: Optional[np.ndarray] = None, x0: Optional[np.ndarray] = None, want_items: bool = True) -> dict:
+        return self._stage_call(self._lib.slam_v2_minimize_stage, self.v2_qn, gate_seq, params, active, x0,
+                                (init_lo, init_hi, bound_lo, bound_hi), exit_loss, want_items=want_items)
 
     def v2_decompose_range(self, first: int, count: int, k_min: int, k_max: int, gate_seqs, layouts, params: OptParams, threshold: float):
         """The span loop of a V2 template on the device (``slam_v2_decompose_range``).  ``layouts[i]`` = (init_lo, init_hi, bound_lo,
@@ -1201,42 +1136,18 @@ class Context:
         n_tot = sum(6 * (k + 1) + qn * k for k in range(k_min, k_max + 1))
         if len(gs) != sum(range(k_min, k_max + 1)) or any(len(v) != n_tot for v in cat):
             raise ValueError("gate_seqs / layouts do not match the span range")
-        best_loss = pageable_pool.empty(count, np.float64)
-        best_x = pageable_pool.empty((count, nmax), np.float64)
-        best_cycles = pageable_pool.empty(count, np.int32)
+        best_loss, best_x, best_cycles = _result_triple(pageable_pool.empty, count, nmax)
         _check(self._lib.slam_v2_decompose_range(self._h, int(first), int(count), int(k_min), int(k_max), _ptr(gs), _ptr(cat[0]), _ptr(cat[1]),
                                                  _ptr(cat[2]), _ptr(cat[3]), C.byref(params), float(threshold), _ptr(best_loss), _ptr(best_x),
                                                  _ptr(best_cycles)))
         return best_loss, best_x, best_cycles
 
     def v2_minimize_stage_trace(self, gate_seq: Sequence[int], params: OptParams, exit_loss: float, trace_cap: int, init_lo, init_hi,
-                                bound_lo=None, bound_hi=None, active: Optional[np.ndarray] = None, _fn=None, _qn=None) -> dict:
+                                bound_lo=None, bound_hi=None, active: Optional[np.ndarray] = None) -> dict:
         """``v2_minimize_stage`` plus the loss / parameters after every accepted iteration of every restart
-        (``trace_loss`` [na, R, cap], ``trace_x`` [na, R, cap, n]; NaN beyond an item's iterations)."""
-        k = len(gate_seq)
-        n = 6 * (k + 1) + (self.v2_qn if _qn is None else _qn) * k
-        gs = np.ascontiguousarray(gate_seq, dtype=np.int32)
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.int32)
-            na = active.shape[0]
-        else:
-            na = self.n_targets
-        R, cap = int(params.restarts), int(trace_cap)
-        vecs = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (init_lo, init_hi, bound_lo, bound_hi)]
-        for v in vecs:
-            if v is not None and v.shape != (n,):
-                raise ValueError(f"per-parameter arrays must have shape [{n}]")
-        out = {
-            "best_loss": np.empty(na, dtype=np.float64), "best_x": np.empty((na, n), dtype=np.float64),
-            "best_restart": np.empty(na, dtype=np.int32), "item_loss": np.empty((na, R), dtype=np.float64),
-            "item_iters": np.empty((na, R), dtype=np.int32), "item_status": np.empty((na, R), dtype=np.int32),
-            "trace_loss": np.empty((na, R, cap), dtype=np.float64), "trace_x": np.empty((na, R, cap, n), dtype=np.float64),
-        }
-        _check((_fn or self._lib.slam_v2_minimize_stage_trace)(
-            self._h, k, _ptr(gs), _ptr(active), na, None, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(vecs[3]), C.byref(params),
-            float(exit_loss), cap, _ptr(out["best_loss"]), _ptr(out["best_x"]), _ptr(out["best_restart"]), _ptr(out["item_loss"]),
-            _ptr(out["item_iters"]), _ptr(out["item_status"]), _ptr(out["trace_loss"]), _ptr(out["trace_x"])))
-        return out
+        (``trace_loss`` [na, R, cap], ``trace_x`` [na, R, cap, n]; NaN beyond an item's iterations).  No ``x0``: NULL goes in its place."""
+        return self._stage_call(self._lib.slam_v2_minimize_stage_trace, self.v2_qn, gate_seq, params, active, None,
+                                (init_lo, init_hi, bound_lo, bound_hi), exit_loss, trace_cap)
 
     # -- parallel-drive ("smush") gates: the same calls as the V2 family -------------------------
     def smush_set_gates(self, gates: Sequence["SmushGate"]) -> None:
@@ -1251,14 +1162,14 @@ class Context:
     def smush_minimize_stage(self, gate_seq, params: OptParams, exit_loss: float, init_lo, init_hi, bound_lo=None, bound_hi=None,
                              active=None, x0=None, want_items: bool = True) -> dict:
         """As ``v2_minimize_stage`` for a smush gate table."""
-        return self.v2_minimize_stage(gate_seq, params, exit_loss, init_lo, init_hi, bound_lo, bound_hi, active, x0, want_items,
-                                      _fn=self._lib.slam_smush_minimize_stage, _qn=self.smush_qn)
+        return self._stage_call(self._lib.slam_smush_minimize_stage, self.smush_qn, gate_seq, params, active, x0,
+                                (init_lo, init_hi, bound_lo, bound_hi), exit_loss, want_items=want_items)
 
     def smush_minimize_stage_trace(self, gate_seq, params: OptParams, exit_loss: float, trace_cap: int, init_lo, init_hi, bound_lo=None,
                                    bound_hi=None, active=None) -> dict:
         """As ``v2_minimize_stage_trace`` for a smush gate table."""
-        return self.v2_minimize_stage_trace(gate_seq, params, exit_loss, trace_cap, init_lo, init_hi, bound_lo, bound_hi, active,
-                                            _fn=self._lib.slam_smush_minimize_stage_trace, _qn=self.smush_qn)
+        return self._stage_call(self._lib.slam_smush_minimize_stage_trace, self.smush_qn, gate_seq, params, active, None,
+                                (init_lo, init_hi, bound_lo, bound_hi), exit_loss, trace_cap)
 
     def _v2_like_eval(self, fn, qn, gate_seq, x, target_of, want_grad, want_unitary):
         k = len(gate_seq)

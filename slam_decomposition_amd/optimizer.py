@@ -20,6 +20,7 @@ Differences a caller can observe:
 from __future__ import annotations
 
 import logging
+from functools import partial
 from typing import List, Sequence
 
 import numpy as np
@@ -41,6 +42,45 @@ _FAIL_MSG = (
     "Failed to converge within error threshold. Try increasing restart attempts or increasing "
     "temperature scaling on preseed."
 )
+
+
+def _check_span_limit(k: int, limit: int) -> None:
+    if k > limit:
+        raise NotImplementedError(f"template spans up to {limit} are implemented on the HIP path (got {k})")
+
+
+def _merge_span(best_loss, best_cycles, span_losses, idx, loss, k: int) -> np.ndarray:
+    """The merge rule of the reference's sequential loop (optimizer.py:281-284) for the targets ``idx`` that ran at template size k
+    with the results ``loss[len(idx)]``: a result is taken if nothing is recorded yet or it is strictly lower.  Updates ``best_loss``
+    and ``best_cycles`` in place, writes the running best into ``span_losses[idx, k - 1]`` (unless None) and returns the ``better``
+    mask over ``idx`` -- what else a path keeps per target (parameters, coverage entry) it copies for ``idx[better]`` itself."""
+    better = (best_cycles[idx] < 0) | (loss < best_loss[idx])
+    best_loss[idx[better]], best_cycles[idx[better]] = loss[better], k
+    if span_losses is not None:
+        span_losses[idx, k - 1] = best_loss[idx]
+    return better
+
+
+def _fan_out(jobs) -> list:
+    """Run the callables side by side, one host thread each: the first recorded error is raised, else their results in job order."""
+    import threading
+
+    parts, errors = [None] * len(jobs), []
+
+    def work(r):
+        try:
+            parts[r] = jobs[r]()
+        except Exception as exc:  # surfaced below
+            errors.append(exc)
+
+    threads = [threading.Thread(target=work, args=(r,)) for r in range(len(jobs))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        raise errors[0]
+    return parts
 
 
 class TemplateOptimizer:
@@ -174,6 +214,27 @@ class TemplateOptimizer:
             **({"gtol_far": 0.0} if getattr(self.basis, "smush", False) else {}),
         )
 
+    def _load_targets(self, ctx, targets, first=None, count=None) -> None:
+        """The batch -- or its share [first, first + count) -- resident in ``ctx``: a device sampler generates it in place (nothing
+        crosses PCIe), anything else is uploaded."""
+        window = () if first is None else (first, count)
+        if self._device_sampler is not None:
+            self._device_sampler.fill(ctx, *window)
+        else:
+            ctx.set_targets(targets if first is None else targets[first : first + count])
+
+    def _prepare(self, ctx, gate_step=None) -> None:
+        """What every path does to a context between making its targets resident and its first run: the gate table -- the basis'
+        fixed gates, or the path's own ``gate_step(ctx)`` (V2 / smush tables and constraints) --, the cost, a fresh statistics block.
+        The paths keep their own order around it (the family lookup runs between targets and gates, the windowed helpers upload
+        their share last): device calls are not reordered to make them look alike."""
+        if gate_step is None:
+            ctx.set_gates(self.basis.gate_matrices)
+        else:
+            gate_step(ctx)
+        ctx.set_cost(self._cost_kind)
+        ctx.reset_stats()
+
     # a span loop side by side for ALL targets (SLAM_FLAG_OVERLAP) runs the LAST span for every target of the call: it pays when
     # that span is needed by a good share of them anyway (CNOT: all; sqrt(iSWAP): 21 % -- 18.1 -> 16.8 ms for 65 536 x 32) and is
     # pure waste when the basis covers the chamber earlier (B: every Haar target at two gates -- the most expensive stage for nothing)
@@ -212,18 +273,9 @@ class TemplateOptimizer:
             raise ValueError("empty spanning range")
         if ks[0] <= 0:
             raise ValueError()  # CircuitTemplate.build(n_repetitions <= 0), basis.py:127-128
-        if max(ks) > _ffi.MAX_SPAN_MINIMIZE:
-            raise NotImplementedError(
-                f"template spans up to {_ffi.MAX_SPAN_MINIMIZE} are implemented on the HIP path "
-                f"(got {max(ks)})"
-            )
+        _check_span_limit(max(ks), _ffi.MAX_SPAN_MINIMIZE)
         if ks != list(range(ks[0], ks[-1] + 1)):
             return self._run_batch_any_order(targets, ks)
-        if ks[-1] > _ffi.MAX_SPAN_MINIMIZE:
-            raise NotImplementedError(
-                f"template spans up to {_ffi.MAX_SPAN_MINIMIZE} are implemented on the HIP path "
-                f"(got maximum_span_guess = {ks[-1]})"
-            )
         gate_seqs = [self.basis.gate_sequence(k) for k in ks]
         prm = self._opt_params()
         n = len(targets)
@@ -238,55 +290,29 @@ class TemplateOptimizer:
             # gains nothing from being split -- what several batches in flight buy is the overlap of SUCCESSIVE
             # batches; the shards of one batch still end with their own tails.  Hence the default of 1.
             devices = devices * int(self.auto_shards)
+
         def run_shard(device, first, count, r=0):
             # a context per shard holding only the shard's targets (kept in runtime's cache: shard r uses slot r of its device);
             # the seeds are keyed on the GLOBAL target index (target_base), so a sharded run draws exactly the seeds of the unsharded one
             single = len(devices) == 1
             ctx = runtime.get_context(device, 0 if single else r)
-            try:
-                if self._device_sampler is not None:
-                    self._device_sampler.fill(ctx, first, count)  # generated in place, nothing crosses PCIe
-                else:
-                    ctx.set_targets(targets[first : first + count])
-                ctx.set_gates(self.basis.gate_matrices)
-                ctx.set_cost(self._cost_kind)
-                ctx.reset_stats()
-                flags = prm.flags | (_ffi.FLAG_OVERLAP if (single and self._overlap_pays(ctx, count, ks)) else 0)
-                sp = _ffi.OptParams(restarts=prm.restarts, maxiter=prm.maxiter, gtol=prm.gtol, stop_loss=prm.stop_loss, seed=prm.seed,
-                                    flags=flags, gtol_far=prm.gtol_far, far_loss=prm.far_loss, items_per_quad=prm.items_per_quad,
-                                    target_base=first)
-                # (one blocking call alone on the device: results into recycled page-locked blocks, _ffi.result_pool)
-                out = ctx.decompose_range(0, count, ks[0], ks[-1], gate_seqs, sp, self.success_threshold, pinned=single)
-                # the running best loss per span feeds the "Cycle (k =...)" log lines only (optimizer.py:297)
-                sl = ctx.fetch_span_losses(0, count) if self._want_span_losses else None
-                return out + (sl,), ctx.stats()
-            finally:
-                pass
+            self._load_targets(ctx, targets, first, count)
+            self._prepare(ctx)
+            overlap = _ffi.FLAG_OVERLAP if (single and self._overlap_pays(ctx, count, ks)) else 0
+            sp = prm.replace(flags=prm.flags | overlap, target_base=first)
+            # (one blocking call alone on the device: results into recycled page-locked blocks, _ffi.result_pool)
+            out = ctx.decompose_range(0, count, ks[0], ks[-1], gate_seqs, sp, self.success_threshold, pinned=single)
+            # the running best loss per span feeds the "Cycle (k =...)" log lines only (optimizer.py:297)
+            sl = ctx.fetch_span_losses(0, count) if self._want_span_losses else None
+            return out + (sl,), ctx.stats()
 
         if len(devices) == 1 or n < len(devices):
             (best_loss, best_x, best_cycles, self._span_losses), st = run_shard(devices[0], 0, n)
             self._set_stats([st])
         else:
-            import threading
-
             from .parallel import shard_range
 
-            parts = [None] * len(devices)
-            errors = []
-            def work(r):
-                try:
-                    first, count = shard_range(n, r, len(devices))
-                    parts[r] = run_shard(devices[r], first, count, r)
-                except Exception as exc:  # surfaced below, in rank order
-                    errors.append(exc)
-
-            threads = [threading.Thread(target=work, args=(r,)) for r in range(len(devices))]
-            for t in threads:
-                t.start()
-            for t in threads:
-                t.join()
-            if errors:
-                raise errors[0]
+            parts = _fan_out([partial(run_shard, devices[r], *shard_range(n, r, len(devices)), r) for r in range(len(devices))])
             best_loss = np.concatenate([p[0][0] for p in parts])
             best_x = np.concatenate([p[0][1] for p in parts])
             best_cycles = np.concatenate([p[0][2] for p in parts])
@@ -355,17 +381,12 @@ class TemplateOptimizer:
                     ctx = runtime.get_context(device, slot)
                     ctx.set_gates(self.basis.gate_matrices)
                     ctx.set_cost(self._cost_kind)
-                    if self._device_sampler is not None:
-                        self._device_sampler.fill(ctx, base, share)
-                    else:
-                        ctx.set_targets(targets[base : base + share])
+                    self._load_targets(ctx, targets, base, share)
                 except Exception:
                     resident.abort()  # the other helpers must not wait for this one
                     raise
                 resident.wait()
-                sp = _ffi.OptParams(restarts=prm.restarts, maxiter=prm.maxiter, gtol=prm.gtol, stop_loss=prm.stop_loss, seed=prm.seed,
-                                    flags=flags, gtol_far=prm.gtol_far, far_loss=prm.far_loss, items_per_quad=prm.items_per_quad,
-                                    target_base=base)
+                sp = prm.replace(flags=flags, target_base=base)
                 for i, (first, count) in enumerate(wins):
                     if errors:
                         return
@@ -420,8 +441,7 @@ class TemplateOptimizer:
         for k in ks:
             if k <= 0:
                 raise ValueError()  # CircuitTemplate.build(n_repetitions <= 0), basis.py:127-128
-            if k > _ffi.MAX_SPAN_EVAL:
-                raise NotImplementedError(f"template spans up to {_ffi.MAX_SPAN_EVAL} are implemented on the HIP path (got {k})")
+            _check_span_limit(k, _ffi.MAX_SPAN_EVAL)
             act = np.nonzero(~(best_loss < self.success_threshold))[0]
             if len(act) == 0:
                 break
@@ -439,12 +459,11 @@ class TemplateOptimizer:
             x, f, _, nfev = host_methods.nelder_mead_batch(fun, x0.reshape(len(act) * R, npar), maxiter=MAXITER)
             evals[k] += int(nfev.sum())
             f, x = f.reshape(len(act), R), x.reshape(len(act), R, npar)
-            for j, t in enumerate(act):
-                below = np.nonzero(f[j] < self.success_threshold)[0]
-                r = int(below[0]) if len(below) else int(np.argmin(f[j]))  # optimizer.py:281-295: sequential restarts, first success wins
-                if best_cycles[t] < 0 or f[j, r] < best_loss[t]:
-                    best_loss[t], best_x[t], best_cycles[t] = float(f[j, r]), x[j, r].copy(), k
-                self._span_losses[t, k - 1] = best_loss[t]
+            below = f < self.success_threshold
+            r = np.where(below.any(axis=1), below.argmax(axis=1), f.argmin(axis=1))  # optimizer.py:281-295: sequential restarts, first success wins
+            better = _merge_span(best_loss, best_cycles, self._span_losses, act, f[np.arange(len(act)), r], k)
+            for j in np.nonzero(better)[0]:
+                best_x[act[j]] = x[j, r[j]].copy()
         self._set_stats([{"kernel_ms": 0.0, "kernel_launches": 0, "evals": evals, "items": [0] * len(evals), "total_ms": 0.0,
                           "kernel_ms_span": [0.0] * len(evals), "wave_rounds": [0] * len(evals), "evals_accepted": [0] * len(evals),
                           "evals_preempted": [0] * len(evals)}])
@@ -457,13 +476,8 @@ class TemplateOptimizer:
         n = len(targets)
         prm = self._opt_params()
         ctx = runtime.get_context(self.devices[0])
-        if self._device_sampler is not None:
-            self._device_sampler.fill(ctx)
-        else:
-            ctx.set_targets(targets)
-        ctx.set_gates(self.basis.gate_matrices)
-        ctx.set_cost(self._cost_kind)
-        ctx.reset_stats()
+        self._load_targets(ctx, targets)
+        self._prepare(ctx)
         k_top = max(ks)
         best_loss = np.full(n, np.inf)
         best_x = np.zeros((n, 6 * (k_top + 1)))
@@ -477,10 +491,8 @@ class TemplateOptimizer:
                 break
             ctx.decompose_list(todo, k, k, [self.basis.gate_sequence(k)], prm, self.success_threshold, k_layout=k_top)
             loss, x, cyc = ctx.fetch_results_range(k_top, 0, n)
-            better = np.zeros(n, bool)
-            better[todo] = (best_cycles[todo] < 0) | (loss[todo] < best_loss[todo])  # optimizer.py:281-284
-            best_loss[better], best_x[better], best_cycles[better] = loss[better], x[better], k
-            self._span_losses[todo, k - 1] = best_loss[todo]
+            won = todo[_merge_span(best_loss, best_cycles, self._span_losses, todo, loss[todo], k)]
+            best_x[won] = x[won]
         self._set_stats([ctx.stats()])
         xs = [best_x[t, self.basis.param_slice(int(best_cycles[t]))].copy() for t in range(n)]
         return best_loss, xs, best_cycles
@@ -498,14 +510,11 @@ class TemplateOptimizer:
         self.basis.minimal_spans(coords)  # raises for a target no entry can contain (polytope_wrap.py:91-93)
         entries = self.basis.candidate_entries(coords)
         k_top = max(len(e) for e, _, _ in entries)
-        if k_top > _ffi.MAX_SPAN_MINIMIZE:
-            raise NotImplementedError(f"template spans up to {_ffi.MAX_SPAN_MINIMIZE} are implemented on the HIP path (got {k_top})")
+        _check_span_limit(k_top, _ffi.MAX_SPAN_MINIMIZE)
         prm = self._opt_params()
         ctx = runtime.get_context(self.devices[0])
-        ctx.set_targets(targets)
-        ctx.set_gates(self.basis.gate_matrices)
-        ctx.set_cost(self._cost_kind)
-        ctx.reset_stats()
+        ctx.set_targets(targets)  # (the coordinates were needed on the host: the batch is there anyway)
+        self._prepare(ctx)
         best_loss = np.full(n, np.inf)
         best_x = np.zeros((n, 6 * (k_top + 1)))
         best_cycles = np.full(n, -1, dtype=np.int32)
@@ -519,9 +528,8 @@ class TemplateOptimizer:
             k = len(e)
             ctx.decompose_list(todo, k, k, [e.gate_indices], prm, self.success_threshold, k_layout=k_top)
             loss, x, _ = ctx.fetch_results_range(k_top, 0, n)
-            better = np.zeros(n, bool)
-            better[todo] = (best_cycles[todo] < 0) | (loss[todo] < best_loss[todo])  # optimizer.py:281-284
-            best_loss[better], best_x[better], best_cycles[better], best_entry[better] = loss[better], x[better], k, j
+            won = todo[_merge_span(best_loss, best_cycles, None, todo, loss[todo], k)]
+            best_x[won], best_entry[won] = x[won], j
             if self._want_span_losses:  # (only the log lines read it)
                 for t in todo:
                     self._entries_tried[t].append((j, float(best_loss[t])))
@@ -538,17 +546,11 @@ class TemplateOptimizer:
         exact = getattr(self.basis, "span_rules_exact", True)
         # exact rules: every target runs at its own size only; lower bounds: the span loop runs from the bound to the template's maximum
         k_top = int(spans.max()) if exact else max(int(spans.max()), int(self.basis.maximum_span_guess))
-        if k_top > _ffi.MAX_SPAN_MINIMIZE:
-            raise NotImplementedError(f"template spans up to {_ffi.MAX_SPAN_MINIMIZE} are implemented on the HIP path (got {k_top})")
+        _check_span_limit(k_top, _ffi.MAX_SPAN_MINIMIZE)
         prm = self._opt_params()
         ctx = runtime.get_context(self.devices[0])
-        if self._device_sampler is not None:
-            self._device_sampler.fill(ctx)
-        else:
-            ctx.set_targets(targets)
-        ctx.set_gates(self.basis.gate_matrices)
-        ctx.set_cost(self._cost_kind)
-        ctx.reset_stats()
+        self._load_targets(ctx, targets)
+        self._prepare(ctx)
         for k in np.unique(spans):
             k = int(k)
             k_hi = k if exact else k_top
@@ -569,22 +571,16 @@ class TemplateOptimizer:
         ``_run_batch_mixed_order`` does, unreachable ones as the cost lookup does."""
         fam = self.basis.family
         ctx = runtime.get_context(self.devices[0])
-        if self._device_sampler is not None:
-            self._device_sampler.fill(ctx)
-        else:
-            ctx.set_targets(targets)
+        self._load_targets(ctx, targets)
         _, _, members, gates = fam.device_lookup(ctx, self.basis.policy, 0, n, want_targets=True)
         if np.any(gates < 0):
             raise fam.unreachable_error()
         if np.any(gates == 0):
             raise ValueError()  # range(0, 1) -> CircuitTemplate.build(0), polytope_wrap.py:53-54, basis.py:127-128
         k_top = int(gates.max())
-        if k_top > _ffi.MAX_SPAN_MINIMIZE:
-            raise NotImplementedError(f"template spans up to {_ffi.MAX_SPAN_MINIMIZE} are implemented on the HIP path (got {k_top})")
+        _check_span_limit(k_top, _ffi.MAX_SPAN_MINIMIZE)
         prm = self._opt_params()
-        ctx.set_gates(self.basis.gate_matrices)
-        ctx.set_cost(self._cost_kind)
-        ctx.reset_stats()
+        self._prepare(ctx)
         pair = members.astype(np.int64) * (k_top + 1) + gates
         for p in np.unique(pair):
             m, k = int(p) // (k_top + 1), int(p) % (k_top + 1)
@@ -603,10 +599,8 @@ class TemplateOptimizer:
         size + one ``slam_decompose_list`` each).  The reference's failures keep their exceptions: a target no prefix of the template
         reaches (polytope_wrap.py:91-93), a local target (``build(0)``, basis.py:127-128)."""
         kmax = int(self.basis.maximum_span_guess)
-        self._device_sampler.fill(ctx)
-        ctx.set_gates(self.basis.gate_matrices)
-        ctx.set_cost(self._cost_kind)
-        ctx.reset_stats()
+        self._load_targets(ctx, None)  # (this path is taken for a device sampler only: there is no array)
+        self._prepare(ctx)
         prm = self._opt_params()
         n_local, n_unreach = ctx.decompose_predicted([self.basis._gate_coords_all[i] for i in self.basis.gate_sequence(kmax)], kmax,
                                                      [self.basis.gate_sequence(k) for k in range(1, kmax + 1)], prm, self.success_threshold, 0, n)
@@ -641,33 +635,38 @@ class TemplateOptimizer:
         # set_constraint (optimizer.py:260-265 switches SciPy to SLSQP): the half-space of every span, for the device
         constraints = {k: basis.constraint_layout(k) for k in ks} if basis.using_constraints else {}
 
+        def gate_step(ctx):
+            basis.set_device_gates(ctx)
+            for k, (w_dev, cost_max) in constraints.items():
+                ctx.v2_set_constraint(k, w_dev, cost_max)
+
+        def user_rows(block, idx):
+            """user parameters (index order) out of rows in a span's device layout"""
+            return list(np.ascontiguousarray(block[:, idx]))
+
+        def device_call(fn, *args, **kw):
+            try:
+                return fn(*args, **kw)
+            except _ffi.SlamHipError as exc:
+                if exc.code == -3:  # SLAM_ERR_UNSUPPORTED: span x parameters-per-gate beyond what the device kernels hold
+                    raise NotImplementedError(str(exc)) from exc
+                raise
+
         def run_shard(device, first, count):
             single = len(self.devices) == 1
             ctx = runtime.get_context(device) if single else _ffi.Context(device)
             try:
                 ctx.set_targets(targets[first : first + count])
-                basis.set_device_gates(ctx)
-                for k, (w_dev, cost_max) in constraints.items():
-                    ctx.v2_set_constraint(k, w_dev, cost_max)
-                ctx.set_cost(self._cost_kind)
-                ctx.reset_stats()
-                sp = _ffi.OptParams(restarts=prm.restarts, maxiter=prm.maxiter, gtol=prm.gtol, stop_loss=prm.stop_loss, seed=prm.seed,
-                                    flags=prm.flags, gtol_far=prm.gtol_far, far_loss=prm.far_loss, target_base=first)
+                self._prepare(ctx, gate_step)
+                sp = prm.replace(target_base=first)
                 if ks == list(range(ks[0], ks[-1] + 1)) and not basis.smush:
                     # the usual case, a run of template sizes: the whole span loop as one chain of kernels on the device
-                    try:
-                        bl, bx, bc = ctx.v2_decompose_range(0, count, ks[0], ks[-1], [layouts[k][0] for k in ks],
-                                                            [layouts[k][3:7] for k in ks], sp, self.success_threshold)
-                    except _ffi.SlamHipError as exc:
-                        if exc.code == -3:
-                            raise NotImplementedError(str(exc)) from exc
-                        raise
+                    bl, bx, bc = device_call(ctx.v2_decompose_range, 0, count, ks[0], ks[-1], [layouts[k][0] for k in ks],
+                                             [layouts[k][3:7] for k in ks], sp, self.success_threshold)
                     xs = [None] * count
                     for k in np.unique(bc):
-                        idx = layouts[int(k)][2]
                         sel = np.nonzero(bc == k)[0]
-                        block = np.ascontiguousarray(bx[sel][:, idx])  # user parameters (index order) of the span's device layout
-                        for i, row in zip(sel.tolist(), block):
+                        for i, row in zip(sel.tolist(), user_rows(bx[sel], layouts[int(k)][2])):
                             xs[i] = row
                     return (bl, xs, bc.astype(np.int32), ctx.fetch_span_losses(0, count)), ctx.stats()
                 best = np.full(count, np.inf)
@@ -679,18 +678,11 @@ class TemplateOptimizer:
                     if len(act) == 0:
                         break
                     seq, _, idx, init_lo, init_hi, blo, bhi = layouts[k]
-                    try:
-                        out = basis.device_minimize_stage(ctx, seq, sp, self.success_threshold, init_lo, init_hi, blo, bhi, active=act,
-                                                          want_items=False)
-                    except _ffi.SlamHipError as exc:
-                        if exc.code == -3:  # SLAM_ERR_UNSUPPORTED: span x parameters-per-gate beyond what the device kernels hold
-                            raise NotImplementedError(str(exc)) from exc
-                        raise
-                    for j, t in enumerate(act):
-                        if best_k[t] < 0 or out["best_loss"][j] < best[t]:  # optimizer.py:281-284
-                            best[t], best_k[t] = out["best_loss"][j], k
-                            best_x[t] = out["best_x"][j][idx].copy()  # user parameters (index order)
-                        span_losses[t, k - 1] = best[t]
+                    out = device_call(basis.device_minimize_stage, ctx, seq, sp, self.success_threshold, init_lo, init_hi, blo, bhi, active=act,
+                                      want_items=False)
+                    better = _merge_span(best, best_k, span_losses, act, out["best_loss"], k)
+                    for t, row in zip(act[better].tolist(), user_rows(out["best_x"][better], idx)):
+                        best_x[t] = row
                 return (best, best_x, best_k, span_losses), ctx.stats()
             finally:
                 if not single:
@@ -700,27 +692,9 @@ class TemplateOptimizer:
             (best, best_x, best_k, self._span_losses), st = run_shard(self.devices[0], 0, n)
             self._set_stats([st])
         else:
-            import threading
-
             from .parallel import shard_range
 
-            parts = [None] * len(self.devices)
-            errors = []
-
-            def work(r):
-                try:
-                    first, count = shard_range(n, r, len(self.devices))
-                    parts[r] = run_shard(self.devices[r], first, count)
-                except Exception as exc:  # surfaced below
-                    errors.append(exc)
-
-            threads = [threading.Thread(target=work, args=(r,)) for r in range(len(self.devices))]
-            for t in threads:
-                t.start()
-            for t in threads:
-                t.join()
-            if errors:
-                raise errors[0]
+            parts = _fan_out([partial(run_shard, self.devices[r], *shard_range(n, r, len(self.devices))) for r in range(len(self.devices))])
             best = np.concatenate([p[0][0] for p in parts])
             best_x = [x for p in parts for x in p[0][1]]
             best_k = np.concatenate([p[0][2] for p in parts])
@@ -729,6 +703,30 @@ class TemplateOptimizer:
         if np.any(best_k < 0):
             raise ValueError("empty spanning range")
         return best, best_x, best_k
+
+    def _run_batch_v2_by_span(self, targets: np.ndarray, spans: np.ndarray):
+        """``CircuitTemplateV2(use_polytopes=True)`` (basisv2.py:77-85): every target at the size ``spans[t]`` its coverage region
+        assigns; one ``_run_batch_v2`` per size over that size's targets."""
+        if np.any(spans <= 0):
+            raise ValueError()  # build(n_repetitions <= 0), basisv2.py:221-222
+        n = len(targets)
+        best_loss = np.full(n, np.inf)
+        best_xs = [None] * n
+        best_cycles = np.full(n, -1, dtype=np.int32)
+        sl_all = np.full((n, _ffi.MAX_SPAN_EVAL), np.nan)
+        stats = []
+        for k in np.unique(spans):
+            sel = np.nonzero(spans == k)[0]
+            bl, bx, bc = self._run_batch_v2(targets[sel], [int(k)])
+            best_loss[sel], best_cycles[sel] = bl, bc
+            for i, x in zip(sel.tolist(), bx):
+                best_xs[i] = x
+            if self._span_losses is not None:
+                sl_all[sel] = self._span_losses
+            stats.extend(self.last_stats_per_device)
+        self._span_losses = sl_all
+        self._set_stats(stats)
+        return best_loss, best_xs, best_cycles
 
     def _run_batch_callback(self, targets: np.ndarray, spans_per_target):
         """``_run`` with ``use_callback=True`` (optimizer.py:217-224,238,287-292): the span loop is driven from the host,
@@ -742,16 +740,16 @@ class TemplateOptimizer:
         n = len(targets)
         prm = self._opt_params()
         ctx = runtime.get_context(self.devices[0])
-        ctx.set_targets(targets)
-        if self._v2:
+        all_ks = sorted({int(k) for ks in spans_per_target for k in ks})
+
+        def v2_gate_step(ctx):
             self.basis.set_device_gates(ctx)
             if self.basis.using_constraints:
-                for k in sorted({int(k) for ks in spans_per_target for k in ks}):
+                for k in all_ks:
                     ctx.v2_set_constraint(k, *self.basis.constraint_layout(k))
-        else:
-            ctx.set_gates(self.basis.gate_matrices)
-        ctx.set_cost(self._cost_kind)
-        ctx.reset_stats()
+
+        ctx.set_targets(targets)
+        self._prepare(ctx, v2_gate_step if self._v2 else None)
         R = int(self.training_restarts)
         best = [None] * n
         best_x = [None] * n
@@ -759,15 +757,13 @@ class TemplateOptimizer:
         temp_loss = [[] for _ in range(n)]  # one list per target, growing over the spans (optimizer.py:229,238)
         self._callback_records = [[] for _ in range(n)]
         self._span_losses = np.full((n, _ffi.MAX_SPAN_EVAL), np.nan)
-        all_ks = sorted({int(k) for ks in spans_per_target for k in ks})
         for k in all_ks:
             if k <= 0:
                 raise ValueError()  # CircuitTemplate.build(n_repetitions <= 0), basis.py:127-128
-            k_lim = _ffi.V2_MAX_SPAN if self._v2 else _ffi.MAX_SPAN_MINIMIZE  # (per-iteration traces: both kernel families)
-            if self._v2:
+            if self._v2:  # (per-iteration traces: both kernel families)
                 self.basis.check_span(k)
-            elif k > k_lim:
-                raise NotImplementedError(f"template spans up to {k_lim} are implemented on the HIP path (got {k})")
+            else:
+                _check_span_limit(k, _ffi.MAX_SPAN_MINIMIZE)
             act = np.array([t for t in range(n) if k in spans_per_target[t] and not (best[t] is not None and best[t] < self.success_threshold)],
                            dtype=np.int32)
             if len(act) == 0:
@@ -1075,27 +1071,9 @@ class TemplateOptimizer:
             spans_of = [spanning_range] * n
             best_loss, best_xs, best_cycles = self._run_batch_host_method(stacked, spanning_range)
         elif self._v2 and not self.use_callback and self.basis.use_polytopes:
-            # basisv2.py:77-85: every target at the size its coverage region assigns; one run per size over that size's targets
             spans = np.asarray(self.basis.minimal_spans(ctx0.c1c2c3(np.asarray(stacked))), dtype=np.int64)
-            if np.any(spans <= 0):
-                raise ValueError()  # build(n_repetitions <= 0), basisv2.py:221-222
+            best_loss, best_xs, best_cycles = self._run_batch_v2_by_span(np.asarray(stacked), spans)
             spans_of = [[int(k)] for k in spans]
-            best_loss = np.full(n, np.inf)
-            best_xs = [None] * n
-            best_cycles = np.full(n, -1, dtype=np.int32)
-            sl_all = np.full((n, _ffi.MAX_SPAN_EVAL), np.nan)
-            stats = []
-            for k in np.unique(spans):
-                sel = np.nonzero(spans == k)[0]
-                bl, bx, bc = self._run_batch_v2(np.asarray(stacked)[sel], [int(k)])
-                best_loss[sel], best_cycles[sel] = bl, bc
-                for i, x in zip(sel.tolist(), bx):
-                    best_xs[i] = x
-                if self._span_losses is not None:
-                    sl_all[sel] = self._span_losses
-                stats.extend(self.last_stats_per_device)
-            self._span_losses = sl_all
-            self._set_stats(stats)
         elif self._v2 and not self.use_callback:
             spanning_range = list(self.basis.get_spanning_range(stacked[0]))
             spans_of = [spanning_range] * n
