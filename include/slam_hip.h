@@ -293,6 +293,48 @@ int slam_b_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* 
                      double* loss, double* gap);
 
 /*
+ * Fidelity-aware approximate decomposition into gates G of the CNOT class (family 0), the iSWAP class (family 1) or the B class
+ * (family 2) on the device, one thread per resident target (csrc/slam_approx.hpp; the basis_fidelity half of qiskit's
+ * TwoQubitBasisDecomposer, which the reference's pass calls at src/slam/utils/transpiler_pass/weyl_decompose.py:475-480).  For the
+ * target's coordinates folded to c1 <= 1/2, (a, b, c) = pi/2 (c1, c2, c3), and G's class (1/2, beta, 0), beta' = pi beta / 2, the best
+ * circuit of k gates reaches |Tr(T^+ W)| = 4 t_k:
+ *     t_0 = |cos a cos b cos c + i sin a sin b sin c|,
+ *     t_1 = |cos(pi/4 - a) cos(beta' - b) cos c + i sin(pi/4 - a) sin(beta' - b) sin c|,
+ *     t_2 = |cos c| (families 0, 1), 1 (family 2),     t_3 = 1 (families 0, 1; family 2 has no k = 3),
+ * with the loss L_k = 1 - t_k, the average gate fidelity F_k = (4 + 16 t_k^2) / 20 and the expected fidelity E_k = F_k f^k for the
+ * fidelity f of one basis gate.  The k with the largest E_k is chosen, compared in the order 0, 1, 2, 3 with strict >: ties go to fewer
+ * gates; with f = 1 that is the fewest gates that equal the target, 0 for a local one.
+ *   gate, dress     as slam_cx_decompose takes them (families 0, 1; double[SLAM_CX_DRESS]) or slam_b_decompose (family 2;
+ *                   double[SLAM_B_DRESS]), checked in the same way
+ *   basis_fidelity  f, in (0, 1]
+ *   force_cycles    -1: select; 0..3 (0..2 for family 2): that size for every target
+ *   x_out   double[count][24]  the 6 (k + 1) template angles in the front of the row, zeros behind; a row of no gate holds one layer
+ *   cycles  int32[count]       k
+ *   loss    double[count]      1 - |Tr(T^+ template(x_out))| / 4, from a forward pass of the written row
+ *   predicted double[count]    L_k of the chosen k, from the formulas above on the unrounded coordinates
+ *   gap     double[count]      max-norm distance (units of pi) between the chamber points of the target and of the circuit after the
+ *                              alignment: the distance to the nearest point that k gates reach
+ * Any output pointer may be NULL.  Arguments are checked before the context.  SLAM_ERR_INVALID for an unknown family, a gate that
+ * the dress factors do not rebuild, a basis_fidelity outside (0, 1] or not finite, force_cycles out of range, a NULL context and a
+ * window outside the resident batch.
+ */
+int slam_approx_decompose(slam_ctx* ctx, int64_t first, int64_t count, int family, const double* gate, const double* dress,
+                          double basis_fidelity, int force_cycles, double* x_out, int32_t* cycles, double* loss, double* predicted,
+                          double* gap);
+
+/*
+ * The same selection for n_fid basis fidelities at once, counted: one launch over the resident targets [first, first + count).
+ *   fidelities  double[n_fid]      each in (0, 1]; n_fid in 1..64
+ *   counts_out  int64[n_fid][4]    targets per chosen size k = 0..3
+ *   fidsum_out  int64[n_fid]       the sum over the targets of llrint(E_k 2^32) for the chosen k: fixed point, so counts and sums do not
+ *                                  depend on the order of addition
+ * Any output pointer may be NULL.  SLAM_ERR_INVALID for an unknown family, n_fid or a fidelity out of range, a NULL context and a
+ * window outside the resident batch.
+ */
+int slam_approx_counts(slam_ctx* ctx, int64_t first, int64_t count, int family, int32_t n_fid, const double* fidelities,
+                       int64_t* counts_out, int64_t* fidsum_out);
+
+/*
  * Span predictor on the device: for every resident target of [first, first + count) the smallest number k of leading gates of a
  * template whose coverage set contains the target -- the lookup CircuitTemplate.get_spanning_range makes with use_polytopes=True
  * (src/slam/basis.py:95-100 -> monodromy_range_from_target, src/slam/utils/polytopes/polytope_wrap.py:39-94).  The coverage sets
@@ -803,7 +845,8 @@ const char* slam_version(void);
  *      later: slam_sqiswap_decompose (a new symbol only);
  *      later: slam_cx_decompose (a new symbol only);
  *      later: slam_b_decompose (a new symbol only);
- *      later: slam_family_lookup (a new symbol only).
+ *      later: slam_family_lookup (a new symbol only);
+ *      later: slam_approx_decompose and slam_approx_counts (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = (
     "slam_sqiswap_decompose",
     "slam_cx_decompose",
     "slam_b_decompose",
+    "slam_approx_decompose",
+    "slam_approx_counts",
     "slam_predict_spans",
     "slam_coverage_lookup",
     "slam_family_lookup",
@@ -243,6 +245,9 @@ def load_library() -> C.CDLL:
         lib.slam_cx_decompose.argtypes = [P, C.c_int64, C.c_int64, C.c_int, P, P, P, P, P, P]
     if hasattr(lib, "slam_b_decompose"):
         lib.slam_b_decompose.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P, P, P]
+    if hasattr(lib, "slam_approx_decompose"):
+        lib.slam_approx_decompose.argtypes = [P, C.c_int64, C.c_int64, C.c_int, P, P, C.c_double, C.c_int, P, P, P, P, P]
+        lib.slam_approx_counts.argtypes = [P, C.c_int64, C.c_int64, C.c_int, C.c_int32, P, P, P]
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
     if hasattr(lib, "slam_coverage_lookup"):
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
@@ -602,6 +607,43 @@ def b_dress(gate):
     return g, dress
 
 
+APPROX_MAX_FID = 64  # slam_approx_counts: fidelities per call
+FAMILY_CNOT, FAMILY_ISWAP, FAMILY_B = 0, 1, 2  # slam_approx_decompose, slam_approx_counts
+
+
+def approx_family(gate) -> int:
+    """The family of a 4x4 basis gate for slam_approx_decompose: 0 (CNOT class), 1 (iSWAP class), 2 (B class), found with
+    ``cx_family`` and ``b_class``; ``ValueError`` (naming the coordinates) for any other gate."""
+    try:
+        return cx_family(gate)
+    except ValueError:
+        pass
+    try:
+        b_class(gate)
+    except ValueError:
+        from . import weyl
+
+        c = tuple(float(v) for v in weyl.c1c2c3(np.asarray(gate, dtype=np.complex128)))
+        raise ValueError(f"the gate is of none of the CNOT, iSWAP and B classes (Weyl coordinates {c})") from None
+    return FAMILY_B
+
+
+def approx_dress(gate):
+    """``(family, gate [4, 4] complex128, dress)`` for slam_approx_decompose: ``cx_dress`` for families 0 and 1, ``b_dress`` for 2."""
+    family = approx_family(gate)
+    if family == FAMILY_B:
+        return (family,) + b_dress(gate)
+    return cx_dress(gate)
+
+
+def check_basis_fidelity(f) -> float:
+    """``f`` as a float in (0, 1]; ``ValueError`` otherwise."""
+    f = float(f)
+    if not (0.0 < f <= 1.0):  # a NaN fails both
+        raise ValueError(f"basis_fidelity must be in (0, 1], got {f}")
+    return f
+
+
 class Context:
     """One GPU: resident targets + gate table + work buffers (``slam_ctx``)."""
 
@@ -735,6 +777,44 @@ class Context:
         (``span_rules._TOL``)."""
         g, dress = b_dress(gate)
         return self._closed_form_call(self._lib.slam_b_decompose, (_ptr(g), _ptr(dress)), first, count)
+
+    def approx_decompose(self, gate, basis_fidelity: float = 1.0, cycles: Optional[int] = None, first: int = 0, count: Optional[int] = None):
+        """Fidelity-aware approximate circuits of ``gate`` -- a 4x4 matrix of the CNOT, the iSWAP or the B class -- for the resident
+        targets [first, first + count) (slam_approx_decompose) -> ``(x [count, 24], cycles [count], loss [count], predicted [count],
+        gap [count])``: per target the size with the highest expected fidelity when one gate has ``basis_fidelity`` (``cycles=k``: that
+        size for every target), the 6 (cycles[i] + 1) angles of the best circuit of that size (one layer for no gate), its BasicCost
+        loss from a forward pass, the loss the closed form predicts, and the chamber distance to the nearest reachable point.
+        ``ValueError`` for a gate outside the classes, a fidelity outside (0, 1] and a size the family does not have."""
+        family, g, dress = approx_dress(gate)
+        f = check_basis_fidelity(basis_fidelity)
+        k_max = 2 if family == FAMILY_B else 3
+        force = -1 if cycles is None else int(cycles)
+        if cycles is not None and not 0 <= force <= k_max:
+            raise ValueError(f"cycles must be None or 0..{k_max} for this basis gate, got {cycles}")
+        count = self.n_targets - first if count is None else int(count)
+        n = max(count, 0)
+        x = np.zeros((n, 24))
+        size = np.zeros(n, dtype=np.int32)
+        loss, predicted, gap = np.zeros(n), np.zeros(n), np.zeros(n)
+        _check(self._lib.slam_approx_decompose(self._h, int(first), count, family, _ptr(g), _ptr(dress), f, force, _ptr(x), _ptr(size),
+                                               _ptr(loss), _ptr(predicted), _ptr(gap)))
+        return x, size, loss, predicted, gap
+
+    def approx_counts(self, gate, basis_fidelities, first: int = 0, count: Optional[int] = None):
+        """The selection of ``approx_decompose`` for up to ``APPROX_MAX_FID`` basis fidelities in one launch over the resident targets
+        [first, first + count) (slam_approx_counts) -> ``(counts int64[n, 4], fidsum int64[n])``: targets per chosen size, and the sum
+        of the chosen expected fidelities in units of 2^-32."""
+        family = approx_family(np.ascontiguousarray(gate, dtype=np.complex128))
+        f = np.ascontiguousarray(basis_fidelities, dtype=np.float64).reshape(-1)
+        if not 1 <= len(f) <= APPROX_MAX_FID:
+            raise ValueError(f"between 1 and {APPROX_MAX_FID} basis fidelities per call, got {len(f)}")
+        for v in f:
+            check_basis_fidelity(v)
+        count = self.n_targets - first if count is None else int(count)
+        counts = np.zeros((len(f), 4), dtype=np.int64)
+        fidsum = np.zeros(len(f), dtype=np.int64)
+        _check(self._lib.slam_approx_counts(self._h, int(first), count, family, len(f), _ptr(f), _ptr(counts), _ptr(fidsum)))
+        return counts, fidsum
 
     def metric_update_check(self, h: np.ndarray, s: np.ndarray, w: np.ndarray, v: np.ndarray):
         """Device check of the metric's rank-2 update ``H += s w^T + v s^T`` (slam_metric_update_check): ``h[n, na (na + 1) / 2, 4, 4]``

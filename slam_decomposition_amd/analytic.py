@@ -27,6 +27,16 @@ Gates of the B class, CAN(1/2, 1/4, 0): one gate for a target of that class, two
 PRL 93, 020502; ``slam_b_decompose``, csrc/slam_b.hpp).  ``decompose`` does not dispatch to it yet:
 
     res = b_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20), BerkeleyGate())
+
+All of the above assume a perfect basis gate.  ``approx_decompose`` is the other half of qiskit's ``TwoQubitBasisDecomposer``: given the
+fidelity f of one basis gate (CNOT, iSWAP or B class) it builds the best circuit of 0, 1, 2 and 3 gates in closed form and returns the
+one with the highest expected fidelity F_k f^k (``slam_approx_decompose``, csrc/slam_approx.hpp); a local target costs no gate.
+``fidelity_sweep`` asks the same question of a whole distribution for many f in one launch:
+
+    res = approx_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20), CXGate(), basis_fidelity=0.99)
+    res.cycles, res.loss, res.predicted_loss, res.expected_fidelity
+    sw = fidelity_sweep(DeviceHaarBatch(seed=7, n_samples=1 << 22), CXGate(), np.linspace(0.9, 1.0, 16))
+    sw.counts, sw.average_gates, sw.average_fidelity
 """
 from __future__ import annotations
 
@@ -67,6 +77,31 @@ class CxDecomposition(SqiswapDecomposition):
     """The same fields for circuits of ``basis_gate`` (``cycles`` 1, 2 or 3; ``gap`` is the coordinate gap left by the alignment of the
     interior circuit): ``entries()`` rows are those of ``CircuitTemplate(base_gates=[basis_gate]).build(cycles)``."""
 
+    basis_gate: object = None
+
+
+@dataclass
+class ApproxDecomposition(CxDecomposition):
+    """The fields of ``CxDecomposition`` for the circuit of highest expected fidelity (``cycles`` 0..3; a row of no gate holds one
+    layer, 6 angles; ``gap`` is the chamber distance to the nearest point that ``cycles`` gates reach), and ``predicted_loss``
+    float64[N] (1 - t_k of the closed form), ``expected_fidelity`` float64[N] ((4 + 16 (1 - loss)^2) / 20 * basis_fidelity^cycles)
+    and ``basis_fidelity``."""
+
+    predicted_loss: np.ndarray = None
+    expected_fidelity: np.ndarray = None
+    basis_fidelity: float = 1.0
+
+
+@dataclass
+class FidelitySweep:
+    """``counts`` int64[n, 4] (targets per chosen size 0..3), ``average_gates`` and ``average_fidelity`` float64[n] per entry of
+    ``basis_fidelities``, over ``n_targets`` targets."""
+
+    basis_fidelities: np.ndarray
+    counts: np.ndarray
+    average_gates: np.ndarray
+    average_fidelity: np.ndarray
+    n_targets: int
     basis_gate: object = None
 
 
@@ -136,6 +171,67 @@ def b_decompose(targets, basis_gate=None, device: int = 0, success_threshold: fl
     from .gates import BerkeleyGate
 
     return _gate_decompose(targets, BerkeleyGate() if basis_gate is None else basis_gate, _ffi.b_class, "b_decompose", device, success_threshold)
+
+
+def _approx_gate(basis_gate):
+    """``(matrix, family)`` of a gate that ``_ffi.approx_family`` accepts; ``NotImplementedError`` naming its coordinates otherwise."""
+    from . import _ffi, weyl
+
+    g = gate_matrix(basis_gate)
+    try:
+        family = _ffi.approx_family(g)
+    except ValueError:
+        raise NotImplementedError(
+            "approximate closed-form decompositions exist for basis gates of the CNOT class (0.5, 0, 0), the iSWAP class (0.5, 0.5, 0) "
+            f"and the B class (0.5, 0.25, 0) only (got {basis_gate} with Weyl coordinates {tuple(float(v) for v in weyl.c1c2c3(g))}); "
+            "no closed form for the nearest two-gate point of sqrt(iSWAP) is established here") from None
+    return g, family
+
+
+def approx_decompose(targets, basis_gate=None, basis_fidelity: float = 1.0, cycles=None, device: int = 0,
+                     success_threshold: float = 1e-10) -> ApproxDecomposition:
+    """Per target the circuit of 0, 1, 2 or 3 gates ``basis_gate`` (default ``CXGate()``; any gate of the CNOT, the iSWAP or the B
+    class, which has no 3) with the highest expected fidelity F_k * basis_fidelity^k, F_k the average gate fidelity of the best circuit
+    of k gates -- what qiskit's ``TwoQubitBasisDecomposer(gate, basis_fidelity)`` chooses; ties go to fewer gates, so
+    ``basis_fidelity=1`` gives the fewest gates that equal the target and no gate for a local one.  ``cycles=k`` takes that size for
+    every target.  ``targets`` are given as for ``sqiswap_decompose``.  ``NotImplementedError`` for ``RiSwapGate(1/2)`` and every other
+    gate outside the three classes, ``ValueError`` for a fidelity outside (0, 1] and a size the gate's class does not have."""
+    from . import _ffi
+
+    basis_gate = CXGate() if basis_gate is None else basis_gate
+    g, family = _approx_gate(basis_gate)
+    f = _ffi.check_basis_fidelity(basis_fidelity)
+    k_max = 2 if family == _ffi.FAMILY_B else 3
+    if cycles is not None and not (isinstance(cycles, (int, np.integer)) and 0 <= cycles <= k_max):
+        raise ValueError(f"cycles must be None or an integer in 0..{k_max} for {basis_gate}, got {cycles!r}")
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
+    if n == 0:
+        return _empty(ApproxDecomposition, success_threshold, basis_gate, np.zeros(0), np.zeros(0), f)
+    x, size, loss, predicted, gap = ctx.approx_decompose(g, f, cycles, 0, n)
+    expected = (4.0 + 16.0 * (1.0 - loss) ** 2) / 20.0 * f ** size
+    return ApproxDecomposition(size, x, loss, gap, success_threshold, basis_gate, predicted, expected, f)
+
+
+def fidelity_sweep(targets, basis_gate, basis_fidelities, device: int = 0) -> FidelitySweep:
+    """The Haar-expected (or any distribution's) gate count and fidelity of ``basis_gate`` at each of ``basis_fidelities`` (at most
+    ``_ffi.APPROX_MAX_FID``), from one launch over ``targets`` (``slam_approx_counts``): the choice of ``approx_decompose`` per target
+    and fidelity, counted per size, and the mean of the chosen expected fidelities (summed in fixed point, 2^-32: the result does not
+    depend on the order of addition).  Refusals as ``approx_decompose``."""
+    from . import _ffi
+
+    g, _ = _approx_gate(basis_gate)
+    f = np.ascontiguousarray(basis_fidelities, dtype=np.float64).reshape(-1)
+    if not 1 <= len(f) <= _ffi.APPROX_MAX_FID:
+        raise ValueError(f"between 1 and {_ffi.APPROX_MAX_FID} basis fidelities per call, got {len(f)}")
+    for v in f:
+        _ffi.check_basis_fidelity(v)
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
+    if n == 0:
+        return FidelitySweep(f, np.zeros((len(f), 4), dtype=np.int64), np.full(len(f), np.nan), np.full(len(f), np.nan), 0, basis_gate)
+    counts, fidsum = ctx.approx_counts(g, f, 0, n)
+    return FidelitySweep(f, counts, counts @ np.arange(4.0) / n, fidsum / 4294967296.0 / n, n, basis_gate)
 
 
 def decompose(targets, basis_gate, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:

@@ -1,12 +1,15 @@
 // slam_analytic.hip -- host side of libslamhip.so, analytic unit: the closed-form decompositions into sqrt(iSWAP) gates
-// (slam_analytic.hpp), into gates of the CNOT or the iSWAP class (slam_cx.hpp) and into gates of the B class (slam_b.hpp).
+// (slam_analytic.hpp), into gates of the CNOT or the iSWAP class (slam_cx.hpp) and into gates of the B class (slam_b.hpp), and the
+// fidelity-aware approximate decomposition into gates of those three classes (slam_approx.hpp).
 #include "slam_host.hpp"
 
 #include <complex>
+#include <type_traits>
 
 #include "slam_analytic.hpp"
 #include "slam_cx.hpp"
 #include "slam_b.hpp"
+#include "slam_approx.hpp"
 
 // ---- slam_cx_decompose, slam_b_decompose: the host's share (plain C++) -------------------------------------------------------------------
 namespace {
@@ -168,12 +171,18 @@ int b_fold_dress(const double* gate, const double* dress, double* table) {
     return SLAM_OK;
 }
 
-// What the three entry points do once their own arguments are checked: the context and the window, the buffers, the kernel's table
+// an argument block with a third double per target, `predicted` (slam_approx.hpp)
+template <class Args, class = void>
+struct has_predicted : std::false_type {};
+template <class Args>
+struct has_predicted<Args, std::void_t<decltype(std::declval<Args&>().predicted)>> : std::true_type {};
+
+// What the entry points do once their own arguments are checked: the context and the window, the buffers, the kernel's table
 // (n_table doubles, the gate and the interior factors; none for sqrt(iSWAP)) into ev_x, the launch and the read-backs, any of which
 // may be NULL.  `own` fills the fields that only this family's argument block has, given the table's device address.
 template <class Args, class Own>
 int run_closed_form(slam_ctx* ctx, int64_t first, int64_t count, void (*kernel)(Args), const double* table, size_t n_table, Own own,
-                    double* x_out, int32_t* cycles, double* loss, double* gap) {
+                    double* x_out, int32_t* cycles, double* loss, double* gap, double* predicted = nullptr) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
     if (first < 0 || count < 0 || first + count > ctx->n_targets)
         return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
@@ -181,7 +190,8 @@ int run_closed_form(slam_ctx* ctx, int64_t first, int64_t count, void (*kernel)(
     if (count == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(ctx->ev_grad.reserve((size_t)count * 24 * sizeof(double)));  // the rows
-    HIP_TRY(ctx->ev_loss.reserve((size_t)count * 2 * sizeof(double)));   // losses, then gaps
+    constexpr size_t per_target = has_predicted<Args>::value ? 3 : 2;
+    HIP_TRY(ctx->ev_loss.reserve((size_t)count * per_target * sizeof(double)));  // losses, then gaps (then predicted losses)
     HIP_TRY(ctx->ev_tof.reserve((size_t)count * sizeof(int32_t)));       // sizes
     if (table) {
         HIP_TRY(ctx->ev_x.reserve(n_table * sizeof(double)));
@@ -195,14 +205,26 @@ int run_closed_form(slam_ctx* ctx, int64_t first, int64_t count, void (*kernel)(
     a.cycles = ctx->ev_tof.as<int32_t>();
     a.loss = ctx->ev_loss.as<double>();
     a.gap = ctx->ev_loss.as<double>() + count;
+    if constexpr (has_predicted<Args>::value) a.predicted = ctx->ev_loss.as<double>() + 2 * count;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((count + kKakBlock - 1) / kKakBlock)), dim3(kKakBlock), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     if (x_out) HIP_TRY(hipMemcpyAsync(x_out, a.x_out, (size_t)count * 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (cycles) HIP_TRY(hipMemcpyAsync(cycles, a.cycles, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (loss) HIP_TRY(hipMemcpyAsync(loss, a.loss, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (gap) HIP_TRY(hipMemcpyAsync(gap, a.gap, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if constexpr (has_predicted<Args>::value)
+        if (predicted) HIP_TRY(hipMemcpyAsync(predicted, a.predicted, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return SLAM_OK;
+}
+
+// The family's table for the approximate kernels: the gate and the interior factors, checked and folded as the exact siblings do.
+int approx_table(int family, const double* gate, const double* dress, double* table, size_t* n_table) {
+    if (family < 0 || family > 2)
+        return fail(SLAM_ERR_INVALID, "family must be 0 (CNOT class), 1 (iSWAP class) or 2 (B class), got %d", family);
+    if (!gate || !dress) return fail(SLAM_ERR_INVALID, "gate and dress are required");
+    *n_table = family == 2 ? kBTable : kCxTable;
+    return family == 2 ? b_fold_dress(gate, dress, table) : cx_fold_dress(family, gate, dress, table);
 }
 
 }  // namespace
@@ -234,6 +256,63 @@ int slam_cx_decompose(slam_ctx* ctx, int64_t first, int64_t count, int family, c
 
 int slam_sqiswap_decompose(slam_ctx* ctx, int64_t first, int64_t count, double* x_out, int32_t* cycles, double* loss, double* gap) {
     return run_closed_form(ctx, first, count, sqiswap_decompose_kernel, nullptr, 0, [](AnalyticArgs&, const double*) {}, x_out, cycles, loss, gap);
+}
+
+int slam_approx_decompose(slam_ctx* ctx, int64_t first, int64_t count, int family, const double* gate, const double* dress,
+                          double basis_fidelity, int force_cycles, double* x_out, int32_t* cycles, double* loss, double* predicted,
+                          double* gap) {
+    static_assert(kCxTable >= kBTable, "one table buffer for the three families");
+    double table[kCxTable];
+    size_t n_table = 0;
+    const int rc = approx_table(family, gate, dress, table, &n_table);
+    if (rc) return rc;
+    if (!(basis_fidelity > 0.0 && basis_fidelity <= 1.0))  // a NaN fails both
+        return fail(SLAM_ERR_INVALID, "basis_fidelity must be in (0, 1], got %g", basis_fidelity);
+    const int k_max = family == 2 ? 2 : 3;
+    if (force_cycles < -1 || force_cycles > k_max)
+        return fail(SLAM_ERR_INVALID, "force_cycles must be -1 (select) or 0..%d for family %d, got %d", k_max, family, force_cycles);
+    return run_closed_form(
+        ctx, first, count, approx_decompose_kernel, table, n_table,
+        [=](ApproxArgs& a, const double* t) { a.table = t, a.family = family, a.force = force_cycles, a.fidelity = basis_fidelity; }, x_out,
+        cycles, loss, gap, predicted);
+}
+
+int slam_approx_counts(slam_ctx* ctx, int64_t first, int64_t count, int family, int32_t n_fid, const double* fidelities,
+                       int64_t* counts_out, int64_t* fidsum_out) {
+    if (family < 0 || family > 2)
+        return fail(SLAM_ERR_INVALID, "family must be 0 (CNOT class), 1 (iSWAP class) or 2 (B class), got %d", family);
+    if (n_fid < 1 || n_fid > kApproxMaxFid) return fail(SLAM_ERR_INVALID, "n_fid must be in 1..%d, got %d", kApproxMaxFid, n_fid);
+    if (!fidelities) return fail(SLAM_ERR_INVALID, "fidelities is NULL");
+    for (int32_t j = 0; j < n_fid; ++j)
+        if (!(fidelities[j] > 0.0 && fidelities[j] <= 1.0))
+            return fail(SLAM_ERR_INVALID, "fidelities[%d] must be in (0, 1], got %g", j, fidelities[j]);
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (counts_out) std::memset(counts_out, 0, (size_t)n_fid * 4 * sizeof(int64_t));
+    if (fidsum_out) std::memset(fidsum_out, 0, (size_t)n_fid * sizeof(int64_t));
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_x.reserve((size_t)n_fid * sizeof(double)));
+    HIP_TRY(ctx->ev_loss.reserve((size_t)n_fid * 5 * sizeof(unsigned long long)));  // counts [n_fid][4], then sums [n_fid]
+    HIP_TRY(hipMemcpy(ctx->ev_x.p, fidelities, (size_t)n_fid * sizeof(double), hipMemcpyHostToDevice));  // the caller's array: done before the call goes on
+    HIP_TRY(hipMemsetAsync(ctx->ev_loss.p, 0, (size_t)n_fid * 5 * sizeof(unsigned long long), ctx->stream));
+    ApproxCountsArgs a{};
+    a.targets = ctx->targets.as<double>() + first * 32;
+    a.fidelities = ctx->ev_x.as<double>();
+    a.M = count;
+    a.family = family;
+    a.n_fid = n_fid;
+    a.counts = ctx->ev_loss.as<unsigned long long>();
+    a.fidsum = a.counts + (size_t)n_fid * 4;
+    hipLaunchKernelGGL(approx_counts_kernel, dim3((unsigned)((count + kApproxCountsBlock - 1) / kApproxCountsBlock)), dim3(kApproxCountsBlock),
+                       0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_fid * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (fidsum_out) HIP_TRY(hipMemcpyAsync(fidsum_out, a.fidsum, (size_t)n_fid * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
 }
 
 }  // extern "C"

@@ -100,6 +100,18 @@ int main() {
         for (double& v : bad) v = 0.0;
         bad[96] = 0.5;
         EXPECT(slam_cx_decompose(nullptr, 0, 1, 0, cx_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);  // all-zero factors
+        // slam_approx_decompose: the same check and fold, then its own arguments, then the context
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 0, cx_gate, cx_dress, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 0, cx_gate, cx_dress, 1.0, 3, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 3, cx_gate, cx_dress, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "family") != nullptr);
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 0, cx_gate, bad, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 0, cx_gate, cx_dress, 0.0, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "basis_fidelity") != nullptr);
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 0, cx_gate, cx_dress, 0.99, 4, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "force_cycles") != nullptr);
     }
     {  // slam_b_decompose likewise: BerkeleyGate and its reduction as Context.b_decompose computes it (_ffi.b_dress)
         const double s = 0.38268343236508984, c = 0.9238795325112867;
@@ -131,6 +143,18 @@ int main() {
         bad[32] = 0.5;
         bad[33] = 0.25;
         EXPECT(slam_b_decompose(nullptr, 0, 1, b_gate, bad, d, i32, d, d) == SLAM_ERR_INVALID);  // all-zero factors
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 2, b_gate, b_dress, 0.99, 2, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 2, b_gate, b_dress, 0.99, 3, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "force_cycles") != nullptr);
+        EXPECT(slam_approx_decompose(nullptr, 0, 1, 2, b_gate, bad, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        const double fid[2] = {0.9, 1.0}, bad_fid[2] = {0.9, 1.5};
+        EXPECT(slam_approx_counts(nullptr, 0, 1, 2, 2, fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_approx_counts(nullptr, 0, 1, 2, 2, bad_fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "fidelities[1]") != nullptr);
+        EXPECT(slam_approx_counts(nullptr, 0, 1, 2, 65, fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(slam_approx_counts(nullptr, 0, 1, 3, 2, fid, &i64, &i64) == SLAM_ERR_INVALID);
     }
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
