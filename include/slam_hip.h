@@ -396,6 +396,29 @@ int slam_family_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_me
                        int64_t* base_counts_out, int32_t* member_out, int32_t* gates_out);
 
 /*
+ * Candidate basis-gate scores on the device (collect_data, src/slam/utils/gates/bare_candidates.py:75-126, for a whole grid of
+ * candidates at once): for every candidate gate g and every resident target t of [first, first + count) the smallest k in 1 .. k_cap
+ * such that k applications of g, with free local gates in between, reach t -- coverage.contains(t, [g] * k, tol): the alcove-point match
+ * of slam_coverage_lookup kind 0 for k = 1, the 14 half-spaces of kind 1 for k >= 2; either alcove point of the target's class may
+ * match.  The device derives every row from the candidate's three coordinates (the max-plus recurrence of coverage._region with the
+ * degree folded into the weight, csrc/slam_candidates.hpp): no table comes from the caller.
+ *   cand_coords  double[n_candidates][3]  Weyl coordinates in units of pi (weyl.c1c2c3); 1 <= n_candidates <= SLAM_CANDIDATE_MAX_GATES
+ *   k_cap        1 .. SLAM_CANDIDATE_MAX_K
+ *   tol          widens the regions (units of pi), as in slam_coverage_lookup
+ *   group_of     int32[count] or NULL: the group (0 .. n_groups - 1) of every target of the window; NULL = one group (n_groups = 1)
+ * counts_out    int64[n_groups][n_candidates][k_cap + 2]: bin k - 1 = targets first reached at k; bin k_cap = local targets (no gate);
+ *               bin k_cap + 1 = targets not reached within k_cap.  A local candidate reaches no non-local target.
+ * first_k_out   int32[n_candidates][count] or NULL: k per (candidate, target); 0 = local target, k_cap + 1 = not reached.
+ * kernel_ms_out double* or NULL: device time of the call's two kernels (events on the context's stream).
+ * Integer counts: the result does not depend on the launch geometry, the window or the order in which the device adds them up.
+ */
+#define SLAM_CANDIDATE_MAX_K 64
+#define SLAM_CANDIDATE_MAX_GATES 65536
+int slam_candidate_scores(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_candidates, const double* cand_coords, int32_t k_cap,
+                          double tol, const int32_t* group_of, int32_t n_groups, int64_t* counts_out, int32_t* first_k_out,
+                          double* kernel_ms_out);
+
+/*
  * Parallel-drive coverage (the sampling half of src/slam/utils/gates/parallel_drive_volume.py:176-256; csrc/slam_pd.hpp).
  *
  * slam_pd_sample: n_samples random templates of k ConversionGainSmushGate(pc, pg, gc, gg, gx[0:N], gy[0:N], t), N = n_slices, with a
@@ -846,7 +869,8 @@ const char* slam_version(void);
  *      later: slam_cx_decompose (a new symbol only);
  *      later: slam_b_decompose (a new symbol only);
  *      later: slam_family_lookup (a new symbol only);
- *      later: slam_approx_decompose and slam_approx_counts (new symbols only).
+ *      later: slam_approx_decompose and slam_approx_counts (new symbols only);
+ *      later: slam_candidate_scores (a new symbol only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

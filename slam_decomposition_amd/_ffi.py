@@ -43,6 +43,8 @@ PD_MAX_DIRS = 1024  # SLAM_PD_MAX_DIRS
 REGION_MAX = 256  # SLAM_REGION_MAX
 FAMILY_MAX_MEMBERS = 32  # SLAM_FAMILY_MAX_MEMBERS
 FAMILY_MAX_BINS = 8192  # slam_family_lookup: E + E_0 + 4 histogram bins at most
+CANDIDATE_MAX_K = 64  # SLAM_CANDIDATE_MAX_K
+CANDIDATE_MAX_GATES = 65536  # SLAM_CANDIDATE_MAX_GATES
 POLICY_REFERENCE, POLICY_BEST = 0, 1  # slam_family_lookup: the reference's walk / the cheapest member
 
 # every symbol include/slam_hip.h declares (checked by tests/test_abi.py)
@@ -70,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "slam_predict_spans",
     "slam_coverage_lookup",
     "slam_family_lookup",
+    "slam_candidate_scores",
     "slam_eval_c1c2c3",
     "slam_sample_haar",
     "slam_sample_haar_indexed",
@@ -253,6 +256,8 @@ def load_library() -> C.CDLL:
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
     if hasattr(lib, "slam_family_lookup"):
         lib.slam_family_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32] + [P] * 7 + [C.c_double, C.c_double, C.c_int32] + [P] * 4
+    if hasattr(lib, "slam_candidate_scores"):
+        lib.slam_candidate_scores.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, C.c_int32, C.c_double, P, C.c_int32, P, P, P]
     lib.slam_eval_c1c2c3.argtypes = [P, C.c_int32, P, P, C.c_int64, C.c_int32, P]
     lib.slam_sample_haar.argtypes = [P, C.c_uint64, C.c_int64, C.c_int64]
     if hasattr(lib, "slam_haar_select_spans"):
@@ -888,6 +893,35 @@ class Context:
                                             _ptr(bounds), _ptr(ce), _ptr(co), _ptr(d), c1q, float(tol), pol, _ptr(counts), _ptr(base_counts),
                                             _ptr(members), _ptr(gates)))
         return counts, base_counts, members, gates
+
+    def candidate_scores(self, coords, k_cap: int, groups=None, n_groups: int = 1, first: int = 0, count: Optional[int] = None,
+                         want_first: bool = False, tol: float = 1e-7):
+        """First number of applications of every candidate gate that reaches each resident target of [first, first + count)
+        (slam_candidate_scores; the device derives the coverage rows from ``coords`` [G, 3], Weyl coordinates in units of pi).
+        ``groups``: int32[count] group of every target of the window (None: one group).  Returns ``(counts, first_k)``:
+        int64 [n_groups, G, k_cap + 2] -- bin k - 1 targets first reached at k, bin ``k_cap`` local targets, bin ``k_cap + 1`` targets
+        not reached -- and, with ``want_first``, int32 [G, count] (k; 0 local; ``k_cap + 1`` not reached), else None.  The device time
+        of the call's kernels is left in ``self.last_candidate_kernel_ms``."""
+        c = np.ascontiguousarray(coords, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != 3 or c.shape[0] < 1:
+            raise ValueError("coords must be [G, 3] with G >= 1")
+        count = self.n_targets - first if count is None else int(count)
+        g = None
+        if groups is not None:
+            g = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+            if g.size != max(count, 0):
+                raise ValueError(f"groups has {g.size} entries for a window of {count} targets")
+        elif int(n_groups) != 1:
+            raise ValueError("n_groups != 1 needs groups")
+        if int(n_groups) < 1:
+            raise ValueError("n_groups must be >= 1")
+        counts = np.zeros((int(n_groups), c.shape[0], max(int(k_cap), 0) + 2), dtype=np.int64)
+        first_k = np.zeros((c.shape[0], max(count, 0)), dtype=np.int32) if want_first else None
+        ms = C.c_double(0.0)
+        _check(self._lib.slam_candidate_scores(self._h, int(first), int(count), c.shape[0], _ptr(c), int(k_cap), float(tol), _ptr(g),
+                                               int(n_groups), _ptr(counts), _ptr(first_k), C.byref(ms)))
+        self.last_candidate_kernel_ms = float(ms.value)
+        return counts, first_k
 
     # -- parallel-drive coverage (slam_pd_*, slam_region_lookup) --------------------------------------------------------------------------
     def pd_sample(self, gc: float, gg: float, t: float, n_slices: int, k: int, n_samples: int, seed: int = 0, bound: float = 4 * np.pi,

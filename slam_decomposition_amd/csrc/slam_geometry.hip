@@ -1,11 +1,12 @@
 // slam_geometry.hip -- host side of libslamhip.so, geometry unit: Weyl coordinates, span prediction, coverage and family lookups, the Haar
-// sampler and its selection by template size, parallel-drive coverage samples and region lookups, the KAK decomposition and
+// sampler and its selection by template size, candidate basis-gate scores (slam_candidates.hpp), parallel-drive coverage samples and region lookups, the KAK decomposition and
 // local-gate completion (slam_weyl.hpp, slam_sampler.hpp, slam_span_sampler.hpp, slam_pd.hpp, slam_kak.hpp; their kernels in
 // slam_span_sampler.hpp and slam_geometry_kernels.hpp).
 #include "slam_host.hpp"
 #include "slam_sampler.hpp"
 #include "slam_span_sampler.hpp"
 #include "slam_geometry_kernels.hpp"
+#include "slam_candidates.hpp"
 
 int enqueue_c1c2c3(slam_ctx* c, const double* d_unitaries, int64_t count, int ndigits, double* d_out) {
     hipLaunchKernelGGL(c1c2c3_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_unitaries, count, ndigits, d_out);
@@ -319,6 +320,88 @@ int slam_family_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_me
     if (member_out) HIP_TRY(hipMemcpyAsync(member_out, d_member, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (gates_out) HIP_TRY(hipMemcpyAsync(gates_out, d_member + count, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
+int slam_candidate_scores(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_candidates, const double* cand_coords, int32_t k_cap,
+                          double tol, const int32_t* group_of, int32_t n_groups, int64_t* counts_out, int32_t* first_k_out,
+                          double* kernel_ms_out) {
+    static_assert(SLAM_CANDIDATE_MAX_K == kCandMaxK, "candidate k_cap");
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (n_candidates < 1 || n_candidates > SLAM_CANDIDATE_MAX_GATES)
+        return fail(SLAM_ERR_INVALID, "n_candidates must be in 1..%d (got %d)", SLAM_CANDIDATE_MAX_GATES, n_candidates);
+    if (k_cap < 1 || k_cap > SLAM_CANDIDATE_MAX_K) return fail(SLAM_ERR_INVALID, "k_cap must be in 1..%d (got %d)", SLAM_CANDIDATE_MAX_K, k_cap);
+    if (!cand_coords) return fail(SLAM_ERR_INVALID, "cand_coords is NULL");
+    for (int64_t j = 0; j < 3 * (int64_t)n_candidates; ++j)
+        if (!std::isfinite(cand_coords[j])) return fail(SLAM_ERR_INVALID, "cand_coords[%lld] is not finite", (long long)j);
+    if (!std::isfinite(tol)) return fail(SLAM_ERR_INVALID, "tol must be finite");
+    if (n_groups < 1) return fail(SLAM_ERR_INVALID, "n_groups must be >= 1 (got %d)", n_groups);
+    if (!group_of && n_groups != 1) return fail(SLAM_ERR_INVALID, "n_groups = %d needs group_of", n_groups);
+    if (group_of)
+        for (int64_t i = 0; i < count; ++i)
+            if (group_of[i] < 0 || group_of[i] >= n_groups)
+                return fail(SLAM_ERR_INVALID, "group_of[%lld] = %d outside [0, %d)", (long long)i, group_of[i], n_groups);
+    if (!counts_out) return fail(SLAM_ERR_INVALID, "counts_out is NULL");
+    const int64_t G = n_candidates, nb = (int64_t)k_cap + 2;
+    const int64_t n_counts = (int64_t)n_groups * G * nb;
+    if (n_counts > ((int64_t)1 << 31)) return fail(SLAM_ERR_INVALID, "n_groups x n_candidates x (k_cap + 2) = %lld counts: too many", (long long)n_counts);
+    std::memset(counts_out, 0, (size_t)n_counts * sizeof(int64_t));
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // one buffer: coordinates [G][3], alcove points [G][4], rows [G][k_cap - 1][14] (doubles), then the groups (int32)
+    const size_t pt_b = (size_t)G * 3 * sizeof(double), row_b = pt_b + (size_t)G * 4 * sizeof(double);
+    const size_t grp_b = row_b + (size_t)G * (size_t)(k_cap - 1) * kSpanPatterns * sizeof(double);
+    const size_t total_b = grp_b + (group_of ? (size_t)count * sizeof(int32_t) : 0);
+    HIP_TRY(ctx->cov_table.reserve(total_b));
+    HIP_TRY(ctx->cov_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
+    if (first_k_out) HIP_TRY(ctx->cov_entries.reserve((size_t)G * (size_t)count * sizeof(int32_t)));
+    char* tb = ctx->cov_table.as<char>();
+    HIP_TRY(hipMemcpyAsync(tb, cand_coords, pt_b, hipMemcpyHostToDevice, ctx->stream));
+    if (group_of) HIP_TRY(hipMemcpyAsync(tb + grp_b, group_of, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->cov_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (kernel_ms_out) {
+        HIP_TRY(hipEventCreate(&ev0));
+        if (hipError_t e = hipEventCreate(&ev1); e != hipSuccess) {
+            (void)hipEventDestroy(ev0);
+            HIP_TRY(e);
+        }
+        (void)hipEventRecord(ev0, ctx->stream);
+    }
+    hipLaunchKernelGGL(candidate_rows_kernel, dim3((unsigned)((G + kCandRowsBlock - 1) / kCandRowsBlock)), dim3(kCandRowsBlock), 0, ctx->stream,
+                       reinterpret_cast<const double*>(tb), (int32_t)G, k_cap, reinterpret_cast<double*>(tb + pt_b),
+                       reinterpret_cast<double*>(tb + row_b));
+    // candidates split over grid.y until the launch has about 2048 blocks: a circuit's few hundred targets still fill the device,
+    // a large batch keeps one chunk (the target's Weyl coordinates are computed once per block)
+    const int64_t t_blocks = (count + kCandBlock - 1) / kCandBlock;
+    int64_t n_chunks = (2048 + t_blocks - 1) / t_blocks;
+    const int64_t max_chunks = (G + 7) / 8;
+    if (n_chunks > max_chunks) n_chunks = max_chunks;
+    const int32_t chunk = (int32_t)((G + n_chunks - 1) / n_chunks);
+    n_chunks = (G + chunk - 1) / chunk;
+    hipLaunchKernelGGL(candidate_scores_kernel, dim3((unsigned)t_blocks, (unsigned)n_chunks), dim3(kCandBlock), 0, ctx->stream,
+                       ctx->targets.as<double>() + first * 32, count, (int32_t)G, chunk, k_cap, reinterpret_cast<const double*>(tb + pt_b),
+                       reinterpret_cast<const double*>(tb + row_b), tol, group_of ? reinterpret_cast<const int32_t*>(tb + grp_b) : nullptr,
+                       ctx->cov_counts.as<unsigned long long>(), first_k_out ? ctx->cov_entries.as<int32_t>() : nullptr);
+    const hipError_t launch_err = hipGetLastError();
+    if (kernel_ms_out) (void)hipEventRecord(ev1, ctx->stream);
+    hipError_t err = launch_err;
+    if (err == hipSuccess) err = hipMemcpyAsync(counts_out, ctx->cov_counts.p, (size_t)n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess && first_k_out)
+        err = hipMemcpyAsync(first_k_out, ctx->cov_entries.p, (size_t)G * (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    if (kernel_ms_out) {
+        float ms = 0.0f;
+        if (err == hipSuccess) err = hipEventElapsedTime(&ms, ev0, ev1);
+        *kernel_ms_out = (double)ms;
+        (void)hipEventDestroy(ev0);
+        (void)hipEventDestroy(ev1);
+    }
+    HIP_TRY(err);
     return SLAM_OK;
 }
 

@@ -159,6 +159,8 @@ int main() {
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_family_lookup(nullptr, 0, 1, 1, i32, i32, d, d, i32, i32, d, 0.1, 1e-7, 0, &i64, &i64, i32, i32) == SLAM_ERR_INVALID);
+    EXPECT(slam_candidate_scores(nullptr, 0, 1, 1, d, 8, 1e-7, nullptr, 1, &i64, i32, nullptr) == SLAM_ERR_INVALID);
+    EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
     EXPECT(slam_pd_sample(nullptr, 1.0, 0.0, 1.0, 4, 1, 1.0, 0, 0, 1, nullptr, 8, d, nullptr, nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_pd_extremes(nullptr, d, 1, &i64, d) == SLAM_ERR_INVALID);
     EXPECT(slam_pd_filter(nullptr, d, 1, 0.0, 0, &i64, nullptr, nullptr) == SLAM_ERR_INVALID);

@@ -9,7 +9,8 @@ of gates a target needs (``coverage_to_haar_expectation``, src/slam/utils/polyto
 (``monodromy_range_from_target``, polytope_wrap.py:39-94).  With ``coverage.py`` the regions of ANY number of applications of a gate are
 14 half-spaces each, so the three scores are a few comparisons per (gate, k) -- no optimisation, no polytope library:
 
-* ``build_gates``  the reference's candidate grid, duplicates of a Weyl class removed the same way;
+* ``build_gates``  the reference's candidate grid, duplicates of a Weyl class removed the same way (now defined in
+  ``slam_decomposition_amd.candidates``, which answers the same questions for all candidates in one device call);
 * ``gate_scores``  (haar_score, cnot_score, swap_score, volumes) of one gate: volumes over a common set of Haar targets (their
   half-space sums are computed once and shared by all gates and all k), exact membership for the two named targets;
 * ``score_gates``  the sweep.
@@ -28,31 +29,12 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from slam_decomposition_amd import coverage  # noqa: E402
+from slam_decomposition_amd.candidates import build_gates  # noqa: E402,F401  (the product's grid: one definition)
 from slam_decomposition_amd.gates import ConversionGainGate, gate_matrix  # noqa: E402
 from slam_decomposition_amd.weyl import c1c2c3  # noqa: E402
 
 CNOT_COORDS = (0.5, 0.0, 0.0)
 SWAP_COORDS = (0.5, 0.5, 0.5)
-
-
-def build_gates(elim_extra_weyl: bool = True) -> Tuple[List[ConversionGainGate], List[list]]:
-    """bare_candidates.py:47-69: ``ConversionGainGate(0, 0, p k pi, (1 - p) k pi)`` for 17 strengths k in [0, 1/2] x 21 splits p in
-    [0, 1], skipping a gate whose Weyl coordinates (c1 folded to <= 1/2) were seen before.  Returns (gates, coordinates per strength)."""
-    unitary_list: List[ConversionGainGate] = []
-    coordinate_list: List[list] = []
-    for k in np.linspace(0, 0.5, 17):
-        inner_list: list = []
-        for p in np.linspace(0, 1, 21):
-            gate = ConversionGainGate(0, 0, p * k * np.pi, (1 - p) * k * np.pi)
-            c = list(c1c2c3(gate.to_matrix()))
-            if elim_extra_weyl and c[0] > 0.5:
-                c[0] = -1 * c[0] + 1
-            if c in inner_list or any(c in inner for inner in coordinate_list):
-                continue
-            inner_list.append(c)
-            unitary_list.append(gate)
-        coordinate_list.append(inner_list)
-    return unitary_list, coordinate_list
 
 
 def haar_targets(n: int, seed: int = 0) -> np.ndarray:
