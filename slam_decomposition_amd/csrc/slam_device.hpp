@@ -642,6 +642,43 @@ __device__ __forceinline__ int theta_slot_bits(int q) {
     return bits;
 }
 
+// Register budget of the optimizer kernels.  Span 1 shares a SIMD with another span-1 wavefront, with span 2 (248 registers) or with
+// span 3 (256 + 14, 272 allocated): it may hold 240 and keep every pairing.  The span-1 kernels of the per-span and multi-queue launches (WL: the
+// one-wavefront span loop has its own, tighter budget) spend part of that on values that depend on neither the item nor the round and that the tighter
+// kernels re-materialise in every evaluation (EvalLaneConsts).  Everything taken under this switch moves an instruction out of the
+// loop and changes no floating-point operation.
+template <int K, int GC, bool MQ, bool WL>
+__host__ __device__ constexpr bool roomy_regs() {
+    return K == 1 && !WL;
+}
+
+// The evaluation's kernel-lifetime lane constants, formed once before the round loop (ROOMY instantiations of eval_quad only) and
+// pinned in registers there (the empty asm: the compiler may not fold them back into their uses).
+template <int NA>
+struct EvalLaneConsts {
+    int hexp[NA];         // v_ldexp_f64 exponent of slot a: -1 where parameter 4a + q is a theta (half angle), else 0
+    double e0[2], e1[2];  // the lane's unit vector e_q as real pairs per qubit: (1 - bit, bit)
+    double s1, c1;        // the sine / cosine polynomials' middle literals: addends beside another literal, so one of the two has to
+                          // be in a vector register (a v_mov_b64 per evaluation otherwise)
+    double c0;            // the cost map's constant coefficient (1 for BasicCost, 1.6 for SquareCost), an addend beside c1 / d1
+};
+template <int K>
+__device__ __forceinline__ void eval_lane_consts(int q, int cost_kind, EvalLaneConsts<Cfg<K>::NA>& lc) {
+    const int theta_bits = theta_slot_bits<K>(q);
+#pragma unroll
+    for (int a = 0; a < Cfg<K>::NA; ++a) {
+        lc.hexp[a] = __builtin_amdgcn_sbfe(theta_bits, a, 1);
+        asm volatile("" : "+v"(lc.hexp[a]));
+    }
+    lc.e0[0] = (q & 1) ? 0.0 : 1.0; lc.e0[1] = (q & 1) ? 1.0 : 0.0;
+    lc.e1[0] = (q & 2) ? 0.0 : 1.0; lc.e1[1] = (q & 2) ? 1.0 : 0.0;
+    const SincosLits L = sincos_lits();
+    lc.s1 = L.s1;
+    lc.c1 = L.c1;
+    lc.c0 = (cost_kind == 1) ? 1.6 : 1.0;
+    asm volatile("" : "+v"(lc.e0[0]), "+v"(lc.e0[1]), "+v"(lc.e1[0]), "+v"(lc.e1[1]), "+v"(lc.s1), "+v"(lc.c1), "+v"(lc.c0));
+}
+
 // ---------------------------------------------------------------------------------
 // MakhlinFunctionalCost (cost_function.py:219-221, weylchamber's J_T_LI, unrounded): J(W; T) = |g(W) - g(T)|^2 with the local
 // invariants g = (Re G1, Im G1, Re G2) of Makhlin in the form without a basis change:
@@ -837,15 +874,19 @@ __device__ __forceinline__ void mk_loss_seed(const double (&wr)[4], const double
 // below that (x0 in [0, 2 pi) or validated by the host, steps <= 2 rad) and instantiates false, so no
 // function call -- and none of the register save/restore traffic a call site drags in -- sits in its loop.
 // MK: MakhlinFunctionalCost instead (cost_kind is ignored, the target column is not read): mkt = the target's invariants g(T)
-template <int K, bool HUGE_ARGS, int GC, bool MK = false>
+// ROOMY (roomy_regs): the lane constants come in through lc, formed once per kernel (theta_bits is not looked at; cost_kind only
+// for the two coefficients that stay scalar)
+template <int K, bool HUGE_ARGS, int GC, bool MK = false, bool ROOMY = false>
 __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const double* tcol,
                                           const double* gates, double* xq, double2* fh, const double2* tbl,
                                           int q, int theta_bits, int cost_kind, double& fout, double (&gd)[Cfg<K>::NA],
-                                          double (&Wr)[4], double (&Wi)[4], const double* mkt = nullptr) {
+                                          double (&Wr)[4], double (&Wi)[4], const double* mkt = nullptr,
+                                          const EvalLaneConsts<Cfg<K>::NA>* lc = nullptr) {
     constexpr bool LEAN = lean_layout<K, GC>();
     constexpr bool PSQ = psq_layout<K, GC>();
     using C = Cfg<K, PSQ>;
-    asm volatile("" : "+v"(theta_bits));  // one register, not NA hoisted lane masks
+    static_assert(!ROOMY || (!HUGE_ARGS && !MK), "the hoisted lane constants: the optimizer's BasicCost / SquareCost evaluation only");
+    if constexpr (!ROOMY) asm volatile("" : "+v"(theta_bits));  // one register, not NA hoisted lane masks
     // this quad's trig table (Cfg::TOFF): offsets (0, 4, 2, 6) doubles for quad mod 4 = 0..3
     double* const xt = xq + (PSQ ? (int)((threadIdx.x & 4) + ((threadIdx.x >> 2) & 2)) : 0);
     auto HS = [](int j) constexpr { return LEAN ? j : 2 * j + 1; };  // fh slot of the layer output h_j
@@ -878,13 +919,18 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
             double rr[C::NA];
             int kk[C::NA];
             double2 tt[C::NA];
-            const SincosLits L = sincos_lits_device();
+            SincosLits L = sincos_lits_device();
+            if constexpr (ROOMY) { L.s1 = lc->s1; L.c1 = lc->c1; }
 #pragma unroll
             for (int a = 0; a < C::NA; ++a) {
                 // theta slots take the half angle: bit a of theta_bits is set when parameter 4a + q is a theta -> exponent
                 // -1 (sign-extended bit-field extract) for v_ldexp_f64, which gets zeros and denormals right.  (The
                 // select form cost a multiplication, two v_cndmask and a lane mask in a scalar register pair per slot.)
-                const double arg = __builtin_amdgcn_ldexp(xd[a], __builtin_amdgcn_sbfe(theta_bits, a, 1));
+                // ROOMY: the NA exponents are extracted once per kernel
+                int hexp;
+                if constexpr (ROOMY) hexp = lc->hexp[a];
+                else hexp = __builtin_amdgcn_sbfe(theta_bits, a, 1);
+                const double arg = __builtin_amdgcn_ldexp(xd[a], hexp);
                 sincos_tbl_lookup<true>(arg, tbl, L, rr[a], kk[a], tt[a]);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -904,11 +950,18 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
     // registers as the next layer's h
     double Pr[4], Pi[4];
     // this lane's unit vector e_q as real pairs per qubit: (1 - bit, bit)
-    // (from an opaque copy of q: four selects per evaluation instead of eight registers live across the optimizer loop)
-    int qo = q;
-    asm volatile("" : "+v"(qo));
-    const double e0[2] = {(qo & 1) ? 0.0 : 1.0, (qo & 1) ? 1.0 : 0.0};
-    const double e1[2] = {(qo & 2) ? 0.0 : 1.0, (qo & 2) ? 1.0 : 0.0};
+    // (from an opaque copy of q: four selects per evaluation instead of eight registers live across the optimizer loop;
+    // ROOMY: the eight registers)
+    double e0[2], e1[2];
+    if constexpr (ROOMY) {
+        e0[0] = lc->e0[0]; e0[1] = lc->e0[1];
+        e1[0] = lc->e1[0]; e1[1] = lc->e1[1];
+    } else {
+        int qo = q;
+        asm volatile("" : "+v"(qo));
+        e0[0] = (qo & 1) ? 0.0 : 1.0; e0[1] = (qo & 1) ? 1.0 : 0.0;
+        e1[0] = (qo & 2) ? 0.0 : 1.0; e1[1] = (qo & 2) ? 1.0 : 0.0;
+    }
     double Fr[4], Fi[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1000,7 +1053,11 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
         // v_readlane -- vector-ALU slots -- per evaluation; re-selected here they are three s_cselect_b64)
         asm volatile("" : "+s"(cost_kind));
         const bool sq = (cost_kind == 1);
-        const double c0 = sq ? 1.6 : 1.0, c1 = sq ? -0.8 : 0.0, d1 = sq ? -1.6 : 0.0;
+        // (ROOMY: c0, the addend of both maps, waits in a vector register -- beside c1 / d1 it had to be moved into one)
+        double c0;
+        if constexpr (ROOMY) c0 = lc->c0;
+        else c0 = sq ? 1.6 : 1.0;
+        const double c1 = sq ? -0.8 : 0.0, d1 = sq ? -1.6 : 0.0;
         fout = basic * fma(c1, basic, c0);
         const double inv = (0.25 * rat) * fma(d1, basic, c0);
         const double zr = -pr * inv, zi = pi * inv;

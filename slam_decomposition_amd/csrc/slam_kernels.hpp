@@ -234,6 +234,12 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
     int q = lane & 3;
     const int quad = lane >> 2;
     const int theta_bits = theta_slot_bits<K>(q);
+    // span 1 has registers to spare (roomy_regs): the evaluation's lane constants are formed here, once, and live across the loop
+    constexpr bool kRoomy = roomy_regs<K, GC, MQ, WL>() && !MK;
+    // (span 2, tried: the per-item values cost it 3 registers -- 251 of 256 -- for 6 of its 2800 instructions; not taken)
+    constexpr bool kRoomyItem = kRoomy && !MQ;  // three more registers, per item (below); the multi-queue dense kernel has none left
+    EvalLaneConsts<NA> lane_consts;
+    if constexpr (kRoomy) eval_lane_consts<K>(q, args.cost_kind, lane_consts);
     double* xq = xchg + quad * C::XSTRIDE;
     float* xq32 = reinterpret_cast<float*>(xchg) + quad * C::FSTRIDE;  // fp32 overlay with its own conflict-free stride
     double2* fh = fhbase + lane;
@@ -297,6 +303,12 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
     // update instead of a multiplication of every stored block
     double pp = 0.0, hs1 = 0.0;
     const double* tcol = cold_args<K, MQ>(cur)->targets + q * 2;  // this lane's column of the quad's target
+    // kRoomyItem: what the early-exit test of every round needs of the item, formed once when the quad takes it -- the address of its
+    // target's flag and the level the flag has to exceed for the item to be beaten (ordered: restarts - r, this restart's own flag
+    // value; else 0 -- the flag is 0 or a positive restarts - r, so `!= 0` is `> 0`)
+    const int32_t* sflag_ptr = nullptr;
+    int beat_level = 0;
+    if constexpr (kRoomyItem) sflag_ptr = args.solved;  // (idle quads look at slot 0)
     double x[NA], g[NA], p[NA];
 #pragma unroll
     for (int a = 0; a < NA; ++a) { x[a] = 0.0; g[a] = 0.0; p[a] = 0.0; }
@@ -467,6 +479,10 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
                             tgt = cold_args<K, MQ>(cur)->orig ? cold_args<K, MQ>(cur)->orig[sl] : cold_args<K, MQ>(cur)->first_target + (int)sl;
                             tcol = cold_args<K, MQ>(cur)->targets + (int64_t)sl * 32 + q * 2;
                         }
+                        if constexpr (kRoomyItem) {
+                            sflag_ptr = args.solved + sl;
+                            beat_level = (args.flags & 2u) ? args.restarts - (int)rs : 0;
+                        }
                         if (!shared) {
 #pragma unroll
                             for (int a = 0; a < NA; ++a) {
@@ -565,6 +581,7 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
         int sflag = 0;
         if (args.flags & 1u) {
             if constexpr (WL) sflag = *reinterpret_cast<volatile int*>(wl.flag);
+            else if constexpr (kRoomyItem) sflag = __hip_atomic_load(sflag_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else sflag = __hip_atomic_load(&(MQ ? cold_args<K, MQ>(cur)->solved : args.solved)[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
 
@@ -579,8 +596,9 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
             if constexpr (MK) {
                 eval_quad<K, false, GC, true>(xt, tcol, args.gates, xq, fh, tbl, q, theta_bits, 0, ft, gt, Wr, Wi, mkt);
             } else {
-                eval_quad<K, false, GC>(xt, tcol, MQ ? cold_args<K, MQ>(cur)->gates : args.gates, xq, fh, tbl, q, theta_bits,
-                                        WL ? __builtin_amdgcn_readfirstlane(args.cost_kind) : args.cost_kind, ft, gt, Wr, Wi);
+                eval_quad<K, false, GC, false, kRoomy>(xt, tcol, MQ ? cold_args<K, MQ>(cur)->gates : args.gates, xq, fh, tbl, q, theta_bits,
+                                                       WL ? __builtin_amdgcn_readfirstlane(args.cost_kind) : args.cost_kind, ft, gt, Wr, Wi, nullptr,
+                                                       kRoomy ? &lane_consts : nullptr);
             }
         }
         const bool active = live;
@@ -749,12 +767,21 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
         // ---- 5. early exit across the restarts of one target (optimizer.py:287-295)
         if (args.flags & 1u) {
             asm volatile("" : "+v"(sflag));  // not to be tested (= waited for) any earlier than here
-            const int mine = args.restarts - (int)(item - (unsigned)slot * (unsigned)args.restarts);
-            const bool beaten = (args.flags & 2u) ? (sflag > mine) : (sflag != 0);
-            if (active && !done && beaten) { status = ST_PREEMPTED; done = true; }
-            if (active && done && status != ST_PREEMPTED && f < args.exit_loss && q == 0) {
-                if constexpr (WL) __hip_atomic_fetch_max(wl.flag, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                else __hip_atomic_fetch_max(&(MQ ? cold_args<K, MQ>(cur)->solved : args.solved)[slot], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (kRoomyItem) {
+                // one compare per round (the level was formed with the item); the flag value itself only where it is published
+                if (active && !done && sflag > beat_level) { status = ST_PREEMPTED; done = true; }
+                if (active && done && status != ST_PREEMPTED && f < args.exit_loss && q == 0) {
+                    const int mine = args.restarts - (int)(item - (unsigned)slot * (unsigned)args.restarts);
+                    __hip_atomic_fetch_max(&args.solved[slot], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            } else {
+                const int mine = args.restarts - (int)(item - (unsigned)slot * (unsigned)args.restarts);
+                const bool beaten = (args.flags & 2u) ? (sflag > mine) : (sflag != 0);
+                if (active && !done && beaten) { status = ST_PREEMPTED; done = true; }
+                if (active && done && status != ST_PREEMPTED && f < args.exit_loss && q == 0) {
+                    if constexpr (WL) __hip_atomic_fetch_max(wl.flag, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    else __hip_atomic_fetch_max(&(MQ ? cold_args<K, MQ>(cur)->solved : args.solved)[slot], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
             }
         }
         // ---- 6. finished items leave; their quads pull new work next round
@@ -814,6 +841,21 @@ __global__ void __launch_bounds__(kWave, (K <= 2 ? 2 : 1)) minimize_kernel(Minim
     WlStage none{};
     minimize_body<K, GC, MQ, false>(args, subs, n_sub, none);
 }
+// Span 3 parks its spills in AGPRs: 256 + 10 .. 16 for four of the gate classes, 256 + 18 for CNOT's -- 280 allocated, which no longer
+// leaves a span-1 wavefront its 240 beside it.  That one kernel is held to the 272 of the others: 256 + 16, and two lane constants
+// (12 bytes per lane) go to scratch once and come back once per round.  The attribute takes a literal only, hence the specialization
+// (the body is the template's), and on this target it counts half of the unified file: 136 is 272 registers.
+// A specialization is a plain function: emitted, like the bookkeeping kernels below, by the one unit that defines SLAM_STAGE_KERNELS.
+template <>
+__global__ void minimize_kernel<3, GC_CX, false>(MinimizeArgs<3> args, const MinimizeArgs<3>* subs, int n_sub);
+#ifdef SLAM_STAGE_KERNELS
+template <>
+__global__ void __launch_bounds__(kWave, 1) __attribute__((amdgpu_num_vgpr(136)))
+minimize_kernel<3, GC_CX, false>(MinimizeArgs<3> args, const MinimizeArgs<3>* subs, int n_sub) {
+    WlStage none{};
+    minimize_body<3, GC_CX, false, false>(args, subs, n_sub, none);
+}
+#endif
 // MakhlinFunctionalCost (SLAM_COST_MAKHLIN): per-span launches, dense gate class
 template <int K>
 __global__ void __launch_bounds__(kWave, (K <= 2 ? 2 : 1)) minimize_mk_kernel(MinimizeArgs<K> args) {

@@ -1,10 +1,10 @@
 #!/bin/bash
 # GPU box: dynamic VALU instructions per lock-step round (steady-state workload), one PMC pass per (gate, k).
-# usage: tools/valu_per_round.sh "<gates>" "<ks>"   [SLAM_HIP_LIB honoured]
+# usage: tools/valu_per_round.sh "<gates>" "<ks>" [ee]   [SLAM_HIP_LIB honoured; ee: the workload with ordered early exit on]
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for g in ${1:-sqiswap}; do for k in ${2:-1 2 3}; do
   OUT=gpurun_out/vpr_tmp; rm -rf $OUT; mkdir -p $OUT
-  timeout -k 10 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $OUT/pmc1 -- python3 tools/steady.py $g $k 8 > $OUT/run.txt 2> $OUT/err.txt || { tail -3 $OUT/err.txt; exit 1; }
+  timeout -k 10 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $OUT/pmc1 -- python3 tools/steady.py $g $k 8 $3 > $OUT/run.txt 2> $OUT/err.txt || { tail -3 $OUT/err.txt; exit 1; }
   python3 - "$OUT" "$g" "$k" <<'PY'
 import sys, csv, glob, collections
 out, g, k = sys.argv[1:4]
