@@ -319,54 +319,8 @@ int reserve_stage_buffers(slam_ctx* c, int64_t n_upper, int k_max, const slam_op
 // inputs, the optimizer kernel, the per-target reduction and (merge) the span loop's bookkeeping.  No host
 // synchronisation: the stage's target count lives in its control block (stage_ctl(c, k)->n_active, at most
 // n_upper), which must have been zeroed and published on the stream before.  Leaves per-slot results in
-// ctx->stage_loss / stage_x / stage_restart and the per-item arrays.
-// What follows the optimizer kernel of a stage inside the span loop (nullptr: single-stage call, reduce only).
-struct SpanLoopStep {
-    double exit_loss;        // ordered early exit: the span loop's success threshold; otherwise params->stop_loss
-    bool inputs_ready;       // the previous kernel of the chain already prepared this stage's inputs
-    bool has_next;           // a longer span follows: compact the unsolved targets into active_out
-    double threshold;
-    int32_t* active_out;
-};
-
-ReduceArgs build_reduce_args(slam_ctx* c, int k, const int32_t* d_active, const slam_opt_params* prm, double exit_loss, bool merge) {
-    ReduceArgs r{};
-    r.slot_ev = (!merge && c->slot_ev_on) ? c->slot_ev.as<unsigned long long>() : nullptr;
-    r.item_rec = c->item_rec.as<ItemRec>();
-    r.item_x = c->item_x.as<double>();
-    r.exit_loss = exit_loss;
-    r.ordered = ((prm->flags & SLAM_FLAG_EARLY_EXIT) && (prm->flags & SLAM_FLAG_ORDERED)) ? 1 : 0;
-    r.ctl = stage_ctl(c, k);
-    r.restarts = prm->restarts;
-    r.n = 6 * (k + 1);
-    r.stage_loss = c->stage_loss.as<double>();
-    r.stage_x = c->stage_x.as<double>();
-    r.stage_restart = c->stage_restart.as<int32_t>();
-    if (merge) {
-        r.active = d_active;
-        r.nmax = c->result_nmax;
-        r.k = k;
-        r.best_loss = c->best_loss.as<double>();
-        r.best_x = c->best_x.as<double>();
-        r.best_cycles = c->best_cycles.as<int32_t>();
-        r.span_loss = c->span_loss.as<double>();
-    }
-    return r;
-}
-
-EpilogueArgs build_epilogue_args(slam_ctx* c, int k, const ReduceArgs& r, const SpanLoopStep& loop) {
-    EpilogueArgs e{};
-    e.r = r;
-    e.has_next = loop.has_next ? 1 : 0;
-    e.threshold = loop.threshold;
-    e.active_out = loop.active_out;
-    e.next = stage_ctl(c, k + 1);
-    e.targets = c->targets.as<double>();
-    e.stage_targets = c->stage_targets.as<double>();
-    e.solved = c->solved.as<int32_t>();
-    return e;
-}
-
+// ctx->stage_loss / stage_x / stage_restart and the per-item arrays.  loop: what follows the optimizer kernel inside the span loop
+// (nullptr: single-stage call, reduce only).
 int enqueue_stage(slam_ctx* c, int k, const int32_t* gate_seq, const int32_t* d_active, int64_t n_upper,
                   const double* d_x0, const slam_opt_params* prm, const SpanLoopStep* loop) {
     const int n = 6 * (k + 1);
@@ -402,7 +356,7 @@ int enqueue_stage(slam_ctx* c, int k, const int32_t* gate_seq, const int32_t* d_
     }
     if (rc != SLAM_OK) return rc;
 
-    const ReduceArgs r = build_reduce_args(c, k, d_active, prm, exit_loss, merge);
+    const ReduceArgs r = build_reduce_args(c, k, n, d_active, prm, exit_loss, merge);
     if (loop) {
         const EpilogueArgs e = build_epilogue_args(c, k, r, *loop);
         return enqueue_stage_epilogue(c, n_upper, e);
@@ -416,6 +370,21 @@ int enqueue_stage(slam_ctx* c, int k, const int32_t* gate_seq, const int32_t* d_
 
 }  // namespace
 
+// The counters of the control blocks h_ctl[k_min..k_max] added to the statistics.  Which blocks are left out is the caller's rule:
+// none; the stages that had no targets; of those, only the ones that counted no evaluation either (the one-launch loops).
+enum FoldSkip { FOLD_ALL, FOLD_SKIP_IDLE, FOLD_SKIP_IDLE_UNEVALUATED };
+static void fold_counters(slam_stats& s, const StageCtl* h_ctl, int k_min, int k_max, int restarts, FoldSkip skip) {
+    for (int k = k_min; k <= k_max; ++k) {
+        const bool idle = h_ctl[k].n_active <= 0;
+        if ((skip == FOLD_SKIP_IDLE && idle) || (skip == FOLD_SKIP_IDLE_UNEVALUATED && idle && h_ctl[k].evals == 0)) continue;
+        s.evals[k] += (int64_t)h_ctl[k].evals;
+        s.evals_accepted[k] += (int64_t)h_ctl[k].evals_accepted;
+        s.evals_preempted[k] += (int64_t)h_ctl[k].evals_preempted;
+        s.wave_rounds[k] += (int64_t)h_ctl[k].rounds;
+        s.items[k] += (int64_t)h_ctl[k].n_active * restarts;
+    }
+}
+
 // ---- shared with the other units (slam_host.hpp) ----
 // After the stream has drained: fold the stages' control blocks and kernel brackets into the statistics.
 int collect_stats(slam_ctx* c, int k_min, int k_max, const StageCtl* h_ctl, int restarts) {
@@ -426,13 +395,67 @@ int collect_stats(slam_ctx* c, int k_min, int k_max, const StageCtl* h_ctl, int 
         c->stats.kernel_ms += ms;
         c->stats.kernel_ms_span[k] += ms;
         c->stats.kernel_launches += 1;
-        c->stats.evals[k] += (int64_t)h_ctl[k].evals;
-        c->stats.evals_accepted[k] += (int64_t)h_ctl[k].evals_accepted;
-        c->stats.evals_preempted[k] += (int64_t)h_ctl[k].evals_preempted;
-        c->stats.wave_rounds[k] += (int64_t)h_ctl[k].rounds;
-        c->stats.items[k] += (int64_t)h_ctl[k].n_active * restarts;
     }
+    fold_counters(c->stats, h_ctl, k_min, k_max, restarts, FOLD_SKIP_IDLE);
     return SLAM_OK;
+}
+
+int enqueue_loop_end(slam_ctx* c, FetchReq* fetch, int nmax, int64_t first, int64_t count) {
+    HIP_TRY(hipEventRecord(c->ev_t1, c->stream));
+    if (fetch) {  // the results ride on the same wait as the span loop
+        const int rc = enqueue_fetch_n(c, nmax, first, count, *fetch);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_ctl, c->counters.p, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), hipMemcpyDeviceToHost, c->stream));
+    return SLAM_OK;
+}
+
+int wait_loop_end(slam_ctx* c, const FetchReq* fetch) {
+    HIP_TRY(hipEventRecord(c->ev_done, c->stream));
+    HIP_TRY(hipEventSynchronize(c->ev_done));  // sleep until the chain is done
+    if (fetch) finish_fetch(c, *fetch);
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
+    c->stats.total_ms = ms;
+    return SLAM_OK;
+}
+
+ReduceArgs build_reduce_args(slam_ctx* c, int k, int n, const int32_t* d_active, const slam_opt_params* prm, double exit_loss, bool merge) {
+    ReduceArgs r{};
+    r.slot_ev = (!merge && c->slot_ev_on) ? c->slot_ev.as<unsigned long long>() : nullptr;
+    r.item_rec = c->item_rec.as<ItemRec>();
+    r.item_x = c->item_x.as<double>();
+    r.exit_loss = exit_loss;
+    r.ordered = ((prm->flags & SLAM_FLAG_EARLY_EXIT) && (prm->flags & SLAM_FLAG_ORDERED)) ? 1 : 0;
+    r.ctl = stage_ctl(c, k);
+    r.restarts = prm->restarts;
+    r.n = n;
+    r.stage_loss = c->stage_loss.as<double>();
+    r.stage_x = c->stage_x.as<double>();
+    r.stage_restart = c->stage_restart.as<int32_t>();
+    if (merge) {
+        r.active = d_active;
+        r.nmax = c->result_nmax;
+        r.k = k;
+        r.best_loss = c->best_loss.as<double>();
+        r.best_x = c->best_x.as<double>();
+        r.best_cycles = c->best_cycles.as<int32_t>();
+        r.span_loss = c->span_loss.as<double>();
+    }
+    return r;
+}
+
+EpilogueArgs build_epilogue_args(slam_ctx* c, int k, const ReduceArgs& r, const SpanLoopStep& loop) {
+    EpilogueArgs e{};
+    e.r = r;
+    e.has_next = loop.has_next ? 1 : 0;
+    e.threshold = loop.threshold;
+    e.active_out = loop.active_out;
+    e.next = stage_ctl(c, k + 1);
+    e.targets = c->targets.as<double>();
+    e.stage_targets = c->stage_targets.as<double>();
+    e.solved = c->solved.as<int32_t>();
+    return e;
 }
 
 static int ensure_results(slam_ctx* c, int k_max) { return ensure_results_n(c, 6 * (k_max + 1)); }
@@ -536,7 +559,8 @@ int enqueue_stage_epilogue(slam_ctx* c, int64_t n_upper, const EpilogueArgs& e) 
     return SLAM_OK;
 }
 
-int pack_stage_bounds(int n, const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi, double* b, bool* bounded) {
+// (init_lo, init_hi, bound_lo, bound_hi) checked and packed into b[4 n]; *bounded: some bound is finite
+static int pack_stage_bounds(int n, const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi, double* b, bool* bounded) {
     *bounded = false;
     for (int i = 0; i < n; ++i) {
         b[i] = init_lo[i];
@@ -551,11 +575,13 @@ int pack_stage_bounds(int n, const double* init_lo, const double* init_hi, const
     return SLAM_OK;
 }
 
-int upload_stage_active(slam_ctx* c, const int32_t* active, int64_t n_active, const int32_t** d_active) {
+// the caller's active list checked and copied into c->active (*d_active stays nullptr without one)
+static int upload_stage_active(slam_ctx* c, const int32_t* active, int64_t n_active, const int32_t** d_active) {
     *d_active = nullptr;
     if (active) {
-        for (int64_t s2 = 0; s2 < n_active; ++s2)
-            if (active[s2] < 0 || active[s2] >= c->n_targets) return fail(SLAM_ERR_INVALID, "active[%lld] outside the resident batch", (long long)s2);
+        for (int64_t s = 0; s < n_active; ++s)
+            if (active[s] < 0 || active[s] >= c->n_targets)
+                return fail(SLAM_ERR_INVALID, "active[%lld] = %d outside [0, %lld)", (long long)s, active[s], (long long)c->n_targets);
         HIP_TRY(c->active.reserve((size_t)n_active * sizeof(int32_t)));
         HIP_TRY(hipMemcpyAsync(c->active.p, active, (size_t)n_active * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         *d_active = c->active.as<int32_t>();
@@ -563,7 +589,8 @@ int upload_stage_active(slam_ctx* c, const int32_t* active, int64_t n_active, co
     return SLAM_OK;
 }
 
-int upload_stage_x0(slam_ctx* c, const double* x0, int64_t count, const double** d_x0) {
+// explicit start points x0[count] checked and copied into c->x0 (*d_x0 stays nullptr without them)
+static int upload_stage_x0(slam_ctx* c, const double* x0, int64_t count, const double** d_x0) {
     *d_x0 = nullptr;
     if (x0) {
         // the optimizer kernel's range reduction covers |x| < 2e9; steps are <= 2 rad each
@@ -576,19 +603,62 @@ int upload_stage_x0(slam_ctx* c, const double* x0, int64_t count, const double**
     return SLAM_OK;
 }
 
+int stage_family_inputs(slam_ctx* c, int k, int n, const int32_t* active, int64_t n_active, const double* x0, const double* init_lo,
+                        const double* init_hi, const double* bound_lo, const double* bound_hi, const slam_opt_params* prm,
+                        const int32_t** d_active, const double** d_x0, bool* bounded) {
+    const int64_t M = n_active * (int64_t)prm->restarts;
+    std::vector<double> b((size_t)4 * n);
+    int rc = pack_stage_bounds(n, init_lo, init_hi, bound_lo, bound_hi, b.data(), bounded);
+    if (rc) return rc;
+    rc = upload_stage_active(c, active, n_active, d_active);
+    if (rc) return rc;
+    rc = upload_stage_x0(c, x0, M * n, d_x0);
+    if (rc) return rc;
+    HIP_TRY(c->v2_bounds.reserve(b.size() * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(c->v2_bounds.p, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // b is a local buffer
+    // stage buffers sized for n parameters per item (reserve_stage_buffers sizes for 6 (k + 1))
+    HIP_TRY(c->item_rec.reserve(M * sizeof(ItemRec)));
+    HIP_TRY(c->item_x.reserve(M * n * sizeof(double)));
+    HIP_TRY(c->stage_loss.reserve(n_active * sizeof(double)));
+    HIP_TRY(c->stage_x.reserve(n_active * n * sizeof(double)));
+    HIP_TRY(c->stage_restart.reserve(n_active * sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), c->stream));
+    rc = enqueue_set_n_active(c, k, n_active);
+    if (rc) return rc;
+    HIP_TRY(c->solved.reserve((size_t)n_active * sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(c->solved.p, 0, (size_t)n_active * sizeof(int32_t), c->stream));
+    return SLAM_OK;
+}
+
+int stage_eval_inputs(slam_ctx* c, const double* x, const int32_t* target_of, int64_t M, int n, bool want_grad, bool want_unitary, EvalBufs* d) {
+    for (int64_t m = 0; m < M; ++m)
+        if (target_of[m] < 0 || target_of[m] >= c->n_targets)
+            return fail(SLAM_ERR_INVALID, "target_of[%lld] = %d outside [0, %lld)", (long long)m, target_of[m], (long long)c->n_targets);
+    HIP_TRY(c->ev_x.reserve((size_t)M * n * sizeof(double)));
+    HIP_TRY(c->ev_tof.reserve((size_t)M * sizeof(int32_t)));
+    HIP_TRY(c->ev_loss.reserve((size_t)M * sizeof(double)));
+    if (want_grad) HIP_TRY(c->ev_grad.reserve((size_t)M * n * sizeof(double)));
+    if (want_unitary) HIP_TRY(c->ev_unitary.reserve((size_t)M * 32 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(c->ev_x.p, x, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ev_tof.p, target_of, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    *d = EvalBufs{c->ev_x.as<double>(), c->ev_tof.as<int32_t>(), c->ev_loss.as<double>(), want_grad ? c->ev_grad.as<double>() : nullptr,
+                  want_unitary ? c->ev_unitary.as<double>() : nullptr};
+    return SLAM_OK;
+}
+
+int enqueue_eval_readback(slam_ctx* c, int64_t M, int n, double* loss, double* grad, double* unitary) {
+    HIP_TRY(hipMemcpyAsync(loss, c->ev_loss.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (grad) HIP_TRY(hipMemcpyAsync(grad, c->ev_grad.p, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (unitary) HIP_TRY(hipMemcpyAsync(unitary, c->ev_unitary.p, (size_t)M * 32 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return SLAM_OK;
+}
+
 // single stage of a parametrised-gate family: per-target reduction only, no merge into resident results
-static int enqueue_stage_reduce(slam_ctx* c, int k, int n, int64_t n_active, int restarts, double exit_loss) {
-    ReduceArgs r{};
-    r.item_rec = c->item_rec.as<ItemRec>();
-    r.item_x = c->item_x.as<double>();
-    r.exit_loss = exit_loss;
-    r.ordered = 1;  // the winner is the restart the reference's sequential loop breaks at (restarts below it always run to their end)
-    r.ctl = stage_ctl(c, k);
-    r.restarts = restarts;
-    r.n = n;
-    r.stage_loss = c->stage_loss.as<double>();
-    r.stage_x = c->stage_x.as<double>();
-    r.stage_restart = c->stage_restart.as<int32_t>();
+static int enqueue_stage_reduce(slam_ctx* c, int k, int n, int64_t n_active, const slam_opt_params* prm, double exit_loss) {
+    ReduceArgs r = build_reduce_args(c, k, n, nullptr, prm, exit_loss, false);
+    r.ordered = 1;  // whatever the flags: the winner is the restart the reference's sequential loop breaks at (restarts below it always run to their end)
+    r.slot_ev = nullptr;  // the evaluations stay in the stage's counters: these stages never run on a helper context of the overlapped loop
     hipLaunchKernelGGL(reduce_merge_kernel, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, c->stream, r);
     HIP_TRY(hipGetLastError());
     return SLAM_OK;
@@ -596,7 +666,7 @@ static int enqueue_stage_reduce(slam_ctx* c, int k, int n, int64_t n_active, int
 
 int finish_single_stage(slam_ctx* c, int k, int n, int64_t n_active, const slam_opt_params* prm, double exit_loss, double* best_loss, double* best_x,
                         int32_t* best_restart, double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals) {
-    int rc = enqueue_stage_reduce(c, k, n, n_active, prm->restarts, exit_loss);
+    int rc = enqueue_stage_reduce(c, k, n, n_active, prm, exit_loss);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(best_loss, c->stage_loss.p, (size_t)n_active * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(best_x, c->stage_x.p, (size_t)n_active * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -801,18 +871,10 @@ int decompose_wave_loop(slam_ctx* c, int64_t first, int64_t count, int k_min, in
         if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(c->ev_b[0], c->stream));
-    HIP_TRY(hipEventRecord(c->ev_t1, c->stream));
-    if (fetch) {
-        rc = enqueue_fetch_n(c, c->result_nmax, first, count, *fetch);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(c->h_ctl, c->counters.p, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_done, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev_done));
-    if (fetch) finish_fetch(c, *fetch);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
-    c->stats.total_ms = ms;
+    rc = enqueue_loop_end(c, fetch, c->result_nmax, first, count);
+    if (rc) return rc;
+    rc = wait_loop_end(c, fetch);
+    if (rc) return rc;
     float kms = 0.f;
     HIP_TRY(hipEventElapsedTime(&kms, c->ev_a[0], c->ev_b[0]));
     c->stats.kernel_ms += kms;
@@ -827,14 +889,7 @@ int decompose_wave_loop(slam_ctx* c, int64_t first, int64_t count, int k_min, in
         c->stats.kernel_ms_span[0] += kms;  // ONE launch for all spans: no per-span split exists -- booked under index 0
     }
     c->stats.kernel_launches += n_launch;
-    for (int k = k_min; k <= k_max; ++k) {
-        if (c->h_ctl[k].n_active <= 0 && c->h_ctl[k].evals == 0) continue;
-        c->stats.evals[k] += (int64_t)c->h_ctl[k].evals;
-        c->stats.evals_accepted[k] += (int64_t)c->h_ctl[k].evals_accepted;
-        c->stats.evals_preempted[k] += (int64_t)c->h_ctl[k].evals_preempted;
-        c->stats.wave_rounds[k] += (int64_t)c->h_ctl[k].rounds;
-        c->stats.items[k] += (int64_t)c->h_ctl[k].n_active * prm->restarts;
-    }
+    fold_counters(c->stats, c->h_ctl, k_min, k_max, prm->restarts, FOLD_SKIP_IDLE_UNEVALUATED);
     return SLAM_OK;
 }
 
@@ -940,19 +995,10 @@ int decompose_overlapped(slam_ctx* c, int64_t first, int64_t count, int k_min, i
     hipLaunchKernelGGL(span_merge_kernel, dim3((unsigned)((count + kWave - 1) / kWave)), dim3(kWave), 0, c->stream, mg);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev_b[0], c->stream));
-    HIP_TRY(hipEventRecord(c->ev_t1, c->stream));
-    int rc = SLAM_OK;
-    if (fetch) {
-        rc = enqueue_fetch_n(c, c->result_nmax, first, count, *fetch);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(c->h_ctl, c->counters.p, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_done, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev_done));
-    if (fetch) finish_fetch(c, *fetch);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
-    c->stats.total_ms = ms;
+    int rc = enqueue_loop_end(c, fetch, c->result_nmax, first, count);
+    if (rc) return rc;
+    rc = wait_loop_end(c, fetch);
+    if (rc) return rc;
     float kms = 0.f;
     HIP_TRY(hipEventElapsedTime(&kms, c->ev_a[0], c->ev_b[0]));
     c->stats.kernel_ms += kms;
@@ -964,13 +1010,7 @@ int decompose_overlapped(slam_ctx* c, int64_t first, int64_t count, int k_min, i
         c->stats.kernel_ms_span[k] += sk;
     }
     c->stats.kernel_launches += 2 * (k_max - k_min + 1) + 1;
-    for (int k = k_min; k <= k_max; ++k) {
-        c->stats.evals[k] += (int64_t)c->h_ctl[k].evals;
-        c->stats.evals_accepted[k] += (int64_t)c->h_ctl[k].evals_accepted;
-        c->stats.evals_preempted[k] += (int64_t)c->h_ctl[k].evals_preempted;
-        c->stats.wave_rounds[k] += (int64_t)c->h_ctl[k].rounds;
-        c->stats.items[k] += (int64_t)c->h_ctl[k].n_active * prm->restarts;
-    }
+    fold_counters(c->stats, c->h_ctl, k_min, k_max, prm->restarts, FOLD_ALL);
     return SLAM_OK;
 }
 
@@ -1046,18 +1086,10 @@ int decompose_body(slam_ctx* c, int64_t first, int64_t count, int k_min, int k_m
             DevBuf* t = cur; cur = nxt; nxt = t;
         }
     }
-    HIP_TRY(hipEventRecord(c->ev_t1, c->stream));
-    if (fetch) {  // the results ride on the same wait as the span loop
-        rc = enqueue_fetch(c, k_layout, h_list ? 0 : first, h_list ? c->n_targets : count, *fetch);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(c->h_ctl, c->counters.p, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_done, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev_done));
-    if (fetch) finish_fetch(c, *fetch);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
-    c->stats.total_ms = ms;
+    rc = enqueue_loop_end(c, fetch, 6 * (k_layout + 1), h_list ? 0 : first, h_list ? c->n_targets : count);
+    if (rc) return rc;
+    rc = wait_loop_end(c, fetch);
+    if (rc) return rc;
     return collect_stats(c, k_min, k_max, c->h_ctl, prm->restarts);
 }
 
@@ -1182,7 +1214,7 @@ int decompose_multi_body(slam_ctx** cs, int n, int64_t first, int64_t count, int
             if (rc) return rc;
             if (c != lead) HIP_TRY(hipStreamSynchronize(c->stream));  // (its gate slot may just have been staged on its own stream)
             SpanLoopStep step{success_threshold, true, k < k_max, success_threshold, nxt[(size_t)i]->as<int32_t>()};
-            const ReduceArgs r = build_reduce_args(c, k, d_active[(size_t)i], prm, success_threshold, true);
+            const ReduceArgs r = build_reduce_args(c, k, 6 * (k + 1), d_active[(size_t)i], prm, success_threshold, true);
             h_ep[slot_i] = build_epilogue_args(c, k, r, step);
         }
         HIP_TRY(hipMemcpyAsync(d, h, slot, hipMemcpyHostToDevice, lead->stream));
@@ -1229,17 +1261,7 @@ int decompose_multi_body(slam_ctx** cs, int n, int64_t first, int64_t count, int
     HIP_TRY(hipEventElapsedTime(&ms, lead->ev_t0, lead->ev_t1));
     lead->stats.total_ms = ms;
     // statistics: every context gets the evaluations / items of its own queues; the kernels' time goes to the leading context
-    for (int i = 0; i < n; ++i) {
-        slam_ctx* c = cs[i];
-        for (int k = k_min; k <= k_max; ++k) {
-            if (c->h_ctl[k].n_active <= 0) continue;
-            c->stats.evals[k] += (int64_t)c->h_ctl[k].evals;
-            c->stats.evals_accepted[k] += (int64_t)c->h_ctl[k].evals_accepted;
-            c->stats.evals_preempted[k] += (int64_t)c->h_ctl[k].evals_preempted;
-            c->stats.wave_rounds[k] += (int64_t)c->h_ctl[k].rounds;
-            c->stats.items[k] += (int64_t)c->h_ctl[k].n_active * prm->restarts;
-        }
-    }
+    for (int i = 0; i < n; ++i) fold_counters(cs[i]->stats, cs[i]->h_ctl, k_min, k_max, prm->restarts, FOLD_SKIP_IDLE);
     for (int k = k_min; k <= k_max; ++k) {
         float kms = 0.f;
         HIP_TRY(hipEventElapsedTime(&kms, lead->ev_a[k], lead->ev_b[k]));
@@ -1424,36 +1446,23 @@ static int eval_body(slam_ctx* ctx, int k, const int32_t* gate_seq, const double
     if (!x || !target_of || !loss) return fail(SLAM_ERR_INVALID, "x, target_of and loss must be non-NULL");
     int rc = check_gate_seq(ctx, k, gate_seq);
     if (rc) return rc;
-    for (int64_t m = 0; m < M; ++m)
-        if (target_of[m] < 0 || target_of[m] >= ctx->n_targets)
-            return fail(SLAM_ERR_INVALID, "target_of[%lld] = %d outside [0, %lld)", (long long)m, target_of[m], (long long)ctx->n_targets);
     const int n = 6 * (k + 1);
-    HIP_TRY(ctx->ev_x.reserve((size_t)M * n * sizeof(double)));
-    HIP_TRY(ctx->ev_tof.reserve((size_t)M * sizeof(int32_t)));
-    HIP_TRY(ctx->ev_loss.reserve((size_t)M * sizeof(double)));
-    if (grad) HIP_TRY(ctx->ev_grad.reserve((size_t)M * n * sizeof(double)));
-    if (unitary || weyl) HIP_TRY(ctx->ev_unitary.reserve((size_t)M * 32 * sizeof(double)));
     if (weyl) HIP_TRY(ctx->ev_weyl.reserve((size_t)M * 3 * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(ctx->ev_x.p, x, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->ev_tof.p, target_of, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    double* d_loss = ctx->ev_loss.as<double>();
-    double* d_grad = grad ? ctx->ev_grad.as<double>() : nullptr;
-    double* d_unit = (unitary || weyl) ? ctx->ev_unitary.as<double>() : nullptr;
-    const double* d_x = ctx->ev_x.as<double>();
-    const int32_t* d_tof = ctx->ev_tof.as<int32_t>();
+    EvalBufs d{};
+    rc = stage_eval_inputs(ctx, x, target_of, M, n, grad != nullptr, unitary || weyl, &d);
+    if (rc) return rc;
     const int gc = classify_gates(ctx, k, gate_seq);
     switch (k) {
-        case 1: rc = launch_eval_gc<1>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
-        case 2: rc = launch_eval_gc<2>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
-        case 3: rc = launch_eval_gc<3>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
-        case 4: rc = launch_eval_gc<4>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
-        case 5: rc = launch_eval_gc<5>(ctx, gc, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;
-        default: rc = launch_eval_long(ctx, k, gate_seq, d_x, d_tof, M, d_loss, d_grad, d_unit); break;  // SLAM_MAX_SPAN_QUAD < k: one wavefront per item
+        case 1: rc = launch_eval_gc<1>(ctx, gc, gate_seq, d.x, d.target_of, M, d.loss, d.grad, d.unitary); break;
+        case 2: rc = launch_eval_gc<2>(ctx, gc, gate_seq, d.x, d.target_of, M, d.loss, d.grad, d.unitary); break;
+        case 3: rc = launch_eval_gc<3>(ctx, gc, gate_seq, d.x, d.target_of, M, d.loss, d.grad, d.unitary); break;
+        case 4: rc = launch_eval_gc<4>(ctx, gc, gate_seq, d.x, d.target_of, M, d.loss, d.grad, d.unitary); break;
+        case 5: rc = launch_eval_gc<5>(ctx, gc, gate_seq, d.x, d.target_of, M, d.loss, d.grad, d.unitary); break;
+        default: rc = launch_eval_long(ctx, k, gate_seq, d.x, d.target_of, M, d.loss, d.grad, d.unitary); break;  // SLAM_MAX_SPAN_QUAD < k: one wavefront per item
     }
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(loss, ctx->ev_loss.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (grad) HIP_TRY(hipMemcpyAsync(grad, ctx->ev_grad.p, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (unitary) HIP_TRY(hipMemcpyAsync(unitary, ctx->ev_unitary.p, (size_t)M * 32 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    rc = enqueue_eval_readback(ctx, M, n, loss, grad, unitary);
+    if (rc) return rc;
     if (weyl) {
         // Weyl coordinates of the template unitaries without bringing the unitaries back (optimizer.py:85,103)
         rc = enqueue_c1c2c3(ctx, ctx->ev_unitary.as<double>(), M, ndigits, ctx->ev_weyl.as<double>());
@@ -1506,14 +1515,8 @@ static int minimize_stage_body(slam_ctx* ctx, int k, const int32_t* gate_seq, co
     const int n = 6 * (k + 1);
     const int64_t M = n_active * (int64_t)params->restarts;
     const int32_t* d_active = nullptr;
-    if (active) {
-        for (int64_t s = 0; s < n_active; ++s)
-            if (active[s] < 0 || active[s] >= ctx->n_targets)
-                return fail(SLAM_ERR_INVALID, "active[%lld] = %d outside [0, %lld)", (long long)s, active[s], (long long)ctx->n_targets);
-        HIP_TRY(ctx->active.reserve((size_t)n_active * sizeof(int32_t)));
-        HIP_TRY(hipMemcpyAsync(ctx->active.p, active, (size_t)n_active * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        d_active = ctx->active.as<int32_t>();
-    }
+    rc = upload_stage_active(ctx, active, n_active, &d_active);
+    if (rc) return rc;
     const double* d_x0 = nullptr;
     rc = upload_stage_x0(ctx, x0, M * n, &d_x0);
     if (rc) return rc;
@@ -1525,19 +1528,16 @@ static int minimize_stage_body(slam_ctx* ctx, int k, const int32_t* gate_seq, co
     HIP_TRY(hipGetLastError());
     rc = enqueue_stage(ctx, k, gate_seq, d_active, n_active, d_x0, params, nullptr);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev_t1, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->h_ctl, ctx->counters.p, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_done, ctx->stream));
-    HIP_TRY(hipEventSynchronize(ctx->ev_done));  // sleep until the stage is done; the copies below then find an idle stream
+    rc = enqueue_loop_end(ctx, nullptr, 0, 0, 0);
+    if (rc) return rc;
+    rc = wait_loop_end(ctx, nullptr);  // sleep until the stage is done; the copies below then find an idle stream
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(best_loss, ctx->stage_loss.p, (size_t)n_active * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(best_x, ctx->stage_x.p, (size_t)n_active * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (best_restart) HIP_TRY(hipMemcpyAsync(best_restart, ctx->stage_restart.p, (size_t)n_active * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     rc = fetch_item_records(ctx, M, item_loss, item_iters, item_status, item_evals);
     if (rc) return rc;
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
-    ctx->stats.total_ms = ms;
     return collect_stats(ctx, k, k, ctx->h_ctl, params->restarts);
 }
 
@@ -1633,14 +1633,11 @@ int decompose_predicted_body(slam_ctx* c, int64_t first, int64_t count, int k_ma
         gs += k;
         DevBuf* t = cur; cur = nxt; nxt = t;
     }
-    HIP_TRY(hipEventRecord(c->ev_t1, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_ctl, c->counters.p, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), hipMemcpyDeviceToHost, c->stream));
+    rc = enqueue_loop_end(c, nullptr, 0, 0, 0);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(c->h_bucket_counts, c->bucket_counts.p, (SLAM_MAX_SPAN_EVAL + 2) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_done, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev_done));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
-    c->stats.total_ms = ms;
+    rc = wait_loop_end(c, nullptr);
+    if (rc) return rc;
     if (n_local) *n_local = c->h_bucket_counts[k_max];
     if (n_unreachable) *n_unreachable = c->h_bucket_counts[k_max + 1];
     return collect_stats(c, 1, k_max, c->h_ctl, prm->restarts);

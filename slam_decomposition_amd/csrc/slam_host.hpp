@@ -285,14 +285,49 @@ SLAM_INTERNAL int enqueue_init_results(slam_ctx* c, hipStream_t stream, int32_t*
 // the epilogue of a span-loop stage with at most n_upper targets on c's stream: picks the kernel by n_upper
 SLAM_INTERNAL int enqueue_stage_epilogue(slam_ctx* c, int64_t n_upper, const EpilogueArgs& e);
 
-// Steps that the single-stage calls of the parametrised-gate families (slam_v2_*, slam_smush_*) share word for word:
-// (init_lo, init_hi, bound_lo, bound_hi) checked and packed into b[4 n]; *bounded: some bound is finite
-SLAM_INTERNAL int pack_stage_bounds(int n, const double* init_lo, const double* init_hi, const double* bound_lo, const double* bound_hi, double* b,
-                                    bool* bounded);
-// the caller's active list checked and copied into c->active (*d_active stays nullptr without one)
-SLAM_INTERNAL int upload_stage_active(slam_ctx* c, const int32_t* active, int64_t n_active, const int32_t** d_active);
-// explicit start points x0[count] checked and copied into c->x0 (*d_x0 stays nullptr without them); also the plain path's
-SLAM_INTERNAL int upload_stage_x0(slam_ctx* c, const double* x0, int64_t count, const double** d_x0);
+// The end of a span loop, in two halves, so that a caller can enqueue a copy of its own between them.
+// First half: records ev_t1, enqueues the fetch of the window [first, first + count) with rows of nmax parameters (fetch may be
+// nullptr: nothing to fetch) and sends the control blocks to c->h_ctl.
+SLAM_INTERNAL int enqueue_loop_end(slam_ctx* c, FetchReq* fetch, int nmax, int64_t first, int64_t count);
+// Second half: records ev_done and sleeps until it has passed, completes the fetch, stats.total_ms = ev_t0 .. ev_t1.
+SLAM_INTERNAL int wait_loop_end(slam_ctx* c, const FetchReq* fetch);
+
+// What follows the optimizer kernel of a stage inside a span loop.
+struct SpanLoopStep {
+    double exit_loss;        // ordered early exit: the span loop's success threshold; otherwise params->stop_loss
+    bool inputs_ready;       // the previous kernel of the chain already prepared this stage's inputs
+    bool has_next;           // a longer span follows: compact the unsolved targets into active_out
+    double threshold;
+    int32_t* active_out;
+};
+// The argument blocks of the reduction over restarts of stage k (rows of n parameters; merge: into the resident results, rows of
+// c->result_nmax) and of the span loop's epilogue around it.  A family that differs in a field overrides it after the call.
+SLAM_INTERNAL ReduceArgs build_reduce_args(slam_ctx* c, int k, int n, const int32_t* d_active, const slam_opt_params* prm, double exit_loss, bool merge);
+SLAM_INTERNAL EpilogueArgs build_epilogue_args(slam_ctx* c, int k, const ReduceArgs& r, const SpanLoopStep& loop);
+
+// The staging of an evaluation call (slam_eval_*, slam_v2_eval_*, slam_smush_eval_*) of M items with rows of n parameters:
+// target_of checked, the ev_* buffers reserved, x and target_of on their way to the device; the device pointers the kernel takes
+// (grad / unitary: nullptr when not wanted)
+struct EvalBufs {
+    const double* x;
+    const int32_t* target_of;
+    double* loss;
+    double* grad;
+    double* unitary;
+};
+SLAM_INTERNAL int stage_eval_inputs(slam_ctx* c, const double* x, const int32_t* target_of, int64_t M, int n, bool want_grad, bool want_unitary,
+                                    EvalBufs* d);
+// ... and its results on their way back (grad, unitary: may be nullptr); no wait: the caller synchronises
+SLAM_INTERNAL int enqueue_eval_readback(slam_ctx* c, int64_t M, int n, double* loss, double* grad, double* unitary);
+
+// What the single-stage calls of the parametrised-gate families (slam_v2_*, slam_smush_*) do between "the arguments are valid" and
+// "build the kernel's argument block", for stage k with rows of n parameters: the bounds checked, packed and uploaded to
+// c->v2_bounds as (init_lo | init_hi | bound_lo | bound_hi)[n] (*bounded: some bound is finite), the active list and the start
+// points checked and uploaded (*d_active / *d_x0 stay nullptr without them), the stage buffers reserved, the control blocks zeroed,
+// n_active published and `solved` zeroed.
+SLAM_INTERNAL int stage_family_inputs(slam_ctx* c, int k, int n, const int32_t* active, int64_t n_active, const double* x0, const double* init_lo,
+                                      const double* init_hi, const double* bound_lo, const double* bound_hi, const slam_opt_params* prm,
+                                      const int32_t** d_active, const double** d_x0, bool* bounded);
 // after the optimizer kernel of stage k (rows of n parameters): the reduction over restarts (ordered winner rule), the results, the
 // per-item records and the statistics brought back
 SLAM_INTERNAL int finish_single_stage(slam_ctx* c, int k, int n, int64_t n_active, const slam_opt_params* prm, double exit_loss, double* best_loss,

@@ -43,27 +43,21 @@ int smush_eval_body(slam_ctx* c, int k, const int32_t* gate_seq, const double* x
     if (M < 0) return fail(SLAM_ERR_INVALID, "M < 0");
     if (M == 0) return SLAM_OK;
     if (!x || !target_of || !loss) return fail(SLAM_ERR_INVALID, "x, target_of and loss must be non-NULL");
-    for (int64_t m = 0; m < M; ++m)
-        if (target_of[m] < 0 || target_of[m] >= c->n_targets) return fail(SLAM_ERR_INVALID, "target_of[%lld] outside the resident batch", (long long)m);
     const SmushMap* d_maps = nullptr;
     rc = smush_stage_maps(c, k, gate_seq, &d_maps);
     if (rc) return rc;
     const int n = 6 * (k + 1) + c->smush_qn * k;
-    HIP_TRY(c->ev_x.reserve((size_t)M * n * sizeof(double)));
-    HIP_TRY(c->ev_tof.reserve((size_t)M * sizeof(int32_t)));
-    HIP_TRY(c->ev_loss.reserve((size_t)M * sizeof(double)));
-    if (grad) HIP_TRY(c->ev_grad.reserve((size_t)M * n * sizeof(double)));
-    if (unitary) HIP_TRY(c->ev_unitary.reserve((size_t)M * 32 * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(c->ev_x.p, x, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ev_tof.p, target_of, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    EvalBufs d{};
+    rc = stage_eval_inputs(c, x, target_of, M, n, grad != nullptr, unitary != nullptr, &d);
+    if (rc) return rc;
     SmushEvalArgs a{};
     a.targets = c->targets.as<double>();
-    a.x = c->ev_x.as<double>();
-    a.target_of = c->ev_tof.as<int32_t>();
+    a.x = d.x;
+    a.target_of = d.target_of;
     a.n_items = M;
-    a.loss = c->ev_loss.as<double>();
-    a.grad = grad ? c->ev_grad.as<double>() : nullptr;
-    a.unitary = unitary ? c->ev_unitary.as<double>() : nullptr;
+    a.loss = d.loss;
+    a.grad = d.grad;
+    a.unitary = d.unitary;
     a.cost_kind = c->cost_kind;
     a.maps = d_maps;
     a.k = k;
@@ -72,9 +66,8 @@ int smush_eval_body(slam_ctx* c, int k, const int32_t* gate_seq, const double* x
     const int64_t blocks = std::min<int64_t>(M, (int64_t)std::max(1, c->compute_units) * 16);
     hipLaunchKernelGGL(eval_smush_kernel, dim3((unsigned)blocks), dim3(kWave), kSmLdsBytes, c->stream, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(loss, c->ev_loss.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (grad) HIP_TRY(hipMemcpyAsync(grad, c->ev_grad.p, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (unitary) HIP_TRY(hipMemcpyAsync(unitary, c->ev_unitary.p, (size_t)M * 32 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    rc = enqueue_eval_readback(c, M, n, loss, grad, unitary);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SLAM_OK;
 }
@@ -95,33 +88,14 @@ int smush_minimize_body(slam_ctx* c, int k, const int32_t* gate_seq, const int32
     if (!init_lo || !init_hi) return fail(SLAM_ERR_INVALID, "init_lo and init_hi must be non-NULL");
     const int n = 6 * (k + 1) + c->smush_qn * k;
     const int64_t M = n_active * (int64_t)prm->restarts;
-    std::vector<double> b((size_t)4 * n);
-    bool bounded = false;
-    rc = pack_stage_bounds(n, init_lo, init_hi, bound_lo, bound_hi, b.data(), &bounded);
-    if (rc) return rc;
     const SmushMap* d_maps = nullptr;
     rc = smush_stage_maps(c, k, gate_seq, &d_maps);
     if (rc) return rc;
     const int32_t* d_active = nullptr;
-    rc = upload_stage_active(c, active, n_active, &d_active);
-    if (rc) return rc;
     const double* d_x0 = nullptr;
-    rc = upload_stage_x0(c, x0, M * n, &d_x0);
+    bool bounded = false;
+    rc = stage_family_inputs(c, k, n, active, n_active, x0, init_lo, init_hi, bound_lo, bound_hi, prm, &d_active, &d_x0, &bounded);
     if (rc) return rc;
-    HIP_TRY(c->v2_bounds.reserve(b.size() * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(c->v2_bounds.p, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // b is a local buffer
-    HIP_TRY(c->item_rec.reserve(M * sizeof(ItemRec)));
-    HIP_TRY(c->item_x.reserve(M * n * sizeof(double)));
-    HIP_TRY(c->stage_loss.reserve(n_active * sizeof(double)));
-    HIP_TRY(c->stage_x.reserve(n_active * n * sizeof(double)));
-    HIP_TRY(c->stage_restart.reserve(n_active * sizeof(int32_t)));
-    HIP_TRY(c->counters.reserve(sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2)));
-    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), c->stream));
-    rc = enqueue_set_n_active(c, k, n_active);
-    if (rc) return rc;
-    HIP_TRY(c->solved.reserve((size_t)n_active * sizeof(int32_t)));
-    HIP_TRY(hipMemsetAsync(c->solved.p, 0, (size_t)n_active * sizeof(int32_t), c->stream));
     int per_cu = 0;
     { rc = kernel_per_cu(c, reinterpret_cast<const void*>(&minimize_smush_kernel), kSmLdsBytes, &per_cu); if (rc) return rc; }
     const int64_t resident = (int64_t)per_cu * std::max(1, c->compute_units);

@@ -154,26 +154,17 @@ int v2_eval_body(slam_ctx* c, int k, const int32_t* gate_seq, const double* x, c
     if (M < 0) return fail(SLAM_ERR_INVALID, "M < 0");
     if (M == 0) return SLAM_OK;
     if (!x || !target_of || !loss) return fail(SLAM_ERR_INVALID, "x, target_of and loss must be non-NULL");
-    for (int64_t m = 0; m < M; ++m)
-        if (target_of[m] < 0 || target_of[m] >= c->n_targets) return fail(SLAM_ERR_INVALID, "target_of[%lld] outside the resident batch", (long long)m);
     const V2GateMap* d_maps = nullptr;
     int rc = v2_stage_maps(c, k, gate_seq, &d_maps);
     if (rc) return rc;
     const int n = 6 * (k + 1) + c->v2_qn * k;
-    HIP_TRY(c->ev_x.reserve((size_t)M * n * sizeof(double)));
-    HIP_TRY(c->ev_tof.reserve((size_t)M * sizeof(int32_t)));
-    HIP_TRY(c->ev_loss.reserve((size_t)M * sizeof(double)));
-    if (grad) HIP_TRY(c->ev_grad.reserve((size_t)M * n * sizeof(double)));
-    if (unitary) HIP_TRY(c->ev_unitary.reserve((size_t)M * 32 * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(c->ev_x.p, x, (size_t)M * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ev_tof.p, target_of, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    double* d_grad = grad ? c->ev_grad.as<double>() : nullptr;
-    double* d_unit = unitary ? c->ev_unitary.as<double>() : nullptr;
-    SLAM_V2_DISPATCH(v2_launch_eval, c, d_maps, c->ev_x.as<double>(), c->ev_tof.as<int32_t>(), M, c->ev_loss.as<double>(), d_grad, d_unit);
+    EvalBufs d{};
+    rc = stage_eval_inputs(c, x, target_of, M, n, grad != nullptr, unitary != nullptr, &d);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(loss, c->ev_loss.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (grad) HIP_TRY(hipMemcpyAsync(grad, c->ev_grad.p, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (unitary) HIP_TRY(hipMemcpyAsync(unitary, c->ev_unitary.p, (size_t)M * 32 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SLAM_V2_DISPATCH(v2_launch_eval, c, d_maps, d.x, d.target_of, M, d.loss, d.grad, d.unitary);
+    if (rc) return rc;
+    rc = enqueue_eval_readback(c, M, n, loss, grad, unitary);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SLAM_OK;
 }
@@ -198,33 +189,11 @@ int v2_minimize_body(slam_ctx* c, int k, const int32_t* gate_seq, const int32_t*
     rc = v2_stage_maps(c, k, gate_seq, &d_maps);
     if (rc) return rc;
     const int n = 6 * (k + 1) + c->v2_qn * k;
-    const int64_t M = n_active * (int64_t)prm->restarts;
-    std::vector<double> b((size_t)4 * n);
-    bool bounded = false;
-    rc = pack_stage_bounds(n, init_lo, init_hi, bound_lo, bound_hi, b.data(), &bounded);
-    if (rc) return rc;
     const int32_t* d_active = nullptr;
-    rc = upload_stage_active(c, active, n_active, &d_active);
-    if (rc) return rc;
     const double* d_x0 = nullptr;
-    rc = upload_stage_x0(c, x0, M * n, &d_x0);
+    bool bounded = false;
+    rc = stage_family_inputs(c, k, n, active, n_active, x0, init_lo, init_hi, bound_lo, bound_hi, prm, &d_active, &d_x0, &bounded);
     if (rc) return rc;
-    HIP_TRY(c->v2_bounds.reserve(b.size() * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(c->v2_bounds.p, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));  // b is a local buffer
-    {
-        // stage buffers sized for n parameters per item (reserve_stage_buffers sizes for 6 (k + 1))
-        HIP_TRY(c->item_rec.reserve(M * sizeof(ItemRec)));
-        HIP_TRY(c->item_x.reserve(M * n * sizeof(double)));
-        HIP_TRY(c->stage_loss.reserve(n_active * sizeof(double)));
-        HIP_TRY(c->stage_x.reserve(n_active * n * sizeof(double)));
-        HIP_TRY(c->stage_restart.reserve(n_active * sizeof(int32_t)));
-    }
-    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), c->stream));
-    rc = enqueue_set_n_active(c, k, n_active);
-    if (rc) return rc;
-    HIP_TRY(c->solved.reserve((size_t)n_active * sizeof(int32_t)));
-    HIP_TRY(hipMemsetAsync(c->solved.p, 0, (size_t)n_active * sizeof(int32_t), c->stream));
     bool riswap_like = c->v2_qn == 1;
     for (int j = 0; j < k && riswap_like; ++j) {
         const V2GateMap& gm = c->v2_gates_host[(size_t)gate_seq[j]];
@@ -341,47 +310,17 @@ int v2_decompose_body(slam_ctx* c, int64_t first, int64_t count, int k_min, int 
                     cur->as<int32_t>(), (int32_t)N, nullptr, c->v2_bounds.as<double>() + b_off[(size_t)si], prm};
         SLAM_V2_DISPATCH(v2_launch_minimize, c, sgt);
         if (rc) return rc;
-        EpilogueArgs e{};
-        e.r.item_rec = c->item_rec.as<ItemRec>();
-        e.r.item_x = c->item_x.as<double>();
-        e.r.exit_loss = success_threshold;
-        e.r.ordered = 1;
-        e.r.ctl = stage_ctl(c, k);
-        e.r.restarts = prm->restarts;
-        e.r.n = n;
-        e.r.stage_loss = c->stage_loss.as<double>();
-        e.r.stage_x = c->stage_x.as<double>();
-        e.r.stage_restart = c->stage_restart.as<int32_t>();
-        e.r.active = cur->as<int32_t>();
-        e.r.nmax = nmax;
-        e.r.k = k;
-        e.r.best_loss = c->best_loss.as<double>();
-        e.r.best_x = c->best_x.as<double>();
-        e.r.best_cycles = c->best_cycles.as<int32_t>();
-        e.r.span_loss = c->span_loss.as<double>();
-        e.has_next = k < k_max ? 1 : 0;
-        e.threshold = success_threshold;
-        e.active_out = nxt->as<int32_t>();
-        e.next = stage_ctl(c, k + 1);
-        e.targets = c->targets.as<double>();
-        e.stage_targets = c->stage_targets.as<double>();
-        e.solved = c->solved.as<int32_t>();
-        rc = enqueue_stage_epilogue(c, N, e);
+        const SpanLoopStep step{success_threshold, true, k < k_max, success_threshold, nxt->as<int32_t>()};
+        ReduceArgs r = build_reduce_args(c, k, n, cur->as<int32_t>(), prm, success_threshold, true);  // (rows of c->result_nmax = nmax)
+        r.ordered = 1;  // whatever the flags: the winner is the restart the reference's sequential loop breaks at
+        rc = enqueue_stage_epilogue(c, N, build_epilogue_args(c, k, r, step));
         if (rc) return rc;
         DevBuf* t = cur; cur = nxt; nxt = t;
     }
-    HIP_TRY(hipEventRecord(c->ev_t1, c->stream));
-    if (fetch) {
-        rc = enqueue_fetch_n(c, nmax, first, count, *fetch);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(c->h_ctl, c->counters.p, sizeof(StageCtl) * (SLAM_MAX_SPAN_EVAL + 2), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_done, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev_done));
-    if (fetch) finish_fetch(c, *fetch);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
-    c->stats.total_ms = ms;
+    rc = enqueue_loop_end(c, fetch, nmax, first, count);
+    if (rc) return rc;
+    rc = wait_loop_end(c, fetch);
+    if (rc) return rc;
     return collect_stats(c, k_min, k_max, c->h_ctl, prm->restarts);
 }
 
