@@ -81,18 +81,6 @@ __global__ __launch_bounds__(kCandRowsBlock) void candidate_rows_kernel(const do
     }
 }
 
-// does candidate g's row k (>= 2) contain the target?  (g, k) is wave-uniform: the row arrives by scalar loads
-__device__ __forceinline__ bool candidate_row_hit(const_as_ptr<double> r, const double (&sm)[2][kSpanPatterns], double tol) {
-    bool ok0 = true, ok1 = true;
-#pragma unroll
-    for (int p = 0; p < kSpanPatterns; ++p) {
-        const double lo = r[p] - tol;  // -inf stays -inf: no constraint
-        ok0 = ok0 && (sm[0][p] >= lo);
-        ok1 = ok1 && (sm[1][p] >= lo);
-    }
-    return ok0 || ok1;
-}
-
 // counts[group][g][k_cap + 2]: bins 0 .. k_cap - 1 = first reached at k = bin + 1, bin k_cap = local target, bin k_cap + 1 = not reached;
 // first_k[g][M] (or NULL): k, 0 local, k_cap + 1 not reached.  Block (x, y): targets [256 x, 256 x + 256), candidates [chunk y, chunk y + chunk).
 __global__ __launch_bounds__(kCandBlock) void candidate_scores_kernel(const double* __restrict__ U, int64_t M, int32_t G, int32_t chunk,
@@ -105,7 +93,7 @@ __global__ __launch_bounds__(kCandBlock) void candidate_scores_kernel(const doub
     const bool live = i < M;
     double pt[2][4], sm[2][kSpanPatterns];
     const bool local = coverage_target(U, i, live, pt, sm);
-    const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
+    const double t1 = point_tol(tol);
     const const_as_ptr<double> kpoints = (const_as_ptr<double>)points;
     const const_as_ptr<double> krows = (const_as_ptr<double>)rows;
     const int32_t nb = k_cap + 2;
@@ -115,21 +103,15 @@ __global__ __launch_bounds__(kCandBlock) void candidate_scores_kernel(const doub
     for (int32_t t0 = g_lo; t0 < g_hi; t0 += kCandTile) {
         const int32_t tn = g_hi - t0 < kCandTile ? g_hi - t0 : kCandTile;
         if (!group_of) {
-            for (int b = threadIdx.x; b < tn * nb; b += kCandBlock) hist[b] = 0u;
+            hist_clear(hist, tn * nb, kCandBlock);
             __syncthreads();
         }
         for (int32_t j = 0; j < tn; ++j) {
             const int32_t g = t0 + j;
             bool searching = live && !local;
             int32_t found = local ? 0 : k_cap + 1;
-            {
-                const const_as_ptr<double> q = kpoints + (int64_t)g * 4;
-                const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-                bool hit = false;
-#pragma unroll
-                for (int sh = 0; sh < 2; ++sh)
-                    hit = hit || (fabs(pt[sh][0] - q0) <= t1 && fabs(pt[sh][1] - q1) <= t1 && fabs(pt[sh][2] - q2) <= t1 &&
-                                  fabs(pt[sh][3] - q3) <= t1);
+            {  // k = 1
+                const bool hit = row_point_hit(pt, kpoints + (int64_t)g * 4, t1);
                 if (searching && hit) {
                     found = 1;
                     searching = false;
@@ -138,7 +120,7 @@ __global__ __launch_bounds__(kCandBlock) void candidate_scores_kernel(const doub
             const const_as_ptr<double> rg = krows + (int64_t)g * (k_cap - 1) * kSpanPatterns;
             for (int32_t k = 2; k <= k_cap; ++k) {
                 if (!__any(searching)) break;  // wave-uniform exit: (g, k) is the same in every lane
-                const bool hit = candidate_row_hit(rg + (int64_t)(k - 2) * kSpanPatterns, sm, tol);
+                const bool hit = row_bounds_hit(sm, rg + (int64_t)(k - 2) * kSpanPatterns, tol);
                 if (searching && hit) {
                     found = k;
                     searching = false;
@@ -155,10 +137,7 @@ __global__ __launch_bounds__(kCandBlock) void candidate_scores_kernel(const doub
         }
         if (!group_of) {
             __syncthreads();
-            for (int b = threadIdx.x; b < tn * nb; b += kCandBlock) {
-                const unsigned int v = hist[b];
-                if (v) atomicAdd(&counts[(int64_t)t0 * nb + b], (unsigned long long)v);
-            }
+            hist_fold(hist, tn * nb, kCandBlock, [&](int b) { return &counts[(int64_t)t0 * nb + b]; });
             __syncthreads();  // the next tile clears the histogram
         }
     }

@@ -8,6 +8,41 @@
 #include "slam_geometry_kernels.hpp"
 #include "slam_candidates.hpp"
 
+// One device (or host) buffer carved into typed sections: add<T>(n) appends n elements of T at the next offset aligned to alignof(T),
+// `total` is what to reserve, and a section gives its typed pointer from the buffer's base and its size in bytes.
+template <class T>
+struct Section {
+    size_t off, bytes;
+    T* at(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+};
+struct Carver {
+    size_t total = 0;
+    template <class T>
+    Section<T> add(size_t n) {
+        const size_t off = (total + alignof(T) - 1) & ~(alignof(T) - 1);
+        total = off + n * sizeof(T);
+        return {off, n * sizeof(T)};
+    }
+};
+
+// the window [first, first + count) of the resident targets; cap_int32: of at most 2^31 - 1 targets
+static int check_window(const slam_ctx* ctx, int64_t first, int64_t count, bool cap_int32) {
+    if (first < 0 || count < 0 || first + count > ctx->n_targets) return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (cap_int32 && count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    return SLAM_OK;
+}
+
+// what slam_coverage_lookup and slam_family_lookup ask of a row table in the same words (each has checks of its own in between)
+static int check_table_start(const int32_t* table_offsets) {
+    if (table_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "table_offsets[0] must be 0 (got %d)", table_offsets[0]);
+    return SLAM_OK;
+}
+static int check_row_kinds(const int32_t* kinds, int64_t E) {
+    for (int64_t e = 0; e < E; ++e)
+        if (kinds[e] != 0 && kinds[e] != 1) return fail(SLAM_ERR_INVALID, "kinds[%lld] = %d (0 = one gate, 1 = half-spaces)", (long long)e, kinds[e]);
+    return SLAM_OK;
+}
+
 int enqueue_c1c2c3(slam_ctx* c, const double* d_unitaries, int64_t count, int ndigits, double* d_out) {
     hipLaunchKernelGGL(c1c2c3_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, d_unitaries, count, ndigits, d_out);
     HIP_TRY(hipGetLastError());
@@ -84,9 +119,7 @@ int slam_kak(slam_ctx* ctx, const double* unitaries, int64_t count, double* phas
 
 int slam_targets_kak(slam_ctx* ctx, int64_t first, int64_t count, double* phase, double* a1, double* a2, double* c, double* b1, double* b2) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
-    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (int rc = check_window(ctx, first, count, true)) return rc;
     if (count == 0) return SLAM_OK;
     if (!phase || !a1 || !a2 || !c || !b1 || !b2) return fail(SLAM_ERR_INVALID, "phase, a1, a2, c, b1 and b2 must be non-NULL");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -154,8 +187,7 @@ int slam_c1c2c3(slam_ctx* ctx, const double* unitaries, int64_t count, int ndigi
 
 int slam_targets_c1c2c3(slam_ctx* ctx, int64_t first, int64_t count, int ndigits, double* out) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (int rc = check_window(ctx, first, count, false)) return rc;
     if (count == 0) return SLAM_OK;
     if (!out) return fail(SLAM_ERR_INVALID, "out is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -165,8 +197,7 @@ int slam_targets_c1c2c3(slam_ctx* ctx, int64_t first, int64_t count, int ndigits
 int slam_predict_spans(slam_ctx* ctx, int64_t first, int64_t count, int k_max, const double* point, const double* bounds, double tol,
                        int32_t* spans_out) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (int rc = check_window(ctx, first, count, false)) return rc;
     if (k_max < 1 || k_max > SLAM_MAX_SPAN_EVAL) return fail(SLAM_ERR_INVALID, "k_max must be 1..%d (got %d)", SLAM_MAX_SPAN_EVAL, k_max);
     if (!point || (k_max > 1 && !bounds)) return fail(SLAM_ERR_INVALID, "point / bounds is NULL");
     if (count == 0) return SLAM_OK;
@@ -183,12 +214,10 @@ int slam_predict_spans(slam_ctx* ctx, int64_t first, int64_t count, int k_max, c
 int slam_coverage_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_tables, const int32_t* table_offsets, const int32_t* kinds,
                          const double* points, const double* bounds, double tol, int64_t* counts_out, int32_t* entry_out) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
-    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (int rc = check_window(ctx, first, count, true)) return rc;
     if (n_tables < 1) return fail(SLAM_ERR_INVALID, "n_tables must be >= 1 (got %d)", n_tables);
     if (!table_offsets) return fail(SLAM_ERR_INVALID, "table_offsets is NULL");
-    if (table_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "table_offsets[0] must be 0 (got %d)", table_offsets[0]);
+    if (int rc = check_table_start(table_offsets)) return rc;
     int32_t max_bins = 0;
     for (int32_t t = 0; t < n_tables; ++t) {
         if (table_offsets[t + 1] < table_offsets[t])
@@ -200,35 +229,32 @@ int slam_coverage_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_
     }
     const int64_t E = table_offsets[n_tables];
     if (E > 0 && (!kinds || !points || !bounds)) return fail(SLAM_ERR_INVALID, "kinds / points / bounds is NULL");
-    for (int64_t e = 0; e < E; ++e)
-        if (kinds[e] != 0 && kinds[e] != 1) return fail(SLAM_ERR_INVALID, "kinds[%lld] = %d (0 = one gate, 1 = half-spaces)", (long long)e, kinds[e]);
+    if (int rc = check_row_kinds(kinds, E)) return rc;
     if (!counts_out) return fail(SLAM_ERR_INVALID, "counts_out is NULL");
     const int64_t n_counts = E + 2 * (int64_t)n_tables;
     std::memset(counts_out, 0, (size_t)n_counts * sizeof(int64_t));
     if (count == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    // one upload: offsets, kinds (int32), then points [E][4] and bounds [E][14] (doubles, 8-byte aligned)
-    const size_t off_b = 0, kind_b = (size_t)(n_tables + 1) * sizeof(int32_t);
-    const size_t pt_b = ((kind_b + (size_t)E * sizeof(int32_t)) + 7) & ~(size_t)7;
-    const size_t bd_b = pt_b + (size_t)E * 4 * sizeof(double);
-    const size_t total_b = bd_b + (size_t)E * kSpanPatterns * sizeof(double);
-    HIP_TRY(ctx->cov_table.reserve(total_b));
+    // one upload: offsets, kinds (int32), then points [E][4] and bounds [E][14] (doubles)
+    Carver cv;
+    const auto s_off = cv.add<int32_t>((size_t)n_tables + 1), s_kind = cv.add<int32_t>((size_t)E);
+    const auto s_pt = cv.add<double>((size_t)E * 4), s_bd = cv.add<double>((size_t)E * kSpanPatterns);
+    HIP_TRY(ctx->cov_table.reserve(cv.total));
     HIP_TRY(ctx->cov_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
     if (entry_out) HIP_TRY(ctx->cov_entries.reserve((size_t)n_tables * (size_t)count * sizeof(int32_t)));
     char* tb = ctx->cov_table.as<char>();
-    HIP_TRY(hipMemcpyAsync(tb + off_b, table_offsets, kind_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s_off.at(tb), table_offsets, s_off.bytes, hipMemcpyHostToDevice, ctx->stream));
     if (E > 0) {
-        HIP_TRY(hipMemcpyAsync(tb + kind_b, kinds, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(tb + pt_b, points, (size_t)E * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(tb + bd_b, bounds, (size_t)E * kSpanPatterns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(s_kind.at(tb), kinds, s_kind.bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(s_pt.at(tb), points, s_pt.bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(s_bd.at(tb), bounds, s_bd.bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     HIP_TRY(hipMemsetAsync(ctx->cov_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
     const int32_t lds_bins = max_bins < kCoverageLdsBins ? max_bins : kCoverageLdsBins;
     hipLaunchKernelGGL(coverage_lookup_kernel, dim3((unsigned)((count + kCoverageBlock - 1) / kCoverageBlock)), dim3(kCoverageBlock),
                        (size_t)lds_bins * sizeof(unsigned int), ctx->stream, ctx->targets.as<double>() + first * 32, count, n_tables,
-                       reinterpret_cast<const int32_t*>(tb + off_b), reinterpret_cast<const int32_t*>(tb + kind_b),
-                       reinterpret_cast<const double*>(tb + pt_b), reinterpret_cast<const double*>(tb + bd_b), tol, lds_bins,
-                       ctx->cov_counts.as<unsigned long long>(), entry_out ? ctx->cov_entries.as<int32_t>() : nullptr);
+                       s_off.at(tb), s_kind.at(tb), s_pt.at(tb), s_bd.at(tb), tol, lds_bins, ctx->cov_counts.as<unsigned long long>(),
+                       entry_out ? ctx->cov_entries.as<int32_t>() : nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(counts_out, ctx->cov_counts.p, (size_t)n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (entry_out)
@@ -243,23 +269,20 @@ int slam_family_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_me
                        const double* durations, double cost_1q, double tol, int32_t policy, int64_t* counts_out, int64_t* base_counts_out,
                        int32_t* member_out, int32_t* gates_out) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
-    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (int rc = check_window(ctx, first, count, true)) return rc;
     static_assert(SLAM_FAMILY_MAX_MEMBERS == kFamilyMaxMembers, "family size");
     if (n_members < 1 || n_members > SLAM_FAMILY_MAX_MEMBERS)
         return fail(SLAM_ERR_INVALID, "n_members must be in 1..%d (got %d)", SLAM_FAMILY_MAX_MEMBERS, n_members);
     if (!table_offsets || !kinds || !points || !bounds) return fail(SLAM_ERR_INVALID, "table_offsets / kinds / points / bounds is NULL");
     if (!child_even || !child_odd || !durations) return fail(SLAM_ERR_INVALID, "child_even / child_odd / durations is NULL");
-    if (table_offsets[0] != 0) return fail(SLAM_ERR_INVALID, "table_offsets[0] must be 0 (got %d)", table_offsets[0]);
+    if (int rc = check_table_start(table_offsets)) return rc;
     for (int32_t m = 0; m < n_members; ++m)
         if (table_offsets[m + 1] <= table_offsets[m])
             return fail(SLAM_ERR_INVALID, "every member needs at least one row (offsets[%d] = %d, offsets[%d] = %d)", m, table_offsets[m], m + 1,
                         table_offsets[m + 1]);
     const int64_t E = table_offsets[n_members], E0 = table_offsets[1];
     if (E + E0 + 4 > kFamilyMaxBins) return fail(SLAM_ERR_INVALID, "too many coverage rows (%lld; at most %d bins)", (long long)E, kFamilyMaxBins);
-    for (int64_t e = 0; e < E; ++e)
-        if (kinds[e] != 0 && kinds[e] != 1) return fail(SLAM_ERR_INVALID, "kinds[%lld] = %d (0 = one gate, 1 = half-spaces)", (long long)e, kinds[e]);
+    if (int rc = check_row_kinds(kinds, E)) return rc;
     for (int32_t m = 0; m < n_members; ++m) {
         // a child has a larger index than its parent: the kernel's one ascending pass over the members relies on it
         if (child_even[m] != -1 && (child_even[m] <= m || child_even[m] >= n_members))
@@ -275,22 +298,20 @@ int slam_family_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_me
     std::memset(base_counts_out, 0, (size_t)(E0 + 2) * sizeof(int64_t));
     if (count == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    // one upload: offsets, kinds, both child lists (int32), then points [E][4], bounds [E][14] and the rows' costs [E] (doubles, 8-byte
-    // aligned).  The costs are computed here, once per row, so that the device compares the very doubles the caller sums.
-    const size_t off_b = 0, kind_b = (size_t)(n_members + 1) * sizeof(int32_t), ce_b = kind_b + (size_t)E * sizeof(int32_t);
-    const size_t co_b = ce_b + (size_t)n_members * sizeof(int32_t);
-    const size_t pt_b = ((co_b + (size_t)n_members * sizeof(int32_t)) + 7) & ~(size_t)7;
-    const size_t bd_b = pt_b + (size_t)E * 4 * sizeof(double);
-    const size_t cs_b = bd_b + (size_t)E * kSpanPatterns * sizeof(double);
-    const size_t total_b = cs_b + (size_t)E * sizeof(double);
-    std::vector<char> host(total_b, 0);
-    std::memcpy(host.data() + off_b, table_offsets, kind_b);
-    std::memcpy(host.data() + kind_b, kinds, (size_t)E * sizeof(int32_t));
-    std::memcpy(host.data() + ce_b, child_even, (size_t)n_members * sizeof(int32_t));
-    std::memcpy(host.data() + co_b, child_odd, (size_t)n_members * sizeof(int32_t));
-    std::memcpy(host.data() + pt_b, points, (size_t)E * 4 * sizeof(double));
-    std::memcpy(host.data() + bd_b, bounds, (size_t)E * kSpanPatterns * sizeof(double));
-    double* row_cost = reinterpret_cast<double*>(host.data() + cs_b);
+    // one upload: offsets, kinds, both child lists (int32), then points [E][4], bounds [E][14] and the rows' costs [E] (doubles).
+    // The costs are computed here, once per row, so that the device compares the very doubles the caller sums.
+    Carver cv;
+    const auto s_off = cv.add<int32_t>((size_t)n_members + 1), s_kind = cv.add<int32_t>((size_t)E);
+    const auto s_ce = cv.add<int32_t>((size_t)n_members), s_co = cv.add<int32_t>((size_t)n_members);
+    const auto s_pt = cv.add<double>((size_t)E * 4), s_bd = cv.add<double>((size_t)E * kSpanPatterns), s_cs = cv.add<double>((size_t)E);
+    std::vector<char> host(cv.total, 0);
+    std::memcpy(s_off.at(host.data()), table_offsets, s_off.bytes);
+    std::memcpy(s_kind.at(host.data()), kinds, s_kind.bytes);
+    std::memcpy(s_ce.at(host.data()), child_even, s_ce.bytes);
+    std::memcpy(s_co.at(host.data()), child_odd, s_co.bytes);
+    std::memcpy(s_pt.at(host.data()), points, s_pt.bytes);
+    std::memcpy(s_bd.at(host.data()), bounds, s_bd.bytes);
+    double* row_cost = s_cs.at(host.data());
     for (int32_t m = 0; m < n_members; ++m)
         for (int32_t e = table_offsets[m]; e < table_offsets[m + 1]; ++e) {
             const double k = (double)(e - table_offsets[m] + 1);
@@ -298,22 +319,19 @@ int slam_family_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_me
             row_cost[e] = c1 + c2;  // (k + 1) cost_1q + k duration_m: two products and a sum, each rounded
         }
     const int64_t n_counts = E + 2 + E0 + 2;
-    HIP_TRY(ctx->cov_table.reserve(total_b));
+    HIP_TRY(ctx->cov_table.reserve(cv.total));
     HIP_TRY(ctx->cov_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
     const bool want = member_out || gates_out;
     if (want) HIP_TRY(ctx->cov_entries.reserve(2 * (size_t)count * sizeof(int32_t)));
     char* tb = ctx->cov_table.as<char>();
-    HIP_TRY(hipMemcpyAsync(tb, host.data(), total_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(tb, host.data(), cv.total, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->cov_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
     unsigned long long* d_counts = ctx->cov_counts.as<unsigned long long>();
     int32_t* d_member = want ? ctx->cov_entries.as<int32_t>() : nullptr;
     hipLaunchKernelGGL(family_lookup_kernel, dim3((unsigned)((count + kCoverageBlock - 1) / kCoverageBlock)), dim3(kCoverageBlock),
                        (size_t)n_counts * sizeof(unsigned int), ctx->stream, ctx->targets.as<double>() + first * 32, count, n_members,
-                       reinterpret_cast<const int32_t*>(tb + off_b), reinterpret_cast<const int32_t*>(tb + kind_b),
-                       reinterpret_cast<const double*>(tb + pt_b), reinterpret_cast<const double*>(tb + bd_b),
-                       reinterpret_cast<const double*>(tb + cs_b), reinterpret_cast<const int32_t*>(tb + ce_b),
-                       reinterpret_cast<const int32_t*>(tb + co_b), tol, policy, d_counts, d_counts + (E + 2), d_member,
-                       want ? d_member + count : nullptr);
+                       s_off.at(tb), s_kind.at(tb), s_pt.at(tb), s_bd.at(tb), s_cs.at(tb), s_ce.at(tb), s_co.at(tb), tol, policy, d_counts,
+                       d_counts + (E + 2), d_member, want ? d_member + count : nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(counts_out, d_counts, (size_t)(E + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(base_counts_out, d_counts + (E + 2), (size_t)(E0 + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -328,9 +346,7 @@ int slam_candidate_scores(slam_ctx* ctx, int64_t first, int64_t count, int32_t n
                           double* kernel_ms_out) {
     static_assert(SLAM_CANDIDATE_MAX_K == kCandMaxK, "candidate k_cap");
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
-    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (int rc = check_window(ctx, first, count, true)) return rc;
     if (n_candidates < 1 || n_candidates > SLAM_CANDIDATE_MAX_GATES)
         return fail(SLAM_ERR_INVALID, "n_candidates must be in 1..%d (got %d)", SLAM_CANDIDATE_MAX_GATES, n_candidates);
     if (k_cap < 1 || k_cap > SLAM_CANDIDATE_MAX_K) return fail(SLAM_ERR_INVALID, "k_cap must be in 1..%d (got %d)", SLAM_CANDIDATE_MAX_K, k_cap);
@@ -353,15 +369,16 @@ int slam_candidate_scores(slam_ctx* ctx, int64_t first, int64_t count, int32_t n
     if (count == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     // one buffer: coordinates [G][3], alcove points [G][4], rows [G][k_cap - 1][14] (doubles), then the groups (int32)
-    const size_t pt_b = (size_t)G * 3 * sizeof(double), row_b = pt_b + (size_t)G * 4 * sizeof(double);
-    const size_t grp_b = row_b + (size_t)G * (size_t)(k_cap - 1) * kSpanPatterns * sizeof(double);
-    const size_t total_b = grp_b + (group_of ? (size_t)count * sizeof(int32_t) : 0);
-    HIP_TRY(ctx->cov_table.reserve(total_b));
+    Carver cv;
+    const auto s_crd = cv.add<double>((size_t)G * 3), s_pt = cv.add<double>((size_t)G * 4);
+    const auto s_row = cv.add<double>((size_t)G * (size_t)(k_cap - 1) * kSpanPatterns);
+    const auto s_grp = cv.add<int32_t>(group_of ? (size_t)count : 0);
+    HIP_TRY(ctx->cov_table.reserve(cv.total));
     HIP_TRY(ctx->cov_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
     if (first_k_out) HIP_TRY(ctx->cov_entries.reserve((size_t)G * (size_t)count * sizeof(int32_t)));
     char* tb = ctx->cov_table.as<char>();
-    HIP_TRY(hipMemcpyAsync(tb, cand_coords, pt_b, hipMemcpyHostToDevice, ctx->stream));
-    if (group_of) HIP_TRY(hipMemcpyAsync(tb + grp_b, group_of, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s_crd.at(tb), cand_coords, s_crd.bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (group_of) HIP_TRY(hipMemcpyAsync(s_grp.at(tb), group_of, s_grp.bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->cov_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (kernel_ms_out) {
@@ -373,8 +390,7 @@ int slam_candidate_scores(slam_ctx* ctx, int64_t first, int64_t count, int32_t n
         (void)hipEventRecord(ev0, ctx->stream);
     }
     hipLaunchKernelGGL(candidate_rows_kernel, dim3((unsigned)((G + kCandRowsBlock - 1) / kCandRowsBlock)), dim3(kCandRowsBlock), 0, ctx->stream,
-                       reinterpret_cast<const double*>(tb), (int32_t)G, k_cap, reinterpret_cast<double*>(tb + pt_b),
-                       reinterpret_cast<double*>(tb + row_b));
+                       s_crd.at(tb), (int32_t)G, k_cap, s_pt.at(tb), s_row.at(tb));
     // candidates split over grid.y until the launch has about 2048 blocks: a circuit's few hundred targets still fill the device,
     // a large batch keeps one chunk (the target's Weyl coordinates are computed once per block)
     const int64_t t_blocks = (count + kCandBlock - 1) / kCandBlock;
@@ -384,9 +400,9 @@ int slam_candidate_scores(slam_ctx* ctx, int64_t first, int64_t count, int32_t n
     const int32_t chunk = (int32_t)((G + n_chunks - 1) / n_chunks);
     n_chunks = (G + chunk - 1) / chunk;
     hipLaunchKernelGGL(candidate_scores_kernel, dim3((unsigned)t_blocks, (unsigned)n_chunks), dim3(kCandBlock), 0, ctx->stream,
-                       ctx->targets.as<double>() + first * 32, count, (int32_t)G, chunk, k_cap, reinterpret_cast<const double*>(tb + pt_b),
-                       reinterpret_cast<const double*>(tb + row_b), tol, group_of ? reinterpret_cast<const int32_t*>(tb + grp_b) : nullptr,
-                       ctx->cov_counts.as<unsigned long long>(), first_k_out ? ctx->cov_entries.as<int32_t>() : nullptr);
+                       ctx->targets.as<double>() + first * 32, count, (int32_t)G, chunk, k_cap, s_pt.at(tb), s_row.at(tb), tol,
+                       group_of ? s_grp.at(tb) : nullptr, ctx->cov_counts.as<unsigned long long>(),
+                       first_k_out ? ctx->cov_entries.as<int32_t>() : nullptr);
     const hipError_t launch_err = hipGetLastError();
     if (kernel_ms_out) (void)hipEventRecord(ev1, ctx->stream);
     hipError_t err = launch_err;
@@ -462,10 +478,12 @@ int slam_haar_select_spans(slam_ctx* ctx, uint64_t seed, int64_t first_index, in
     HIP_TRY(hipSetDevice(ctx->device));
     const int64_t n_blocks = (n_candidates + kSelBlock - 1) / kSelBlock;
     const int64_t cap = capacity < n_candidates ? capacity : n_candidates;
-    // sel_blocks: votes per block [n_blocks], their exclusive scan [n_blocks] (32 bits each), then the total (64 bits, 8-byte aligned)
-    const size_t tot_b = 0, off_b = (size_t)n_blocks * sizeof(uint32_t), sum_b = (2 * off_b + 7) & ~(size_t)7;
+    // sel_blocks: votes per block [n_blocks], their exclusive scan [n_blocks] (32 bits each), then the total (64 bits)
+    Carver cv;
+    const auto s_tot = cv.add<uint32_t>((size_t)n_blocks), s_scan = cv.add<uint32_t>((size_t)n_blocks);
+    const auto s_sum = cv.add<unsigned long long>(1);
     HIP_TRY(ctx->sel_masks.reserve((size_t)n_blocks * kSelWaves * sizeof(unsigned long long)));
-    HIP_TRY(ctx->sel_blocks.reserve(sum_b + sizeof(unsigned long long)));
+    HIP_TRY(ctx->sel_blocks.reserve(cv.total));
     HIP_TRY(ctx->sel_counts.reserve(kSelBins * sizeof(unsigned long long)));
     if (cap > 0) HIP_TRY(ctx->sel_indices.reserve((size_t)cap * sizeof(int64_t)));
     char* bl = ctx->sel_blocks.as<char>();
@@ -479,18 +497,17 @@ int slam_haar_select_spans(slam_ctx* ctx, uint64_t seed, int64_t first_index, in
     a.span_lo = span_lo;
     a.span_hi = span_hi;
     hipLaunchKernelGGL(haar_span_select_kernel, dim3((unsigned)n_blocks), dim3(kSelBlock), 0, ctx->stream, r, a,
-                       ctx->sel_masks.as<unsigned long long>(), reinterpret_cast<uint32_t*>(bl + tot_b), ctx->sel_counts.as<unsigned long long>());
+                       ctx->sel_masks.as<unsigned long long>(), s_tot.at(bl), ctx->sel_counts.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, reinterpret_cast<const uint32_t*>(bl + tot_b), n_blocks,
-                       reinterpret_cast<uint32_t*>(bl + off_b), reinterpret_cast<unsigned long long*>(bl + sum_b));
+    hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, s_tot.at(bl), n_blocks, s_scan.at(bl), s_sum.at(bl));
     HIP_TRY(hipGetLastError());
     if (cap > 0) {
         hipLaunchKernelGGL(span_scatter_kernel, dim3((unsigned)n_blocks), dim3(kSelBlock), 0, ctx->stream, ctx->sel_masks.as<unsigned long long>(),
-                           reinterpret_cast<const uint32_t*>(bl + off_b), first_index, cap, ctx->sel_indices.as<int64_t>());
+                           s_scan.at(bl), first_index, cap, ctx->sel_indices.as<int64_t>());
         HIP_TRY(hipGetLastError());
     }
     unsigned long long total = 0, counts[kSelBins] = {0};
-    HIP_TRY(hipMemcpyAsync(&total, bl + sum_b, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&total, s_sum.at(bl), sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(counts, ctx->sel_counts.p, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *n_selected = (int64_t)total;
@@ -506,8 +523,7 @@ int slam_haar_select_spans(slam_ctx* ctx, uint64_t seed, int64_t first_index, in
 
 int slam_get_targets(slam_ctx* ctx, int64_t first, int64_t count, double* out) {
     if (!ctx || !out) return fail(SLAM_ERR_INVALID, "NULL argument");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (int rc = check_window(ctx, first, count, false)) return rc;
     if (count == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpyAsync(out, ctx->targets.as<double>() + first * 32, (size_t)count * 32 * sizeof(double),
@@ -545,22 +561,23 @@ int slam_pd_sample(slam_ctx* ctx, double gc, double gg, double t, int32_t n_slic
     sp.n_params = 6 * (k - 1) + k * (2 + 2 * n_slices);
     sp.seed = seed;
     // staging: indices, then parameter rows, then unitaries
-    const size_t idx_b = indices ? (size_t)n_samples * sizeof(int64_t) : 0;
-    const size_t prm_b = params_out ? (size_t)n_samples * sp.n_params * sizeof(double) : 0;
-    const size_t uni_b = unitaries_out ? (size_t)n_samples * 32 * sizeof(double) : 0;
+    Carver cv;
+    const auto s_idx = cv.add<int64_t>(indices ? (size_t)n_samples : 0);
+    const auto s_prm = cv.add<double>(params_out ? (size_t)n_samples * sp.n_params : 0);
+    const auto s_uni = cv.add<double>(unitaries_out ? (size_t)n_samples * 32 : 0);
     HIP_TRY(ctx->pd_coords.reserve((size_t)n_samples * 3 * sizeof(double)));
     ctx->pd_n = 0;
-    if (idx_b + prm_b + uni_b) HIP_TRY(ctx->pd_stage.reserve(idx_b + prm_b + uni_b));
+    if (cv.total) HIP_TRY(ctx->pd_stage.reserve(cv.total));
     char* st = ctx->pd_stage.as<char>();
-    if (indices) HIP_TRY(hipMemcpyAsync(st, indices, idx_b, hipMemcpyHostToDevice, ctx->stream));
+    if (indices) HIP_TRY(hipMemcpyAsync(s_idx.at(st), indices, s_idx.bytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(pd_sample_kernel, dim3((unsigned)((n_samples + kPdBlock - 1) / kPdBlock)), dim3(kPdBlock), 0, ctx->stream, sp,
-                       first_index, n_samples, indices ? reinterpret_cast<const int64_t*>(st) : nullptr, ndigits, ctx->pd_coords.as<double>(),
-                       params_out ? reinterpret_cast<double*>(st + idx_b) : nullptr, unitaries_out ? reinterpret_cast<double*>(st + idx_b + prm_b) : nullptr);
+                       first_index, n_samples, indices ? s_idx.at(st) : nullptr, ndigits, ctx->pd_coords.as<double>(),
+                       params_out ? s_prm.at(st) : nullptr, unitaries_out ? s_uni.at(st) : nullptr);
     HIP_TRY(hipGetLastError());
     if (coords_out)
         HIP_TRY(hipMemcpyAsync(coords_out, ctx->pd_coords.p, (size_t)n_samples * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (params_out) HIP_TRY(hipMemcpyAsync(params_out, st + idx_b, prm_b, hipMemcpyDeviceToHost, ctx->stream));
-    if (unitaries_out) HIP_TRY(hipMemcpyAsync(unitaries_out, st + idx_b + prm_b, uni_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (params_out) HIP_TRY(hipMemcpyAsync(params_out, s_prm.at(st), s_prm.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (unitaries_out) HIP_TRY(hipMemcpyAsync(unitaries_out, s_uni.at(st), s_uni.bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->pd_n = n_samples;
     return SLAM_OK;
@@ -575,22 +592,24 @@ int slam_pd_extremes(slam_ctx* ctx, const double* directions, int32_t n_dirs, in
         if (!std::isfinite(directions[d])) return fail(SLAM_ERR_INVALID, "directions must be finite");
     HIP_TRY(hipSetDevice(ctx->device));
     // staging: directions [n_dirs][3], keys [n_dirs], indices [n_dirs], coordinates [n_dirs][3]
-    const size_t dir_b = (size_t)n_dirs * 3 * sizeof(double), key_b = (size_t)n_dirs * sizeof(unsigned long long);
-    const size_t idx_b = (size_t)n_dirs * sizeof(int64_t), crd_b = (size_t)n_dirs * 3 * sizeof(double);
-    HIP_TRY(ctx->pd_out.reserve(dir_b + key_b + idx_b + crd_b));
+    Carver cv;
+    const auto s_dir = cv.add<double>((size_t)n_dirs * 3);
+    const auto s_key = cv.add<unsigned long long>((size_t)n_dirs);
+    const auto s_idx = cv.add<int64_t>((size_t)n_dirs);
+    const auto s_crd = cv.add<double>((size_t)n_dirs * 3);
+    HIP_TRY(ctx->pd_out.reserve(cv.total));
     char* b = ctx->pd_out.as<char>();
-    HIP_TRY(hipMemcpyAsync(b, directions, dir_b, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(b + dir_b, 0, key_b, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s_dir.at(b), directions, s_dir.bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(s_key.at(b), 0, s_key.bytes, ctx->stream));
     const int64_t n = ctx->pd_n;
     hipLaunchKernelGGL(pd_extremes_kernel, dim3((unsigned)((n + kPdScanBlock - 1) / kPdScanBlock)), dim3(kPdScanBlock), 0, ctx->stream,
-                       ctx->pd_coords.as<double>(), n, reinterpret_cast<const double*>(b), n_dirs, reinterpret_cast<unsigned long long*>(b + dir_b));
+                       ctx->pd_coords.as<double>(), n, s_dir.at(b), n_dirs, s_key.at(b));
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(pd_gather_kernel, dim3((unsigned)((n_dirs + 63) / 64)), dim3(64), 0, ctx->stream, ctx->pd_coords.as<double>(),
-                       reinterpret_cast<const unsigned long long*>(b + dir_b), n_dirs, reinterpret_cast<int64_t*>(b + dir_b + key_b),
-                       reinterpret_cast<double*>(b + dir_b + key_b + idx_b));
+                       s_key.at(b), n_dirs, s_idx.at(b), s_crd.at(b));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(index_out, b + dir_b + key_b, idx_b, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(coords_out, b + dir_b + key_b + idx_b, crd_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(index_out, s_idx.at(b), s_idx.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(coords_out, s_crd.at(b), s_crd.bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return SLAM_OK;
 }
@@ -607,25 +626,27 @@ int slam_pd_filter(slam_ctx* ctx, const double* facets, int32_t n_facets, double
         if (!std::isfinite(facets[f])) return fail(SLAM_ERR_INVALID, "facets must be finite");
     HIP_TRY(hipSetDevice(ctx->device));
     const int64_t n = ctx->pd_n;
-    // staging: facets [n_facets][4], the counter (8 bytes), indices [n], coordinates [n][3]
-    const size_t fac_b = ((size_t)n_facets * 4 * sizeof(double) + 7) & ~(size_t)7, cnt_b = 8;
-    const size_t idx_b = (size_t)n * sizeof(int64_t), crd_b = (size_t)n * 3 * sizeof(double);
-    HIP_TRY(ctx->pd_out.reserve(fac_b + cnt_b + idx_b + crd_b));
+    // staging: facets [n_facets][4], the counter, indices [n], coordinates [n][3]
+    Carver cv;
+    const auto s_fac = cv.add<double>((size_t)n_facets * 4);
+    const auto s_cnt = cv.add<unsigned int>(1);
+    const auto s_idx = cv.add<int64_t>((size_t)n);
+    const auto s_crd = cv.add<double>((size_t)n * 3);
+    HIP_TRY(ctx->pd_out.reserve(cv.total));
     char* b = ctx->pd_out.as<char>();
-    if (n_facets > 0) HIP_TRY(hipMemcpyAsync(b, facets, (size_t)n_facets * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(b + fac_b, 0, cnt_b, ctx->stream));
+    if (n_facets > 0) HIP_TRY(hipMemcpyAsync(s_fac.at(b), facets, s_fac.bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(s_cnt.at(b), 0, s_cnt.bytes, ctx->stream));
     hipLaunchKernelGGL(pd_filter_kernel, dim3((unsigned)((n + kPdScanBlock - 1) / kPdScanBlock)), dim3(kPdScanBlock), 0, ctx->stream,
-                       ctx->pd_coords.as<double>(), n, reinterpret_cast<const double*>(b), n_facets, eps, reinterpret_cast<unsigned int*>(b + fac_b),
-                       reinterpret_cast<int64_t*>(b + fac_b + cnt_b), reinterpret_cast<double*>(b + fac_b + cnt_b + idx_b));
+                       ctx->pd_coords.as<double>(), n, s_fac.at(b), n_facets, eps, s_cnt.at(b), s_idx.at(b), s_crd.at(b));
     HIP_TRY(hipGetLastError());
     unsigned int m = 0;
-    HIP_TRY(hipMemcpyAsync(&m, b + fac_b, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&m, s_cnt.at(b), sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *n_out = (int64_t)m;
     const int64_t copy = (int64_t)m < capacity ? (int64_t)m : capacity;
     if (copy > 0) {
-        HIP_TRY(hipMemcpyAsync(index_out, b + fac_b + cnt_b, (size_t)copy * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(coords_out, b + fac_b + cnt_b + idx_b, (size_t)copy * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(index_out, s_idx.at(b), (size_t)copy * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(coords_out, s_crd.at(b), (size_t)copy * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     return SLAM_OK;
@@ -634,8 +655,7 @@ int slam_pd_filter(slam_ctx* ctx, const double* facets, int32_t n_facets, double
 int slam_region_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_regions, const int32_t* region_offsets, const int32_t* kinds,
                        const int32_t* facet_offsets, const double* facets, const double* aux, double tol, int64_t* counts_out) {
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets) return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
-    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (int rc = check_window(ctx, first, count, true)) return rc;
     if (n_regions < 1 || n_regions > SLAM_REGION_MAX) return fail(SLAM_ERR_INVALID, "n_regions must be in 1..%d (got %d)", SLAM_REGION_MAX, n_regions);
     if (!region_offsets || !counts_out) return fail(SLAM_ERR_INVALID, "region_offsets / counts_out is NULL");
     if (!std::isfinite(tol)) return fail(SLAM_ERR_INVALID, "tol must be finite");
@@ -661,28 +681,25 @@ int slam_region_lookup(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_re
     std::memset(counts_out, 0, (size_t)n_counts * sizeof(int64_t));
     if (count == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    // one upload: region offsets, kinds, facet offsets (int32), then facets [F][4] and aux [P][14] (doubles, 8-byte aligned)
-    const size_t ro_b = 0, ki_b = (size_t)(n_regions + 1) * sizeof(int32_t), fo_b = ki_b + (size_t)P * sizeof(int32_t);
-    const size_t fa_b = ((fo_b + (size_t)(P + 1) * sizeof(int32_t)) + 7) & ~(size_t)7;
-    const size_t ax_b = fa_b + (size_t)F * 4 * sizeof(double);
-    const size_t total_b = ax_b + (size_t)P * kSpanPatterns * sizeof(double);
-    HIP_TRY(ctx->reg_table.reserve(total_b));
+    // one upload: region offsets, kinds, facet offsets (int32), then facets [F][4] and aux [P][14] (doubles)
+    Carver cv;
+    const auto s_ro = cv.add<int32_t>((size_t)n_regions + 1), s_ki = cv.add<int32_t>((size_t)P), s_fo = cv.add<int32_t>((size_t)P + 1);
+    const auto s_fa = cv.add<double>((size_t)F * 4), s_ax = cv.add<double>((size_t)P * kSpanPatterns);
+    HIP_TRY(ctx->reg_table.reserve(cv.total));
     HIP_TRY(ctx->reg_counts.reserve((size_t)n_counts * sizeof(unsigned long long)));
     char* tb = ctx->reg_table.as<char>();
-    HIP_TRY(hipMemcpyAsync(tb + ro_b, region_offsets, ki_b, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s_ro.at(tb), region_offsets, s_ro.bytes, hipMemcpyHostToDevice, ctx->stream));
     if (P > 0) {
-        HIP_TRY(hipMemcpyAsync(tb + ki_b, kinds, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(tb + fo_b, facet_offsets, (size_t)(P + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        if (F > 0) HIP_TRY(hipMemcpyAsync(tb + fa_b, facets, (size_t)F * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        if (aux) HIP_TRY(hipMemcpyAsync(tb + ax_b, aux, (size_t)P * kSpanPatterns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(s_ki.at(tb), kinds, s_ki.bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(s_fo.at(tb), facet_offsets, s_fo.bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (F > 0) HIP_TRY(hipMemcpyAsync(s_fa.at(tb), facets, s_fa.bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (aux) HIP_TRY(hipMemcpyAsync(s_ax.at(tb), aux, s_ax.bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     HIP_TRY(hipMemsetAsync(ctx->reg_counts.p, 0, (size_t)n_counts * sizeof(unsigned long long), ctx->stream));
     static_assert(SLAM_REGION_MAX == kRegionMax, "region table size");
     hipLaunchKernelGGL(region_lookup_kernel, dim3((unsigned)((count + kRegionBlock - 1) / kRegionBlock)), dim3(kRegionBlock), 0, ctx->stream,
-                       ctx->targets.as<double>() + first * 32, count, n_regions, reinterpret_cast<const int32_t*>(tb + ro_b),
-                       reinterpret_cast<const int32_t*>(tb + ki_b), reinterpret_cast<const int32_t*>(tb + fo_b),
-                       reinterpret_cast<const double*>(tb + fa_b), reinterpret_cast<const double*>(tb + ax_b), tol,
-                       ctx->reg_counts.as<unsigned long long>());
+                       ctx->targets.as<double>() + first * 32, count, n_regions, s_ro.at(tb), s_ki.at(tb), s_fo.at(tb), s_fa.at(tb), s_ax.at(tb),
+                       tol, ctx->reg_counts.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(counts_out, ctx->reg_counts.p, (size_t)n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -16,9 +16,10 @@ __global__ void c1c2c3_kernel(const double* __restrict__ U, int64_t M, int ndigi
 __global__ void span_predict_kernel(const double* __restrict__ U, int64_t M, SpanRegions r, int32_t* __restrict__ spans) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
-    double c[3];
+    double c[3], pt[2][4], sm[2][kSpanPatterns];
     weyl_c1c2c3(U + i * 32, 8, c);
-    spans[i] = span_classify(c, r, r.tol);
+    const bool local = target_frame(c, pt, sm);
+    spans[i] = span_classify(local, pt, sm, r, r.tol);
 }
 
 constexpr int kCoverageBlock = 256;
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(kCoverageBlock) void coverage_lookup_kernel(
     const bool live = i < M;
     double pt[2][4], sm[2][kSpanPatterns];
     const bool local = coverage_target(U, i, live, pt, sm);
-    const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
+    const double t1 = point_tol(tol);
     const const_as_ptr<int32_t> koffsets = (const_as_ptr<int32_t>)offsets;
     const const_as_ptr<int32_t> kkinds = (const_as_ptr<int32_t>)kinds;
     const const_as_ptr<double> kpoints = (const_as_ptr<double>)points;
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(kCoverageBlock) void coverage_lookup_kernel(
         const int32_t nb = n + 2;
         const int32_t nl = nb < lds_bins ? nb : lds_bins;
         unsigned long long* __restrict__ cnt = counts + (int64_t)(e0 - base0) + 2 * (int64_t)t;
-        for (int b = threadIdx.x; b < nl; b += blockDim.x) hist[b] = 0u;
+        hist_clear(hist, nl, blockDim.x);
         __syncthreads();
         bool searching = live && !local;
         int32_t found = local ? n : n + 1;
@@ -60,16 +61,10 @@ __global__ __launch_bounds__(kCoverageBlock) void coverage_lookup_kernel(
         }
         if (live) {
             if (entry_out) entry_out[(int64_t)t * M + i] = found;
-            if (found < nl)
-                atomicAdd(&hist[found], 1u);
-            else
-                atomicAdd(&cnt[found], 1ull);
+            hist_count(hist, nl, cnt, found);
         }
         __syncthreads();
-        for (int b = threadIdx.x; b < nl; b += blockDim.x) {
-            const unsigned int v = hist[b];
-            if (v) atomicAdd(&cnt[b], (unsigned long long)v);
-        }
+        hist_fold(hist, nl, blockDim.x, [&](int b) { return &cnt[b]; });
         __syncthreads();  // the next table clears the histogram
     }
 }
@@ -102,7 +97,7 @@ __global__ __launch_bounds__(kCoverageBlock) void family_lookup_kernel(
     const bool live = i < M;
     double pt[2][4], sm[2][kSpanPatterns];
     const bool local = coverage_target(U, i, live, pt, sm);
-    const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
+    const double t1 = point_tol(tol);
     const const_as_ptr<int32_t> koffsets = (const_as_ptr<int32_t>)offsets;
     const const_as_ptr<int32_t> kkinds = (const_as_ptr<int32_t>)kinds;
     const const_as_ptr<double> kpoints = (const_as_ptr<double>)points;
@@ -112,7 +107,7 @@ __global__ __launch_bounds__(kCoverageBlock) void family_lookup_kernel(
     const const_as_ptr<int32_t> kodd = (const_as_ptr<int32_t>)child_odd;
     const int32_t E = koffsets[n_members], E0 = koffsets[1];
     const int32_t n_bins = E + 2 + E0 + 2;  // <= kFamilyMaxBins (host)
-    for (int b = threadIdx.x; b < n_bins; b += blockDim.x) hist[b] = 0u;
+    hist_clear(hist, n_bins, blockDim.x);
     __syncthreads();
     int32_t cur = (live && !local) ? 0 : -1;  // reference policy: the member the walk is at (-1: over)
     bool reachable = live && !local;            // member 0 contains the target (decided at m = 0)
@@ -161,10 +156,7 @@ __global__ __launch_bounds__(kCoverageBlock) void family_lookup_kernel(
         if (gates_out) gates_out[i] = local ? 0 : best_k;
     }
     __syncthreads();
-    for (int b = threadIdx.x; b < n_bins; b += blockDim.x) {
-        const unsigned int v = hist[b];
-        if (v) atomicAdd(b < E + 2 ? &counts[b] : &base_counts[b - (E + 2)], (unsigned long long)v);
-    }
+    hist_fold(hist, n_bins, blockDim.x, [&](int b) { return b < E + 2 ? &counts[b] : &base_counts[b - (E + 2)]; });
 }
 
 // ---- slam_pd.hpp --------------------------------------------------------------------------------------------------------------------
@@ -327,22 +319,11 @@ __global__ __launch_bounds__(kRegionBlock) void region_lookup_kernel(const doubl
     const bool live = i < M;
     double c[3] = {0.0, 0.0, 0.0}, pt[2][4], sm[2][kSpanPatterns];
     if (live) weyl_c1c2c3(U + i * 32, 8, c);
-#pragma unroll
-    for (int sh = 0; sh < 2; ++sh) {
-        double a[4];
-        alcove_point(c[0], c[1], c[2], sh ? 0.5 : 0.0, a);
-        const double g1 = a[3], g2 = a[2], g3 = a[1], g4 = a[0];  // the order of span_predict_kernel
-        const double s[kSpanPatterns] = {g1, g2, g3, g4, g1 + g2, g1 + g3, g1 + g4, g2 + g3, g2 + g4, g3 + g4,
-                                         g1 + g2 + g3, g1 + g2 + g4, g1 + g3 + g4, g2 + g3 + g4};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pt[sh][j] = a[j];
-#pragma unroll
-        for (int p = 0; p < kSpanPatterns; ++p) sm[sh][p] = s[p];
-    }
+    target_frame(c, pt, sm);  // (kind 0 reads c itself; a dead lane's frame is that of c = 0 and never counts)
     const int nb = 2 * n_regions + 1;
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) hist[b] = 0u;
+    hist_clear(hist, nb, blockDim.x);
     __syncthreads();
-    const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
+    const double t1 = point_tol(tol);
     const const_as_ptr<int32_t> kro = (const_as_ptr<int32_t>)region_offsets;
     const const_as_ptr<int32_t> kki = (const_as_ptr<int32_t>)kinds;
     const const_as_ptr<int32_t> kfo = (const_as_ptr<int32_t>)facet_offsets;
@@ -362,6 +343,8 @@ __global__ __launch_bounds__(kRegionBlock) void region_lookup_kernel(const doubl
                     ok = ok && (v <= tol);
                 }
             } else if (kind == 1) {
+                // row_bounds_hit / row_point_hit written out: called here they make the compiler reload the region's polytope range
+                // in every pass of the loop, and the lookup ran 1-2 % slower (profiles/geometry_frame_ab.txt)
                 const const_as_ptr<double> bd = ka + (int64_t)p * kSpanPatterns;
                 bool ok0 = true, ok1 = true;
 #pragma unroll
@@ -389,10 +372,7 @@ __global__ __launch_bounds__(kRegionBlock) void region_lookup_kernel(const doubl
     }
     if (live) atomicAdd(&hist[n_regions + first], 1u);
     __syncthreads();
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) {
-        const unsigned int v = hist[b];
-        if (v) atomicAdd(&counts[b], (unsigned long long)v);
-    }
+    hist_fold(hist, nb, blockDim.x, [&](int b) { return &counts[b]; });
 }
 
 // ---- slam_kak.hpp -------------------------------------------------------------------------------------------------------------------

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(kSelBlock) void haar_span_select_kernel(SpanRegions
                                                                      uint32_t* __restrict__ totals, unsigned long long* __restrict__ counts) {
     __shared__ unsigned int hist[kSelBins];
     __shared__ unsigned int wave_votes[kSelWaves];
-    if (threadIdx.x < kSelBins) hist[threadIdx.x] = 0u;
+    hist_clear(hist, kSelBins, kSelBlock);
     __syncthreads();
     const int64_t t = (int64_t)blockIdx.x * kSelBlock + threadIdx.x;
     bool vote = false;
@@ -54,10 +54,13 @@ __global__ __launch_bounds__(kSelBlock) void haar_span_select_kernel(SpanRegions
         for (int e = 0; e < 32; ++e) asm volatile("" : "+v"(U[e]));
         double c[3];
         weyl_c1c2c3(U, 8, c);
-        const int span = span_classify(c, r, r.tol);
+        double pt[2][4], sm[2][kSpanPatterns];
+        const bool local = target_frame(c, pt, sm);  // one frame for the three classifications: it does not depend on the tolerance
+        const int span = span_classify(local, pt, sm, r, r.tol);
         atomicAdd(&hist[span], 1u);
         vote = span >= a.span_lo && span <= a.span_hi;
-        if (vote && a.margin > 0.0) vote = span_classify(c, r, r.tol + a.margin) == span && span_classify(c, r, r.tol - a.margin) == span;
+        if (vote && a.margin > 0.0)
+            vote = span_classify(local, pt, sm, r, r.tol + a.margin) == span && span_classify(local, pt, sm, r, r.tol - a.margin) == span;
     }
     const unsigned long long m = __ballot(vote);
     const int w = threadIdx.x >> 6;
@@ -72,10 +75,7 @@ __global__ __launch_bounds__(kSelBlock) void haar_span_select_kernel(SpanRegions
         for (int j = 0; j < kSelWaves; ++j) s += wave_votes[j];
         totals[blockIdx.x] = s;
     }
-    if (threadIdx.x < kSelBins) {
-        const unsigned int v = hist[threadIdx.x];
-        if (v) atomicAdd(&counts[threadIdx.x], (unsigned long long)v);
-    }
+    hist_fold(hist, kSelBins, kSelBlock, [&](int b) { return &counts[b]; });
 }
 
 // one block: offsets[b] = totals[0] + .. + totals[b - 1], *n_selected = the sum of all (at most 2^31 - 1 candidates: 32 bits hold it)

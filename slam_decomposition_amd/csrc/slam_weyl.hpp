@@ -189,29 +189,63 @@ __device__ inline void alcove_point(double c1, double c2, double c3, double shif
     for (int j = 0; j < 4; ++j) a[j] = e[j + s];
 }
 
-// template size of the class with Weyl coordinates c (weyl_c1c2c3, 8 digits) for the regions r widened by tol: 0 local, 1 .. k_max,
-// k_max + 1 out of reach.  The one classifier: span_predict_kernel and haar_span_select_kernel (slam_span_sampler.hpp) both ask here.
-__device__ __forceinline__ int span_classify(const double (&c)[3], const SpanRegions& r, double tol) {
-    int best = r.k_max + 1;
+// The target's side of every row, from its Weyl coordinates c (weyl_c1c2c3, 8 digits): both alcove points of the class (shift 0 and
+// 1/2) and, per point, the sums over the 14 subsets K (coverage._PATTERNS order): gamma_{5 - k}, k in K -> zero-based a[4 - k], added
+// left to right as on the host.  Returns whether the class is local.  The one frame: every lookup kernel of the unit asks here.
+__device__ __forceinline__ bool target_frame(const double (&c)[3], double (&pt)[2][4], double (&sm)[2][kSpanPatterns]) {
     bool local = false;
+#pragma unroll
     for (int sh = 0; sh < 2; ++sh) {
         double a[4];
         alcove_point(c[0], c[1], c[2], sh ? 0.5 : 0.0, a);
         local = local || (fabs(a[0]) <= 1e-8 && fabs(a[3]) <= 1e-8);
-        // sums over the subsets K (coverage._PATTERNS order): gamma_{5 - k}, k in K  ->  zero-based a[4 - k]
         const double g1 = a[3], g2 = a[2], g3 = a[1], g4 = a[0];  // g_k = gamma_{5 - k}
-        const double sums[kSpanPatterns] = {g1, g2, g3, g4, g1 + g2, g1 + g3, g1 + g4, g2 + g3, g2 + g4, g3 + g4,
-                                            g1 + g2 + g3, g1 + g2 + g4, g1 + g3 + g4, g2 + g3 + g4};
-        const double t1 = (tol > 0.0 ? tol : 0.0) + 1e-12;
-        if (fabs(a[0] - r.point[0]) <= t1 && fabs(a[1] - r.point[1]) <= t1 && fabs(a[2] - r.point[2]) <= t1 && fabs(a[3] - r.point[3]) <= t1)
-            best = 1;
-        for (int k = 2; k <= r.k_max && k < best; ++k) {
-            bool ok = true;
-            for (int p = 0; p < kSpanPatterns; ++p) ok = ok && (sums[p] >= r.bounds[k - 1][p] - tol);
-            if (ok) best = k;
-        }
+        const double s[kSpanPatterns] = {g1, g2, g3, g4, g1 + g2, g1 + g3, g1 + g4, g2 + g3, g2 + g4, g3 + g4,
+                                         g1 + g2 + g3, g1 + g2 + g4, g1 + g3 + g4, g2 + g3 + g4};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pt[sh][j] = a[j];
+#pragma unroll
+        for (int p = 0; p < kSpanPatterns; ++p) sm[sh][p] = s[p];
     }
-    return local ? 0 : best;
+    return local;
+}
+
+// The two row tests and their tolerance.  A row is whatever q[j] / r[p] reads: a const_as_ptr<double> at a wave-uniform address (the
+// row arrives by scalar loads and sits in SGPRs) or an array of the by-value SpanRegions in the kernel's arguments.
+// one gate: the target's class is the gate's -- |a_j - q_j| <= t1 = point_tol(tol) for one of the two alcove points
+__device__ __forceinline__ double point_tol(double tol) { return (tol > 0.0 ? tol : 0.0) + 1e-12; }
+template <class Row>
+__device__ __forceinline__ bool row_point_hit(const double (&pt)[2][4], Row q, double t1) {
+    const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    bool hit = false;
+#pragma unroll
+    for (int sh = 0; sh < 2; ++sh)
+        hit = hit || (fabs(pt[sh][0] - q0) <= t1 && fabs(pt[sh][1] - q1) <= t1 && fabs(pt[sh][2] - q2) <= t1 && fabs(pt[sh][3] - q3) <= t1);
+    return hit;
+}
+// two or more gates: r[p] - tol <= sum_p(gamma) for all 14 subsets, for one of the two alcove points (-inf stays -inf: no constraint)
+template <class Row>
+__device__ __forceinline__ bool row_bounds_hit(const double (&sm)[2][kSpanPatterns], Row r, double tol) {
+    bool ok0 = true, ok1 = true;
+#pragma unroll
+    for (int p = 0; p < kSpanPatterns; ++p) {
+        const double lo = r[p] - tol;
+        ok0 = ok0 && (sm[0][p] >= lo);
+        ok1 = ok1 && (sm[1][p] >= lo);
+    }
+    return ok0 || ok1;
+}
+
+// template size of the class with the frame (local, pt, sm) for the regions r widened by tol: 0 local, the first k in 1 .. k_max for
+// which either alcove point is inside, k_max + 1 out of reach.  The one classifier: span_predict_kernel and haar_span_select_kernel
+// (slam_span_sampler.hpp) both ask here; the frame does not depend on tol.
+__device__ __forceinline__ int span_classify(bool local, const double (&pt)[2][4], const double (&sm)[2][kSpanPatterns], const SpanRegions& r,
+                                             double tol) {
+    if (local) return 0;
+    if (row_point_hit(pt, r.point, point_tol(tol))) return 1;
+    for (int k = 2; k <= r.k_max; ++k)
+        if (row_bounds_hit(sm, r.bounds[k - 1], tol)) return k;
+    return r.k_max + 1;
 }
 
 // ---------------------------------------------------------------------------------
@@ -232,62 +266,51 @@ __device__ __forceinline__ int span_classify(const double (&c)[3], const SpanReg
 template <class T>
 using const_as_ptr = const __attribute__((address_space(4))) T*;
 
-// the target's side of every row, once per target: Weyl coordinates (8 digits), both alcove points of its class and their 14 subset
-// sums; returns whether the class is local.  Lanes beyond the batch get zeros (they never count).
+// the frame of target i, once per target for all rows; lanes beyond the batch get zeros (they never count)
 __device__ __forceinline__ bool coverage_target(const double* __restrict__ U, int64_t i, bool live, double (&pt)[2][4],
                                                 double (&sm)[2][kSpanPatterns]) {
-    bool local = false;
     if (live) {
         double c[3];
         weyl_c1c2c3(U + i * 32, 8, c);
-#pragma unroll
-        for (int sh = 0; sh < 2; ++sh) {
-            double a[4];
-            alcove_point(c[0], c[1], c[2], sh ? 0.5 : 0.0, a);
-            local = local || (fabs(a[0]) <= 1e-8 && fabs(a[3]) <= 1e-8);
-            const double g1 = a[3], g2 = a[2], g3 = a[1], g4 = a[0];  // same order as span_predict_kernel
-            const double s[kSpanPatterns] = {g1, g2, g3, g4, g1 + g2, g1 + g3, g1 + g4, g2 + g3, g2 + g4, g3 + g4,
-                                             g1 + g2 + g3, g1 + g2 + g4, g1 + g3 + g4, g2 + g3 + g4};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pt[sh][j] = a[j];
-#pragma unroll
-            for (int p = 0; p < kSpanPatterns; ++p) sm[sh][p] = s[p];
-        }
-    } else {
-#pragma unroll
-        for (int sh = 0; sh < 2; ++sh) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pt[sh][j] = 0.0;
-#pragma unroll
-            for (int p = 0; p < kSpanPatterns; ++p) sm[sh][p] = 0.0;
-        }
+        return target_frame(c, pt, sm);
     }
-    return local;
+#pragma unroll
+    for (int sh = 0; sh < 2; ++sh) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pt[sh][j] = 0.0;
+#pragma unroll
+        for (int p = 0; p < kSpanPatterns; ++p) sm[sh][p] = 0.0;
+    }
+    return false;
 }
 
 // does row e contain the target?  e is wave-uniform, so the row arrives by scalar loads and sits in SGPRs
 __device__ __forceinline__ bool coverage_row_hit(const_as_ptr<int32_t> kkinds, const_as_ptr<double> kpoints, const_as_ptr<double> kbounds,
                                                  int32_t e, const double (&pt)[2][4], const double (&sm)[2][kSpanPatterns], double tol,
                                                  double t1) {
-    if (kkinds[e] == 0) {
-        const const_as_ptr<double> q = kpoints + (int64_t)e * 4;
-        const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-        bool hit = false;
-#pragma unroll
-        for (int sh = 0; sh < 2; ++sh)
-            hit = hit || (fabs(pt[sh][0] - q0) <= t1 && fabs(pt[sh][1] - q1) <= t1 && fabs(pt[sh][2] - q2) <= t1 &&
-                          fabs(pt[sh][3] - q3) <= t1);
-        return hit;
+    return kkinds[e] == 0 ? row_point_hit(pt, kpoints + (int64_t)e * 4, t1) : row_bounds_hit(sm, kbounds + (int64_t)e * kSpanPatterns, tol);
+}
+
+// A block's integer histogram in LDS: every thread helps to clear it, the counts are LDS atomics, and the block folds its non-empty
+// bins into global memory with one 64-bit atomic each; dest(b) is the global counter of bin b.  The barriers between clear, count and
+// fold are the caller's.  `block` is the block's size: blockDim.x, or the constant the kernel is launched with.
+template <class Block>
+__device__ __forceinline__ void hist_clear(unsigned int* hist, int n_bins, Block block) {
+    for (int b = threadIdx.x; b < n_bins; b += block) hist[b] = 0u;
+}
+template <class Block, class Dest>
+__device__ __forceinline__ void hist_fold(const unsigned int* hist, int n_bins, Block block, Dest dest) {
+    for (int b = threadIdx.x; b < n_bins; b += block) {
+        const unsigned int v = hist[b];
+        if (v) atomicAdd(dest(b), (unsigned long long)v);
     }
-    const const_as_ptr<double> r = kbounds + (int64_t)e * kSpanPatterns;
-    bool ok0 = true, ok1 = true;
-#pragma unroll
-    for (int p = 0; p < kSpanPatterns; ++p) {
-        const double lo = r[p] - tol;
-        ok0 = ok0 && (sm[0][p] >= lo);
-        ok1 = ok1 && (sm[1][p] >= lo);
-    }
-    return ok0 || ok1;
+}
+// one count in bin b of a histogram whose first n_lds bins are in LDS: the others go straight to global memory
+__device__ __forceinline__ void hist_count(unsigned int* hist, int n_lds, unsigned long long* counts, int b) {
+    if (b < n_lds)
+        atomicAdd(&hist[b], 1u);
+    else
+        atomicAdd(&counts[b], 1ull);
 }
 
 }  // namespace slamdev
