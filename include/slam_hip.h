@@ -335,6 +335,31 @@ int slam_approx_counts(slam_ctx* ctx, int64_t first, int64_t count, int family, 
                        int64_t* counts_out, int64_t* fidsum_out);
 
 /*
+ * The same decomposition into gates G of ANY supercontrolled class CAN(1/2, beta, 0), 0 <= beta <= 1/2 (csrc/slam_sc.hpp): the line of
+ * the Weyl chamber through the CNOT (beta = 0), the B (1/4) and the iSWAP class (1/2), every full-strength conversion-gain gate
+ * included.  Three such gates reach every target (the construction of qiskit's TwoQubitBasisDecomposer); the t_k, F_k, E_k and the
+ * selection are those of slam_approx_decompose with the gate's own beta, t_2 = |cos c| and t_3 = 1 for every beta.  For
+ * 0 < beta < 1/2 two gates reach more than the plane c3 = 0, but this two-gate formula is exact on the plane only: a target off it
+ * gets three gates at f = 1 (at beta = 1/4 slam_b_decompose returns two for every target).
+ *   gate    double[32]            G, row-major (re, im)
+ *   dress   double[SLAM_SC_DRESS] the host's reduction of G as slam_b_decompose takes it: l1, l0, r1, r0, then c[3], with
+ *                                 G = e^{i .} (l1 (x) l0) CAN(c) (r1 (x) r0), c within 4e-8 of (1/2, beta, 0) once folded to c1 <= 1/2.
+ *                                 The constant matrices of the construction depend on beta alone; the library forms them itself and
+ *                                 folds l and r into them
+ *   basis_fidelity, force_cycles (-1, 0..3), x_out, cycles, loss, predicted, gap   as slam_approx_decompose
+ * Any output pointer may be NULL.  Arguments are checked before the context.  SLAM_ERR_INVALID for a gate off the line, a gate that
+ * the dress factors do not rebuild to 1e-12, a basis_fidelity outside (0, 1] or not finite, force_cycles out of range, a NULL
+ * context and a window outside the resident batch; nothing is written then.
+ */
+#define SLAM_SC_DRESS 35
+int slam_sc_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* gate, const double* dress, double basis_fidelity,
+                      int force_cycles, double* x_out, int32_t* cycles, double* loss, double* predicted, double* gap);
+
+/* The sweep of slam_approx_counts for such a gate: gate and dress as slam_sc_decompose, the rest as slam_approx_counts. */
+int slam_sc_counts(slam_ctx* ctx, int64_t first, int64_t count, const double* gate, const double* dress, int32_t n_fid,
+                   const double* fidelities, int64_t* counts_out, int64_t* fidsum_out);
+
+/*
  * Span predictor on the device: for every resident target of [first, first + count) the smallest number k of leading gates of a
  * template whose coverage set contains the target -- the lookup CircuitTemplate.get_spanning_range makes with use_polytopes=True
  * (src/slam/basis.py:95-100 -> monodromy_range_from_target, src/slam/utils/polytopes/polytope_wrap.py:39-94).  The coverage sets
@@ -870,7 +895,8 @@ const char* slam_version(void);
  *      later: slam_b_decompose (a new symbol only);
  *      later: slam_family_lookup (a new symbol only);
  *      later: slam_approx_decompose and slam_approx_counts (new symbols only);
- *      later: slam_candidate_scores (a new symbol only).
+ *      later: slam_candidate_scores (a new symbol only);
+ *      later: slam_sc_decompose and slam_sc_counts (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = (
     "slam_b_decompose",
     "slam_approx_decompose",
     "slam_approx_counts",
+    "slam_sc_decompose",
+    "slam_sc_counts",
     "slam_predict_spans",
     "slam_coverage_lookup",
     "slam_family_lookup",
@@ -251,6 +253,9 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "slam_approx_decompose"):
         lib.slam_approx_decompose.argtypes = [P, C.c_int64, C.c_int64, C.c_int, P, P, C.c_double, C.c_int, P, P, P, P, P]
         lib.slam_approx_counts.argtypes = [P, C.c_int64, C.c_int64, C.c_int, C.c_int32, P, P, P]
+    if hasattr(lib, "slam_sc_decompose"):
+        lib.slam_sc_decompose.argtypes = [P, C.c_int64, C.c_int64, P, P, C.c_double, C.c_int, P, P, P, P, P]
+        lib.slam_sc_counts.argtypes = [P, C.c_int64, C.c_int64, P, P, C.c_int32, P, P, P]
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
     if hasattr(lib, "slam_coverage_lookup"):
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
@@ -641,6 +646,32 @@ def approx_dress(gate):
     return cx_dress(gate)
 
 
+SC_DRESS = 35  # SLAM_SC_DRESS
+
+
+def sc_class(gate) -> float:
+    """beta of a 4x4 supercontrolled gate, one of the class CAN(1/2, beta, 0) with 0 <= beta <= 1/2 (the CNOT, B and iSWAP classes are
+    beta = 0, 1/4, 1/2), judged on the 8-digit Weyl coordinates with ``span_rules._TOL``; ``ValueError`` (naming the coordinates) for
+    any other gate."""
+    from . import span_rules, weyl
+
+    c = weyl.c1c2c3(np.asarray(gate, dtype=np.complex128))
+    f = span_rules._fold(c)[0]
+    if not (abs(f[0] - 0.5) < span_rules._TOL and abs(f[2]) < span_rules._TOL):
+        raise ValueError(f"the gate is not supercontrolled, of a class (0.5, beta, 0) (Weyl coordinates {tuple(float(v) for v in c)})")
+    return float(min(max(f[1], 0.0), 0.5))
+
+
+def sc_dress(gate):
+    """The host's reduction of a basis gate for slam_sc_decompose and slam_sc_counts (include/slam_hip.h): ``(gate [4, 4] complex128,
+    dress float64[SC_DRESS])`` from one ``weyl.kak`` call -- G = e^{i .} (l1 (x) l0) CAN(c) (r1 (x) r0)."""
+    g, _, (_, l1, l0, c, r1, r0) = _dress_head(gate, sc_class)
+    dress = np.concatenate([np.ascontiguousarray(np.stack([l1, l0, r1, r0]), dtype=np.complex128).view(np.float64).ravel(),
+                            np.asarray(c, dtype=np.float64)])
+    assert dress.shape == (SC_DRESS,)
+    return g, dress
+
+
 def check_basis_fidelity(f) -> float:
     """``f`` as a float in (0, 1]; ``ValueError`` otherwise."""
     f = float(f)
@@ -819,6 +850,36 @@ class Context:
         counts = np.zeros((len(f), 4), dtype=np.int64)
         fidsum = np.zeros(len(f), dtype=np.int64)
         _check(self._lib.slam_approx_counts(self._h, int(first), count, family, len(f), _ptr(f), _ptr(counts), _ptr(fidsum)))
+        return counts, fidsum
+
+    def sc_decompose(self, gate, basis_fidelity: float = 1.0, cycles: Optional[int] = None, first: int = 0, count: Optional[int] = None):
+        """``approx_decompose`` for ``gate`` of any supercontrolled class CAN(1/2, beta, 0) (slam_sc_decompose): the same five arrays,
+        sizes 0..3 for every beta.  ``ValueError`` for a gate off that line, a fidelity outside (0, 1] and a size outside 0..3."""
+        g, dress = sc_dress(gate)
+        f = check_basis_fidelity(basis_fidelity)
+        force = -1 if cycles is None else int(cycles)
+        if cycles is not None and not 0 <= force <= 3:
+            raise ValueError(f"cycles must be None or 0..3, got {cycles}")
+        predicted = np.zeros(max(self.n_targets - first if count is None else int(count), 0))
+
+        def fn(h, first, count, x, size, loss, gap):  # the four outputs of _closed_form_call, `predicted` between loss and gap
+            return self._lib.slam_sc_decompose(h, first, count, _ptr(g), _ptr(dress), f, force, x, size, loss, _ptr(predicted), gap)
+
+        x, size, loss, gap = self._closed_form_call(fn, (), first, count)
+        return x, size, loss, predicted, gap
+
+    def sc_counts(self, gate, basis_fidelities, first: int = 0, count: Optional[int] = None):
+        """``approx_counts`` for ``gate`` of any supercontrolled class (slam_sc_counts) -> ``(counts int64[n, 4], fidsum int64[n])``."""
+        g, dress = sc_dress(gate)
+        f = np.ascontiguousarray(basis_fidelities, dtype=np.float64).reshape(-1)
+        if not 1 <= len(f) <= APPROX_MAX_FID:
+            raise ValueError(f"between 1 and {APPROX_MAX_FID} basis fidelities per call, got {len(f)}")
+        for v in f:
+            check_basis_fidelity(v)
+        count = self.n_targets - first if count is None else int(count)
+        counts = np.zeros((len(f), 4), dtype=np.int64)
+        fidsum = np.zeros(len(f), dtype=np.int64)
+        _check(self._lib.slam_sc_counts(self._h, int(first), count, _ptr(g), _ptr(dress), len(f), _ptr(f), _ptr(counts), _ptr(fidsum)))
         return counts, fidsum
 
     def metric_update_check(self, h: np.ndarray, s: np.ndarray, w: np.ndarray, v: np.ndarray):

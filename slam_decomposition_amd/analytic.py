@@ -37,6 +37,12 @@ one with the highest expected fidelity F_k f^k (``slam_approx_decompose``, csrc/
     res.cycles, res.loss, res.predicted_loss, res.expected_fidelity
     sw = fidelity_sweep(DeviceHaarBatch(seed=7, n_samples=1 << 22), CXGate(), np.linspace(0.9, 1.0, 16))
     sw.counts, sw.average_gates, sw.average_fidelity
+
+The three classes are three points of one line of the Weyl chamber, the supercontrolled gates CAN(1/2, beta, 0), on which every
+full-strength conversion-gain gate lies.  ``sc_decompose`` is ``approx_decompose`` for any gate of that line (``slam_sc_decompose``,
+csrc/slam_sc.hpp); ``decompose``, ``approx_decompose`` and ``fidelity_sweep`` go there for the gates between the three points:
+
+    res = sc_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20), ConversionGainGate(0, 0, 0.4 * np.pi, 0.1 * np.pi, 1), basis_fidelity=0.99)
 """
 from __future__ import annotations
 
@@ -173,19 +179,55 @@ def b_decompose(targets, basis_gate=None, device: int = 0, success_threshold: fl
     return _gate_decompose(targets, BerkeleyGate() if basis_gate is None else basis_gate, _ffi.b_class, "b_decompose", device, success_threshold)
 
 
+_SC_FAMILY = -1  # what ``_approx_gate`` returns for a supercontrolled gate outside the three named classes
+
+
 def _approx_gate(basis_gate):
-    """``(matrix, family)`` of a gate that ``_ffi.approx_family`` accepts; ``NotImplementedError`` naming its coordinates otherwise."""
+    """``(matrix, family)`` of a gate that ``_ffi.approx_family`` accepts, ``(matrix, _SC_FAMILY)`` of any other supercontrolled gate
+    (``_ffi.sc_class``); ``NotImplementedError`` naming its coordinates otherwise."""
     from . import _ffi, weyl
 
     g = gate_matrix(basis_gate)
     try:
-        family = _ffi.approx_family(g)
+        return g, _ffi.approx_family(g)
+    except ValueError:
+        pass
+    try:
+        _ffi.sc_class(g)
     except ValueError:
         raise NotImplementedError(
             "approximate closed-form decompositions exist for basis gates of the CNOT class (0.5, 0, 0), the iSWAP class (0.5, 0.5, 0) "
-            f"and the B class (0.5, 0.25, 0) only (got {basis_gate} with Weyl coordinates {tuple(float(v) for v in weyl.c1c2c3(g))}); "
+            "and the B class (0.5, 0.25, 0), and of every other supercontrolled class (0.5, beta, 0), "
+            f"only (got {basis_gate} with Weyl coordinates {tuple(float(v) for v in weyl.c1c2c3(g))}); "
             "no closed form for the nearest two-gate point of sqrt(iSWAP) is established here") from None
-    return g, family
+    return g, _SC_FAMILY
+
+
+def sc_decompose(targets, basis_gate, basis_fidelity: float = 1.0, cycles=None, device: int = 0,
+                 success_threshold: float = 1e-10) -> ApproxDecomposition:
+    """``approx_decompose`` for ANY supercontrolled ``basis_gate``, one of a class CAN(1/2, beta, 0) with 0 <= beta <= 1/2 -- the line
+    of the Weyl chamber through the CNOT, the B and the iSWAP class, on which every full-strength conversion-gain gate
+    (``ConversionGainGate(0, 0, gc, gg, 1)`` with gc + gg = pi/2) lies, dressed with local gates or not: per target the circuit of 0,
+    1, 2 or 3 gates with the highest expected fidelity F_k * basis_fidelity^k (``slam_sc_decompose``, csrc/slam_sc.hpp; the
+    construction of qiskit's ``TwoQubitBasisDecomposer``, exact with three gates for every target).  One known limit, shared with
+    that decomposer: for 0 < beta < 1/2 two gates reach more than the plane c3 = 0, but the two-gate formula is exact on that plane
+    only, so at ``basis_fidelity=1`` a target off it gets three gates even where an optimiser finds two; at beta = 1/4 this returns
+    three where ``b_decompose`` returns two.  ``targets`` and ``cycles`` as for ``approx_decompose``.  ``ValueError`` for a gate off the
+    line (before any context is made), a fidelity outside (0, 1] and a size outside 0..3."""
+    from . import _ffi
+
+    g = gate_matrix(basis_gate)
+    _ffi.sc_class(g)
+    f = _ffi.check_basis_fidelity(basis_fidelity)
+    if cycles is not None and not (isinstance(cycles, (int, np.integer)) and 0 <= cycles <= 3):
+        raise ValueError(f"cycles must be None or an integer in 0..3 for {basis_gate}, got {cycles!r}")
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
+    if n == 0:
+        return _empty(ApproxDecomposition, success_threshold, basis_gate, np.zeros(0), np.zeros(0), f)
+    x, size, loss, predicted, gap = ctx.sc_decompose(g, f, cycles, 0, n)
+    expected = (4.0 + 16.0 * (1.0 - loss) ** 2) / 20.0 * f ** size
+    return ApproxDecomposition(size, x, loss, gap, success_threshold, basis_gate, predicted, expected, f)
 
 
 def approx_decompose(targets, basis_gate=None, basis_fidelity: float = 1.0, cycles=None, device: int = 0,
@@ -194,12 +236,15 @@ def approx_decompose(targets, basis_gate=None, basis_fidelity: float = 1.0, cycl
     class, which has no 3) with the highest expected fidelity F_k * basis_fidelity^k, F_k the average gate fidelity of the best circuit
     of k gates -- what qiskit's ``TwoQubitBasisDecomposer(gate, basis_fidelity)`` chooses; ties go to fewer gates, so
     ``basis_fidelity=1`` gives the fewest gates that equal the target and no gate for a local one.  ``cycles=k`` takes that size for
-    every target.  ``targets`` are given as for ``sqiswap_decompose``.  ``NotImplementedError`` for ``RiSwapGate(1/2)`` and every other
-    gate outside the three classes, ``ValueError`` for a fidelity outside (0, 1] and a size the gate's class does not have."""
+    every target.  ``targets`` are given as for ``sqiswap_decompose``.  A supercontrolled gate outside the three classes goes to
+    ``sc_decompose``.  ``NotImplementedError`` for ``RiSwapGate(1/2)`` and every other gate that is not supercontrolled, ``ValueError``
+    for a fidelity outside (0, 1] and a size the gate's class does not have."""
     from . import _ffi
 
     basis_gate = CXGate() if basis_gate is None else basis_gate
     g, family = _approx_gate(basis_gate)
+    if family == _SC_FAMILY:
+        return sc_decompose(targets, basis_gate, basis_fidelity, cycles, device, success_threshold)
     f = _ffi.check_basis_fidelity(basis_fidelity)
     k_max = 2 if family == _ffi.FAMILY_B else 3
     if cycles is not None and not (isinstance(cycles, (int, np.integer)) and 0 <= cycles <= k_max):
@@ -220,7 +265,7 @@ def fidelity_sweep(targets, basis_gate, basis_fidelities, device: int = 0) -> Fi
     depend on the order of addition).  Refusals as ``approx_decompose``."""
     from . import _ffi
 
-    g, _ = _approx_gate(basis_gate)
+    g, family = _approx_gate(basis_gate)
     f = np.ascontiguousarray(basis_fidelities, dtype=np.float64).reshape(-1)
     if not 1 <= len(f) <= _ffi.APPROX_MAX_FID:
         raise ValueError(f"between 1 and {_ffi.APPROX_MAX_FID} basis fidelities per call, got {len(f)}")
@@ -230,15 +275,16 @@ def fidelity_sweep(targets, basis_gate, basis_fidelities, device: int = 0) -> Fi
     n = _resident(ctx, targets)
     if n == 0:
         return FidelitySweep(f, np.zeros((len(f), 4), dtype=np.int64), np.full(len(f), np.nan), np.full(len(f), np.nan), 0, basis_gate)
-    counts, fidsum = ctx.approx_counts(g, f, 0, n)
+    counts, fidsum = (ctx.sc_counts if family == _SC_FAMILY else ctx.approx_counts)(g, f, 0, n)
     return FidelitySweep(f, counts, counts @ np.arange(4.0) / n, fidsum / 4294967296.0 / n, n, basis_gate)
 
 
 def decompose(targets, basis_gate, device: int = 0, success_threshold: float = 1e-10) -> SqiswapDecomposition:
     """The closed-form decomposition that exists for ``basis_gate``, chosen as the reference's pass chooses it: ``RiSwapGate(1/2)`` (any
     gate whose matrix is that gate's) goes to ``sqiswap_decompose``, a gate of the CNOT class or of the iSWAP class to
-    ``cx_decompose``; ``NotImplementedError`` naming the gate's Weyl coordinates for anything else -- a gate of the B class included,
-    which ``b_decompose`` takes when it is called by name."""
+    ``cx_decompose``, any other supercontrolled gate CAN(1/2, beta, 0) -- the reference's ``TwoQubitBasisDecomposer`` branch again --
+    to ``sc_decompose`` with a perfect gate; ``NotImplementedError`` naming the gate's Weyl coordinates for anything else -- a gate of
+    the B class included, which ``b_decompose`` takes when it is called by name."""
     from . import _ffi, weyl
     from .gates import RiSwapGate
 
@@ -248,8 +294,15 @@ def decompose(targets, basis_gate, device: int = 0, success_threshold: float = 1
     try:
         _ffi.cx_family(g)
     except ValueError:
+        try:
+            family = _approx_gate(basis_gate)[1]  # the B class has a family of its own and keeps its refusal
+        except NotImplementedError:
+            family = None
+        if family == _SC_FAMILY:
+            return sc_decompose(targets, basis_gate, 1.0, None, device, success_threshold)
         raise NotImplementedError(
             "closed-form decompositions exist for RiSwapGate(1/2) and for basis gates of the CNOT class (0.5, 0, 0) and of the iSWAP "
-            f"class (0.5, 0.5, 0) only (got {basis_gate} with Weyl coordinates {tuple(float(v) for v in weyl.c1c2c3(g))}); a gate of "
+            "class (0.5, 0.5, 0), and of every other supercontrolled class (0.5, beta, 0), "
+            f"only (got {basis_gate} with Weyl coordinates {tuple(float(v) for v in weyl.c1c2c3(g))}); a gate of "
             "the B class (0.5, 0.25, 0) is not dispatched here: call b_decompose") from None
     return cx_decompose(targets, basis_gate, device, success_threshold)

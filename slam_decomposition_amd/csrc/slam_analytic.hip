@@ -1,6 +1,7 @@
 // slam_analytic.hip -- host side of libslamhip.so, analytic unit: the closed-form decompositions into sqrt(iSWAP) gates
 // (slam_analytic.hpp), into gates of the CNOT or the iSWAP class (slam_cx.hpp) and into gates of the B class (slam_b.hpp), and the
-// fidelity-aware approximate decomposition into gates of those three classes (slam_approx.hpp).
+// fidelity-aware approximate decomposition into gates of those three classes (slam_approx.hpp) and of any supercontrolled class
+// (slam_sc.hpp).
 #include "slam_host.hpp"
 
 #include <complex>
@@ -10,6 +11,7 @@
 #include "slam_cx.hpp"
 #include "slam_b.hpp"
 #include "slam_approx.hpp"
+#include "slam_sc.hpp"
 
 // ---- slam_cx_decompose, slam_b_decompose: the host's share (plain C++) -------------------------------------------------------------------
 namespace {
@@ -171,6 +173,43 @@ int b_fold_dress(const double* gate, const double* dress, double* table) {
     return SLAM_OK;
 }
 
+// Checks gate against dress and folds dress into the kernel's table (slam_sc.hpp); *beta_p = pi beta / 2 of the gate's class
+// (1/2, beta, 0).  dress: the four 2x2 factors l1, l0, r1, r0 (row-major re, im), then the gate's KAK coordinates c[3].  The constant
+// matrices of the construction depend on beta alone and are formed here, so a dress cannot carry wrong ones.
+int sc_fold_dress(const double* gate, const double* dress, double* table, double* beta_p) {
+    M2 f[4];
+    const double beta = std::fmin(std::fabs(dress[33]), 0.5);  // a NaN, or anything beyond 1/2, fails the head's check
+    const double own[3] = {0.5, beta, 0.0};
+    const int rc = fold_dress_head(4, own, "a supercontrolled class (0.5, beta, 0), 0 <= beta <= 0.5", gate, dress, f);
+    if (rc) return rc;
+    const double bp = 1.57079632679489661923 * beta, h = 0.70710678118654752440;
+    const cd i1(0.0, 1.0), em = std::polar(1.0, -bp), ep = std::polar(1.0, bp), Em = std::polar(1.0, -2.0 * bp), Ep = std::polar(1.0, 2.0 * bp);
+    const cd p = 1.0 / cd(1.0, 1.0), m = 1.0 / cd(1.0, -1.0);
+    const M2 one = {{{1.0, 0.0}, {0.0, 1.0}}};
+    const M2 K11l = {{{-p * i1 * em, p * em}, {-p * i1 * ep, -p * ep}}}, K11r = {{{h * i1 * em, -h * em}, {h * ep, -h * i1 * ep}}};
+    const M2 K3221l = {{{h * (1.0 + i1 * std::cos(2.0 * bp)), h * i1 * std::sin(2.0 * bp)},
+                        {h * i1 * std::sin(2.0 * bp), h * (1.0 - i1 * std::cos(2.0 * bp))}}};
+    const M2 K21r = {{{-m * i1 * Em, m * Em}, {m * i1 * Ep, m * Ep}}}, K32r = {{{m * ep, -m * em}, {-m * i1 * ep, -m * i1 * em}}};
+    const M2 K22l = {{{h, -h}, {h, h}}}, K22r = {{{0.0, 1.0}, {-1.0, 0.0}}}, ipz = {{{i1, 0.0}, {0.0, -i1}}};
+    for (int j = 0; j < 32; ++j) table[j] = gate[j];
+    // an interior factor L rz(t) R of the S-circuit is (r^+ L) rz(t) (R l^+) in the G-circuit; entry order as slam_sc.hpp lists it
+    const M2 l1d = dag(f[0]), l0d = dag(f[1]), r1d = dag(f[2]), r0d = dag(f[3]);
+    const M2 L[kScEntries] = {mul(r0d, mul(ipz, dag(K11r))), mul(r1d, dag(K11l)), mul(r0d, K22r), mul(r1d, K22l), mul(r0d, K32r),
+                              mul(r1d, mul(K3221l, l1d))};
+    const M2 R[kScEntries] = {mul(K11r, l0d), mul(K11l, l1d), mul(K11r, l0d), mul(K11l, l1d), mul(K21r, l0d), one};
+    for (int j = 0; j < kScEntries; ++j)
+        for (int r = 0; r < 2; ++r)
+            for (int k = 0; k < 2; ++k) {
+                double* e = table + 32 + 16 * j + 2 * (2 * r + k);
+                e[0] = L[j].m[r][k].real();
+                e[1] = L[j].m[r][k].imag();
+                e[8] = R[j].m[r][k].real();
+                e[9] = R[j].m[r][k].imag();
+            }
+    *beta_p = bp;
+    return SLAM_OK;
+}
+
 // an argument block with a third double per target, `predicted` (slam_approx.hpp)
 template <class Args, class = void>
 struct has_predicted : std::false_type {};
@@ -227,6 +266,45 @@ int approx_table(int family, const double* gate, const double* dress, double* ta
     return family == 2 ? b_fold_dress(gate, dress, table) : cx_fold_dress(family, gate, dress, table);
 }
 
+// What the two sweeps do once the gate is known: the fidelities and the window are checked, the outputs cleared, the fidelities
+// uploaded, the histogram zeroed, the launch and the two optional read-backs.  `own` fills what only this kernel's block has.
+template <class Args, class Own>
+int run_counts(slam_ctx* ctx, int64_t first, int64_t count, void (*kernel)(Args), Own own, int32_t n_fid, const double* fidelities,
+               int64_t* counts_out, int64_t* fidsum_out) {
+    if (n_fid < 1 || n_fid > kApproxMaxFid) return fail(SLAM_ERR_INVALID, "n_fid must be in 1..%d, got %d", kApproxMaxFid, n_fid);
+    if (!fidelities) return fail(SLAM_ERR_INVALID, "fidelities is NULL");
+    for (int32_t j = 0; j < n_fid; ++j)
+        if (!(fidelities[j] > 0.0 && fidelities[j] <= 1.0))
+            return fail(SLAM_ERR_INVALID, "fidelities[%d] must be in (0, 1], got %g", j, fidelities[j]);
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    if (first < 0 || count < 0 || first + count > ctx->n_targets)
+        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
+    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
+    if (counts_out) std::memset(counts_out, 0, (size_t)n_fid * 4 * sizeof(int64_t));
+    if (fidsum_out) std::memset(fidsum_out, 0, (size_t)n_fid * sizeof(int64_t));
+    if (count == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->ev_x.reserve((size_t)n_fid * sizeof(double)));
+    HIP_TRY(ctx->ev_loss.reserve((size_t)n_fid * 5 * sizeof(unsigned long long)));  // counts [n_fid][4], then sums [n_fid]
+    HIP_TRY(hipMemcpy(ctx->ev_x.p, fidelities, (size_t)n_fid * sizeof(double), hipMemcpyHostToDevice));  // the caller's array: done before the call goes on
+    HIP_TRY(hipMemsetAsync(ctx->ev_loss.p, 0, (size_t)n_fid * 5 * sizeof(unsigned long long), ctx->stream));
+    Args a{};
+    own(a);
+    a.targets = ctx->targets.as<double>() + first * 32;
+    a.fidelities = ctx->ev_x.as<double>();
+    a.M = count;
+    a.n_fid = n_fid;
+    a.counts = ctx->ev_loss.as<unsigned long long>();
+    a.fidsum = a.counts + (size_t)n_fid * 4;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((count + kApproxCountsBlock - 1) / kApproxCountsBlock)), dim3(kApproxCountsBlock), 0,
+                       ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_fid * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (fidsum_out) HIP_TRY(hipMemcpyAsync(fidsum_out, a.fidsum, (size_t)n_fid * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,38 +359,34 @@ int slam_approx_counts(slam_ctx* ctx, int64_t first, int64_t count, int family, 
                        int64_t* counts_out, int64_t* fidsum_out) {
     if (family < 0 || family > 2)
         return fail(SLAM_ERR_INVALID, "family must be 0 (CNOT class), 1 (iSWAP class) or 2 (B class), got %d", family);
-    if (n_fid < 1 || n_fid > kApproxMaxFid) return fail(SLAM_ERR_INVALID, "n_fid must be in 1..%d, got %d", kApproxMaxFid, n_fid);
-    if (!fidelities) return fail(SLAM_ERR_INVALID, "fidelities is NULL");
-    for (int32_t j = 0; j < n_fid; ++j)
-        if (!(fidelities[j] > 0.0 && fidelities[j] <= 1.0))
-            return fail(SLAM_ERR_INVALID, "fidelities[%d] must be in (0, 1], got %g", j, fidelities[j]);
-    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
-    if (first < 0 || count < 0 || first + count > ctx->n_targets)
-        return fail(SLAM_ERR_INVALID, "target window outside the resident batch");
-    if (count > 0x7fffffffLL) return fail(SLAM_ERR_INVALID, "too many targets in one call (%lld)", (long long)count);
-    if (counts_out) std::memset(counts_out, 0, (size_t)n_fid * 4 * sizeof(int64_t));
-    if (fidsum_out) std::memset(fidsum_out, 0, (size_t)n_fid * sizeof(int64_t));
-    if (count == 0) return SLAM_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->ev_x.reserve((size_t)n_fid * sizeof(double)));
-    HIP_TRY(ctx->ev_loss.reserve((size_t)n_fid * 5 * sizeof(unsigned long long)));  // counts [n_fid][4], then sums [n_fid]
-    HIP_TRY(hipMemcpy(ctx->ev_x.p, fidelities, (size_t)n_fid * sizeof(double), hipMemcpyHostToDevice));  // the caller's array: done before the call goes on
-    HIP_TRY(hipMemsetAsync(ctx->ev_loss.p, 0, (size_t)n_fid * 5 * sizeof(unsigned long long), ctx->stream));
-    ApproxCountsArgs a{};
-    a.targets = ctx->targets.as<double>() + first * 32;
-    a.fidelities = ctx->ev_x.as<double>();
-    a.M = count;
-    a.family = family;
-    a.n_fid = n_fid;
-    a.counts = ctx->ev_loss.as<unsigned long long>();
-    a.fidsum = a.counts + (size_t)n_fid * 4;
-    hipLaunchKernelGGL(approx_counts_kernel, dim3((unsigned)((count + kApproxCountsBlock - 1) / kApproxCountsBlock)), dim3(kApproxCountsBlock),
-                       0, ctx->stream, a);
-    HIP_TRY(hipGetLastError());
-    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_fid * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (fidsum_out) HIP_TRY(hipMemcpyAsync(fidsum_out, a.fidsum, (size_t)n_fid * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SLAM_OK;
+    return run_counts(ctx, first, count, approx_counts_kernel, [family](ApproxCountsArgs& a) { a.family = family; }, n_fid, fidelities,
+                      counts_out, fidsum_out);
+}
+
+int slam_sc_decompose(slam_ctx* ctx, int64_t first, int64_t count, const double* gate, const double* dress, double basis_fidelity,
+                      int force_cycles, double* x_out, int32_t* cycles, double* loss, double* predicted, double* gap) {
+    if (!gate || !dress) return fail(SLAM_ERR_INVALID, "gate and dress are required");
+    double table[kScTable], bp = 0.0;
+    const int rc = sc_fold_dress(gate, dress, table, &bp);
+    if (rc) return rc;
+    if (!(basis_fidelity > 0.0 && basis_fidelity <= 1.0))  // a NaN fails both
+        return fail(SLAM_ERR_INVALID, "basis_fidelity must be in (0, 1], got %g", basis_fidelity);
+    if (force_cycles < -1 || force_cycles > 3)
+        return fail(SLAM_ERR_INVALID, "force_cycles must be -1 (select) or 0..3, got %d", force_cycles);
+    return run_closed_form(
+        ctx, first, count, sc_decompose_kernel, table, kScTable,
+        [=](ScArgs& a, const double* t) { a.table = t, a.beta_p = bp, a.force = force_cycles, a.fidelity = basis_fidelity; }, x_out, cycles,
+        loss, gap, predicted);
+}
+
+int slam_sc_counts(slam_ctx* ctx, int64_t first, int64_t count, const double* gate, const double* dress, int32_t n_fid,
+                   const double* fidelities, int64_t* counts_out, int64_t* fidsum_out) {
+    if (!gate || !dress) return fail(SLAM_ERR_INVALID, "gate and dress are required");
+    double table[kScTable], bp = 0.0;
+    const int rc = sc_fold_dress(gate, dress, table, &bp);
+    if (rc) return rc;
+    return run_counts(ctx, first, count, sc_counts_kernel, [bp](ScCountsArgs& a) { a.beta_p = bp; }, n_fid, fidelities, counts_out,
+                      fidsum_out);
 }
 
 }  // extern "C"

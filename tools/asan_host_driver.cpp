@@ -156,6 +156,50 @@ int main() {
         EXPECT(slam_approx_counts(nullptr, 0, 1, 2, 65, fid, &i64, &i64) == SLAM_ERR_INVALID);
         EXPECT(slam_approx_counts(nullptr, 0, 1, 3, 2, fid, &i64, &i64) == SLAM_ERR_INVALID);
     }
+    {  // slam_sc_decompose, slam_sc_counts: CAN(1/2, 0.3, 0) and its reduction as Context.sc_decompose computes it (_ffi.sc_dress)
+        const double c1 = 0.9510565162951535, s1 = 0.3090169943749474, c4 = 0.30901699437494745, s4 = 0.9510565162951535;
+        const double sc_gate[32] = {
+            c1, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, s1,
+            0.0, 0.0, c4, 0.0, 0.0, s4, 0.0, 0.0,
+            0.0, 0.0, 0.0, s4, c4, 0.0, 0.0, 0.0,
+            0.0, s1, 0.0, 0.0, 0.0, 0.0, c1, 0.0};
+        const double sc_dress[SLAM_SC_DRESS] = {
+            1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0,
+            1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0,
+            1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0,
+            1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0,
+            0.5, 0.3, 0.0};
+        const double fid[2] = {0.9, 1.0}, bad_fid[2] = {0.9, 1.5};
+        EXPECT(slam_sc_decompose(nullptr, 0, 1, sc_gate, sc_dress, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_sc_counts(nullptr, 0, 1, sc_gate, sc_dress, 2, fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_sc_decompose(nullptr, 0, 1, nullptr, sc_dress, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(slam_sc_counts(nullptr, 0, 1, sc_gate, nullptr, 2, fid, &i64, &i64) == SLAM_ERR_INVALID);
+        double bad[SLAM_SC_DRESS];
+        std::memcpy(bad, sc_dress, sizeof(bad));
+        bad[32] = 0.25;  // off the line
+        EXPECT(slam_sc_decompose(nullptr, 0, 1, sc_gate, bad, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "coordinates") != nullptr);
+        std::memcpy(bad, sc_dress, sizeof(bad));
+        bad[33] = 0.6;  // beyond the iSWAP end of the line
+        EXPECT(slam_sc_counts(nullptr, 0, 1, sc_gate, bad, 2, fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "coordinates") != nullptr);
+        bad[33] = 0.2;  // another gate of the line
+        EXPECT(slam_sc_decompose(nullptr, 0, 1, sc_gate, bad, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "rebuild the gate") != nullptr);
+        std::memcpy(bad, sc_dress, sizeof(bad));
+        bad[3] += 1e-9;  // one factor off: the gate is not rebuilt
+        EXPECT(slam_sc_decompose(nullptr, 0, 1, sc_gate, bad, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "rebuild the gate") != nullptr);
+        EXPECT(slam_sc_decompose(nullptr, 0, 1, sc_gate, sc_dress, 0.0, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "basis_fidelity") != nullptr);
+        EXPECT(slam_sc_decompose(nullptr, 0, 1, sc_gate, sc_dress, 0.99, 4, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "force_cycles") != nullptr);
+        EXPECT(slam_sc_counts(nullptr, 0, 1, sc_gate, sc_dress, 2, bad_fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "fidelities[1]") != nullptr);
+        EXPECT(slam_sc_counts(nullptr, 0, 1, sc_gate, sc_dress, 65, fid, &i64, &i64) == SLAM_ERR_INVALID);
+    }
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_family_lookup(nullptr, 0, 1, 1, i32, i32, d, d, i32, i32, d, 0.1, 1e-7, 0, &i64, &i64, i32, i32) == SLAM_ERR_INVALID);
