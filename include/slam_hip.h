@@ -360,6 +360,31 @@ int slam_sc_counts(slam_ctx* ctx, int64_t first, int64_t count, const double* ga
                    const double* fidelities, int64_t* counts_out, int64_t* fidsum_out);
 
 /*
+ * The same decomposition into gates S = sqrt(iSWAP) = RiSwapGate(1/2), the gate of slam_sqiswap_decompose, which is not supercontrolled
+ * (csrc/slam_sqapprox.hpp): per target the circuit of 0, 1, 2 or 3 S with the highest expected fidelity.  Coordinates in units of pi,
+ * folded to (x, y, z) = (c1, c2, c3), or (1 - c1, c2, -c3) where c1 > 1/2; w = |z|, s = sign(z);
+ * ov(d) = |Tr CAN(d)| / 4 = sqrt((cos d1' cos d2' cos d3')^2 + (sin d1' sin d2' sin d3')^2), d' = pi d / 2.  The best circuit of k
+ * gates reaches |Tr(T^+ W)| = 4 t_k:
+ *     t_0 = ov(x, y, z),     t_1 = ov(1/4 - x, 1/4 - y, z),     t_3 = 1,
+ *     t_2 = 1 inside the region w <= x - y that two S reach (tested as slam_sqiswap_decompose tests its size: on coordinates rounded to
+ *           8 digits, with 2e-8 of tolerance); outside it t_2 = ov(p - (x, y, z)) for the nearest point p of the region: with
+ *           u = (w - x + y) / 3, p = (x + u, y - u, s (w - u)), or, where x + u > 1/2, p = (1/2, y - r / 2, s (w - r / 2)) with
+ *           r = y + w - 1/2 (the ridge of the region at the fold c1 = 1/2).
+ * L_k, F_k, E_k and the selection are those of slam_approx_decompose.  With f = 1: no gate for a local target, one for a target of S's
+ * class, otherwise the size of slam_sqiswap_decompose.  Three gates are built as slam_sqiswap_decompose builds them.
+ *   basis_fidelity, force_cycles (-1, 0..3), x_out, cycles, loss, predicted, gap   as slam_approx_decompose (gap for three gates: the
+ *   gap of slam_sqiswap_decompose)
+ * Any output pointer may be NULL.  Arguments are checked before the context.  SLAM_ERR_INVALID for a basis_fidelity outside (0, 1] or
+ * not finite, force_cycles out of range, a NULL context and a window outside the resident batch; nothing is written then.
+ */
+int slam_sqiswap_approx_decompose(slam_ctx* ctx, int64_t first, int64_t count, double basis_fidelity, int force_cycles, double* x_out,
+                                  int32_t* cycles, double* loss, double* predicted, double* gap);
+
+/* The sweep of slam_approx_counts for sqrt(iSWAP): the selection of slam_sqiswap_approx_decompose, the rest as slam_approx_counts. */
+int slam_sqiswap_approx_counts(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_fid, const double* fidelities, int64_t* counts_out,
+                               int64_t* fidsum_out);
+
+/*
  * Span predictor on the device: for every resident target of [first, first + count) the smallest number k of leading gates of a
  * template whose coverage set contains the target -- the lookup CircuitTemplate.get_spanning_range makes with use_polytopes=True
  * (src/slam/basis.py:95-100 -> monodromy_range_from_target, src/slam/utils/polytopes/polytope_wrap.py:39-94).  The coverage sets
@@ -896,7 +921,8 @@ const char* slam_version(void);
  *      later: slam_family_lookup (a new symbol only);
  *      later: slam_approx_decompose and slam_approx_counts (new symbols only);
  *      later: slam_candidate_scores (a new symbol only);
- *      later: slam_sc_decompose and slam_sc_counts (new symbols only).
+ *      later: slam_sc_decompose and slam_sc_counts (new symbols only);
+ *      later: slam_sqiswap_approx_decompose and slam_sqiswap_approx_counts (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

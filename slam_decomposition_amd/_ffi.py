@@ -71,6 +71,8 @@ EXPORTED_SYMBOLS = (
     "slam_approx_counts",
     "slam_sc_decompose",
     "slam_sc_counts",
+    "slam_sqiswap_approx_decompose",
+    "slam_sqiswap_approx_counts",
     "slam_predict_spans",
     "slam_coverage_lookup",
     "slam_family_lookup",
@@ -256,6 +258,9 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "slam_sc_decompose"):
         lib.slam_sc_decompose.argtypes = [P, C.c_int64, C.c_int64, P, P, C.c_double, C.c_int, P, P, P, P, P]
         lib.slam_sc_counts.argtypes = [P, C.c_int64, C.c_int64, P, P, C.c_int32, P, P, P]
+    if hasattr(lib, "slam_sqiswap_approx_decompose"):
+        lib.slam_sqiswap_approx_decompose.argtypes = [P, C.c_int64, C.c_int64, C.c_double, C.c_int, P, P, P, P, P]
+        lib.slam_sqiswap_approx_counts.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P]
     lib.slam_predict_spans.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, C.c_double, P]
     if hasattr(lib, "slam_coverage_lookup"):
         lib.slam_coverage_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, C.c_double, P, P]
@@ -880,6 +885,35 @@ class Context:
         counts = np.zeros((len(f), 4), dtype=np.int64)
         fidsum = np.zeros(len(f), dtype=np.int64)
         _check(self._lib.slam_sc_counts(self._h, int(first), count, _ptr(g), _ptr(dress), len(f), _ptr(f), _ptr(counts), _ptr(fidsum)))
+        return counts, fidsum
+
+    def sqiswap_approx_decompose(self, basis_fidelity: float = 1.0, cycles: Optional[int] = None, first: int = 0, count: Optional[int] = None):
+        """``approx_decompose`` for sqrt(iSWAP) = ``RiSwapGate(1/2)`` (slam_sqiswap_approx_decompose; no gate is uploaded): the same five
+        arrays, sizes 0..3; with ``basis_fidelity=1`` no gate for a local target, one for a target of the gate's class and otherwise the
+        sizes of ``sqiswap_decompose``.  ``ValueError`` for a fidelity outside (0, 1] and a size outside 0..3."""
+        f = check_basis_fidelity(basis_fidelity)
+        force = -1 if cycles is None else int(cycles)
+        if cycles is not None and not 0 <= force <= 3:
+            raise ValueError(f"cycles must be None or 0..3, got {cycles}")
+        predicted = np.zeros(max(self.n_targets - first if count is None else int(count), 0))
+
+        def fn(h, first, count, x, size, loss, gap):  # the four outputs of _closed_form_call, `predicted` between loss and gap
+            return self._lib.slam_sqiswap_approx_decompose(h, first, count, f, force, x, size, loss, _ptr(predicted), gap)
+
+        x, size, loss, gap = self._closed_form_call(fn, (), first, count)
+        return x, size, loss, predicted, gap
+
+    def sqiswap_approx_counts(self, basis_fidelities, first: int = 0, count: Optional[int] = None):
+        """``approx_counts`` for sqrt(iSWAP) (slam_sqiswap_approx_counts) -> ``(counts int64[n, 4], fidsum int64[n])``."""
+        f = np.ascontiguousarray(basis_fidelities, dtype=np.float64).reshape(-1)
+        if not 1 <= len(f) <= APPROX_MAX_FID:
+            raise ValueError(f"between 1 and {APPROX_MAX_FID} basis fidelities per call, got {len(f)}")
+        for v in f:
+            check_basis_fidelity(v)
+        count = self.n_targets - first if count is None else int(count)
+        counts = np.zeros((len(f), 4), dtype=np.int64)
+        fidsum = np.zeros(len(f), dtype=np.int64)
+        _check(self._lib.slam_sqiswap_approx_counts(self._h, int(first), count, len(f), _ptr(f), _ptr(counts), _ptr(fidsum)))
         return counts, fidsum
 
     def metric_update_check(self, h: np.ndarray, s: np.ndarray, w: np.ndarray, v: np.ndarray):

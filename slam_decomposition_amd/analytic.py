@@ -43,6 +43,15 @@ full-strength conversion-gain gate lies.  ``sc_decompose`` is ``approx_decompose
 csrc/slam_sc.hpp); ``decompose``, ``approx_decompose`` and ``fidelity_sweep`` go there for the gates between the three points:
 
     res = sc_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20), ConversionGainGate(0, 0, 0.4 * np.pi, 0.1 * np.pi, 1), basis_fidelity=0.99)
+
+sqrt(iSWAP) is not on that line: two of it reach a solid region of the chamber, |z| <= x - y, and the nearest point of that region
+has a closed form of its own (csrc/slam_sqapprox.hpp).  ``sqiswap_approx_decompose`` and ``sqiswap_fidelity_sweep`` are the entry
+points for an imperfect ``RiSwapGate(1/2)`` -- 0, 1, 2 or 3 gates by expected fidelity, the sizes of ``sqiswap_decompose`` at f = 1
+except that a local target costs no gate and a target of the gate's class one; ``approx_decompose``, ``fidelity_sweep`` and
+``decompose`` do not dispatch to them yet:
+
+    res = sqiswap_approx_decompose(DeviceHaarBatch(seed=7, n_samples=1 << 20), basis_fidelity=0.99)
+    sw = sqiswap_fidelity_sweep(DeviceHaarBatch(seed=7, n_samples=1 << 22), np.linspace(0.9, 1.0, 16))
 """
 from __future__ import annotations
 
@@ -258,24 +267,74 @@ def approx_decompose(targets, basis_gate=None, basis_fidelity: float = 1.0, cycl
     return ApproxDecomposition(size, x, loss, gap, success_threshold, basis_gate, predicted, expected, f)
 
 
-def fidelity_sweep(targets, basis_gate, basis_fidelities, device: int = 0) -> FidelitySweep:
-    """The Haar-expected (or any distribution's) gate count and fidelity of ``basis_gate`` at each of ``basis_fidelities`` (at most
-    ``_ffi.APPROX_MAX_FID``), from one launch over ``targets`` (``slam_approx_counts``): the choice of ``approx_decompose`` per target
-    and fidelity, counted per size, and the mean of the chosen expected fidelities (summed in fixed point, 2^-32: the result does not
-    depend on the order of addition).  Refusals as ``approx_decompose``."""
+def _check_fidelities(basis_fidelities) -> np.ndarray:
+    """``basis_fidelities`` as a float64 vector of 1.. ``_ffi.APPROX_MAX_FID`` entries of (0, 1]; ``ValueError`` otherwise."""
     from . import _ffi
 
-    g, family = _approx_gate(basis_gate)
     f = np.ascontiguousarray(basis_fidelities, dtype=np.float64).reshape(-1)
     if not 1 <= len(f) <= _ffi.APPROX_MAX_FID:
         raise ValueError(f"between 1 and {_ffi.APPROX_MAX_FID} basis fidelities per call, got {len(f)}")
     for v in f:
         _ffi.check_basis_fidelity(v)
+    return f
+
+
+def fidelity_sweep(targets, basis_gate, basis_fidelities, device: int = 0) -> FidelitySweep:
+    """The Haar-expected (or any distribution's) gate count and fidelity of ``basis_gate`` at each of ``basis_fidelities`` (at most
+    ``_ffi.APPROX_MAX_FID``), from one launch over ``targets`` (``slam_approx_counts``): the choice of ``approx_decompose`` per target
+    and fidelity, counted per size, and the mean of the chosen expected fidelities (summed in fixed point, 2^-32: the result does not
+    depend on the order of addition).  Refusals as ``approx_decompose``."""
+    g, family = _approx_gate(basis_gate)
+    f = _check_fidelities(basis_fidelities)
     ctx = runtime.get_context(device)
     n = _resident(ctx, targets)
     if n == 0:
         return FidelitySweep(f, np.zeros((len(f), 4), dtype=np.int64), np.full(len(f), np.nan), np.full(len(f), np.nan), 0, basis_gate)
     counts, fidsum = (ctx.sc_counts if family == _SC_FAMILY else ctx.approx_counts)(g, f, 0, n)
+    return FidelitySweep(f, counts, counts @ np.arange(4.0) / n, fidsum / 4294967296.0 / n, n, basis_gate)
+
+
+def sqiswap_approx_decompose(targets, basis_fidelity: float = 1.0, cycles=None, device: int = 0,
+                             success_threshold: float = 1e-10) -> ApproxDecomposition:
+    """The entry point for an imperfect sqrt(iSWAP): ``approx_decompose`` for ``RiSwapGate(1/2)``, which that function refuses.  Per
+    target the circuit of 0, 1, 2 or 3 sqrt(iSWAP) gates with the highest expected fidelity F_k * basis_fidelity^k
+    (``slam_sqiswap_approx_decompose``, csrc/slam_sqapprox.hpp): no gate, one gate, the nearest point of the region |z| <= x - y that
+    two gates reach (the target itself inside it), and the three gates of ``sqiswap_decompose``; ties go to fewer gates, so
+    ``basis_fidelity=1`` gives the sizes of ``sqiswap_decompose`` except that a local target costs no gate and a target of the gate's
+    own class one.  ``cycles=k`` takes that size for every target.  ``targets`` are given as for ``sqiswap_decompose``; the result's
+    ``basis_gate`` is ``RiSwapGate(1/2)``.  ``ValueError`` (before any context is made) for a fidelity outside (0, 1] and a size
+    outside 0..3."""
+    from . import _ffi
+    from .gates import RiSwapGate
+
+    f = _ffi.check_basis_fidelity(basis_fidelity)
+    if cycles is not None and not (isinstance(cycles, (int, np.integer)) and 0 <= cycles <= 3):
+        raise ValueError(f"cycles must be None or an integer in 0..3, got {cycles!r}")
+    basis_gate = RiSwapGate(1 / 2)
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
+    if n == 0:
+        return _empty(ApproxDecomposition, success_threshold, basis_gate, np.zeros(0), np.zeros(0), f)
+    x, size, loss, predicted, gap = ctx.sqiswap_approx_decompose(f, cycles, 0, n)
+    expected = (4.0 + 16.0 * (1.0 - loss) ** 2) / 20.0 * f ** size
+    return ApproxDecomposition(size, x, loss, gap, success_threshold, basis_gate, predicted, expected, f)
+
+
+def sqiswap_fidelity_sweep(targets, basis_fidelities, device: int = 0) -> FidelitySweep:
+    """The entry point for the sweep of an imperfect sqrt(iSWAP): ``fidelity_sweep`` for ``RiSwapGate(1/2)``, which that function
+    refuses -- the choice of ``sqiswap_approx_decompose`` per target at each of ``basis_fidelities`` (at most
+    ``_ffi.APPROX_MAX_FID``), counted per size, and the mean of the chosen expected fidelities, from one launch
+    (``slam_sqiswap_approx_counts``).  ``ValueError`` (before any context is made) for a fidelity outside (0, 1] and for no or too
+    many fidelities."""
+    from .gates import RiSwapGate
+
+    f = _check_fidelities(basis_fidelities)
+    basis_gate = RiSwapGate(1 / 2)
+    ctx = runtime.get_context(device)
+    n = _resident(ctx, targets)
+    if n == 0:
+        return FidelitySweep(f, np.zeros((len(f), 4), dtype=np.int64), np.full(len(f), np.nan), np.full(len(f), np.nan), 0, basis_gate)
+    counts, fidsum = ctx.sqiswap_approx_counts(f, 0, n)
     return FidelitySweep(f, counts, counts @ np.arange(4.0) / n, fidsum / 4294967296.0 / n, n, basis_gate)
 
 

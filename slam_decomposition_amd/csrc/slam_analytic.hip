@@ -1,7 +1,7 @@
 // slam_analytic.hip -- host side of libslamhip.so, analytic unit: the closed-form decompositions into sqrt(iSWAP) gates
 // (slam_analytic.hpp), into gates of the CNOT or the iSWAP class (slam_cx.hpp) and into gates of the B class (slam_b.hpp), and the
-// fidelity-aware approximate decomposition into gates of those three classes (slam_approx.hpp) and of any supercontrolled class
-// (slam_sc.hpp).
+// fidelity-aware approximate decomposition into gates of those three classes (slam_approx.hpp), of any supercontrolled class
+// (slam_sc.hpp) and into sqrt(iSWAP) gates (slam_sqapprox.hpp).
 #include "slam_host.hpp"
 
 #include <complex>
@@ -12,6 +12,7 @@
 #include "slam_b.hpp"
 #include "slam_approx.hpp"
 #include "slam_sc.hpp"
+#include "slam_sqapprox.hpp"
 
 // ---- slam_cx_decompose, slam_b_decompose: the host's share (plain C++) -------------------------------------------------------------------
 namespace {
@@ -387,6 +388,22 @@ int slam_sc_counts(slam_ctx* ctx, int64_t first, int64_t count, const double* ga
     if (rc) return rc;
     return run_counts(ctx, first, count, sc_counts_kernel, [bp](ScCountsArgs& a) { a.beta_p = bp; }, n_fid, fidelities, counts_out,
                       fidsum_out);
+}
+
+int slam_sqiswap_approx_decompose(slam_ctx* ctx, int64_t first, int64_t count, double basis_fidelity, int force_cycles, double* x_out,
+                                  int32_t* cycles, double* loss, double* predicted, double* gap) {
+    if (!(basis_fidelity > 0.0 && basis_fidelity <= 1.0))  // a NaN fails both
+        return fail(SLAM_ERR_INVALID, "basis_fidelity must be in (0, 1], got %g", basis_fidelity);
+    if (force_cycles < -1 || force_cycles > 3)
+        return fail(SLAM_ERR_INVALID, "force_cycles must be -1 (select) or 0..3, got %d", force_cycles);
+    return run_closed_form(
+        ctx, first, count, sqiswap_approx_decompose_kernel, nullptr, 0,
+        [=](SqApproxArgs& a, const double*) { a.force = force_cycles, a.fidelity = basis_fidelity; }, x_out, cycles, loss, gap, predicted);
+}
+
+int slam_sqiswap_approx_counts(slam_ctx* ctx, int64_t first, int64_t count, int32_t n_fid, const double* fidelities, int64_t* counts_out,
+                               int64_t* fidsum_out) {
+    return run_counts(ctx, first, count, sqiswap_approx_counts_kernel, [](SqApproxCountsArgs&) {}, n_fid, fidelities, counts_out, fidsum_out);
 }
 
 }  // extern "C"

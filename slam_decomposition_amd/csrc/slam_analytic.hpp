@@ -100,11 +100,13 @@ __device__ __forceinline__ void shift_locals(int i, cplx (&g)[2][2], cplx (&gp)[
     }
 }
 
-// the six angles of the layer C1 (x) C2 for the folded class f (units of pi): qubit 0 (C2), then qubit 1 (C1)
-__device__ inline void analytic_interior(const double (&f)[3], double* __restrict__ p) {
+// the six angles of the layer C1 (x) C2 for the folded class f (units of pi): qubit 0 (C2), then qubit 1 (C1).  face: f is known to
+// lie on the face |z| = x - y of the region, where C vanishes analytically; it is taken as 0 (alpha = beta) and not from its rounding
+// residue (slam_sqapprox.hpp)
+__device__ inline void analytic_interior(const double (&f)[3], double* __restrict__ p, bool face = false) {
     const double hp = 1.57079632679489661923;
     const double x = hp * f[0], y = hp * f[1], z = hp * f[2];
-    const double C = sin(x + y - z) * sin(x - y + z) * sin(-x - y - z) * sin(-x + y + z);
+    const double C = face ? 0.0 : sin(x + y - z) * sin(x - y + z) * sin(-x - y - z) * sin(-x + y + z);
     const double rc = 2.0 * sqrt(fmax(C, 0.0));
     const double c2x = cos(2.0 * x), c2y = cos(2.0 * y), c2z = cos(2.0 * z);
     const double base = c2x - c2y + c2z;
@@ -142,6 +144,68 @@ __device__ inline void analytic_can(const double (&c)[3], double (&u)[32]) {
     u[10] = d1.re; u[11] = d1.im; u[12] = o1.re; u[13] = o1.im;   // row 1: columns 1, 2
     u[18] = o1.re; u[19] = o1.im; u[20] = d1.re; u[21] = d1.im;   // row 2: columns 1, 2
     u[24] = o0.re; u[25] = o0.im; u[30] = d0.re; u[31] = d0.im;   // row 3: columns 0, 3
+}
+
+// The three-gate construction of sqiswap_decompose_kernel in three pieces, for sqiswap_approx_decompose_kernel (slam_sqapprox.hpp).
+// They are copies, statement for statement: the kernel below keeps its own statements, because moved onto these functions -- any one of
+// them -- it compiles to another register allocation (gfx950, checked on the ISA), and its generated code stays as it is.
+// The placement of the chamber point c whose reduced class has the largest margin (the lowest index among equals): its index into
+// shift, the reduced class into f, c - s into raw.  All three keep what they held if no margin exceeds -1 (none does not).
+__device__ __forceinline__ void analytic_best_shift(const double (&c)[3], int& shift, double (&f)[3], double (&raw)[3]) {
+    double best = -1.0;
+    for (int s = 0; s < 12; ++s) {
+        double sh[3], fs[3];
+        analytic_shift(s, sh);
+        const double rs[3] = {c[0] - sh[0], c[1] - sh[1], c[2] - sh[2]};
+        analytic_fold(rs, fs);
+        const double m = (fs[0] - fs[1]) - fabs(fs[2]);
+        if (m > best) {
+            best = m;
+            shift = s;
+            f[0] = fs[0]; f[1] = fs[1]; f[2] = fs[2];
+            raw[0] = rs[0]; raw[1] = rs[1]; raw[2] = rs[2];
+        }
+    }
+}
+
+// L = A A_V^+, R = B_V^+ B of the aligned pair (kv, kr); index 1 of a pair acts on qubit 1 (angles 3..5 of a layer), index 2 on qubit 0
+__device__ __forceinline__ void analytic_align_products(const Kak& kv, const Kak& kr, cplx (&L1)[2][2], cplx (&L2)[2][2], cplx (&R1)[2][2],
+                                                        cplx (&R2)[2][2]) {
+    cplx dg[2][2];
+    dagger2(kv.a1, dg);
+    mul2(kr.a1, dg, L1);
+    dagger2(kv.a2, dg);
+    mul2(kr.a2, dg, L2);
+    dagger2(kv.b1, dg);
+    mul2(dg, kr.b1, R1);
+    dagger2(kv.b2, dg);
+    mul2(dg, kr.b2, R2);
+}
+
+// the row of three gates: T ~ (A L1) S C S (R1 Ls) S (Rs B) with the interior layer `mid` and the local gates of placement `shift`
+__device__ __forceinline__ void analytic_row3(int shift, const Kak& kt, const cplx (&L1)[2][2], const cplx (&L2)[2][2], const cplx (&R1)[2][2],
+                                              const cplx (&R2)[2][2], const double (&mid)[6], double* __restrict__ xo) {
+    cplx g[2][2], gp[2][2], dg[2][2], m[2][2];
+    shift_locals(shift, g, gp);
+    // layer 0 = Rs B_T = (p^+ g^+ B1) (x) (g^+ B2)
+    dagger2(g, dg);
+    mul2(dg, kt.b2, m);
+    put_u3(m, xo);
+    dagger2(gp, dg);
+    mul2(dg, kt.b1, m);
+    put_u3(m, xo + 3);
+    // layer 1 = R1 Ls = (R1 g p) (x) (R2 g)
+    mul2(R2, g, m);
+    put_u3(m, xo + 6);
+    mul2(R1, gp, m);
+    put_u3(m, xo + 9);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) xo[12 + j] = mid[j];
+    // layer 3 = A_T L1
+    mul2(kt.a2, L2, m);
+    put_u3(m, xo + 18);
+    mul2(kt.a1, L1, m);
+    put_u3(m, xo + 21);
 }
 
 __global__ __launch_bounds__(kKakBlock) void sqiswap_decompose_kernel(AnalyticArgs a) {

@@ -200,6 +200,23 @@ int main() {
         EXPECT(std::strstr(slam_last_error(), "fidelities[1]") != nullptr);
         EXPECT(slam_sc_counts(nullptr, 0, 1, sc_gate, sc_dress, 65, fid, &i64, &i64) == SLAM_ERR_INVALID);
     }
+    {  // slam_sqiswap_approx_decompose, slam_sqiswap_approx_counts: no gate to reduce, the fidelity and the size come first
+        const double fid[2] = {0.9, 1.0}, bad_fid[2] = {0.9, 1.5};
+        EXPECT(slam_sqiswap_approx_decompose(nullptr, 0, 1, 0.99, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_sqiswap_approx_decompose(nullptr, 0, 1, 0.99, 3, nullptr, nullptr, nullptr, nullptr, nullptr) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_sqiswap_approx_decompose(nullptr, 0, 1, 0.0, -1, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "basis_fidelity") != nullptr);
+        EXPECT(slam_sqiswap_approx_decompose(nullptr, 0, 1, 0.99, 4, d, i32, d, d, d) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "force_cycles") != nullptr);
+        EXPECT(slam_sqiswap_approx_counts(nullptr, 0, 1, 2, fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_sqiswap_approx_counts(nullptr, 0, 1, 2, bad_fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "fidelities[1]") != nullptr);
+        EXPECT(slam_sqiswap_approx_counts(nullptr, 0, 1, 65, fid, &i64, &i64) == SLAM_ERR_INVALID);
+        EXPECT(slam_sqiswap_approx_counts(nullptr, 0, 1, 2, nullptr, &i64, &i64) == SLAM_ERR_INVALID);
+    }
     EXPECT(slam_predict_spans(nullptr, 0, 1, 3, d, d, 0.0, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_coverage_lookup(nullptr, 0, 1, 1, i32, i32, d, d, 0.0, &i64, i32) == SLAM_ERR_INVALID);
     EXPECT(slam_family_lookup(nullptr, 0, 1, 1, i32, i32, d, d, i32, i32, d, 0.1, 1e-7, 0, &i64, &i64, i32, i32) == SLAM_ERR_INVALID);
