@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "slam_sincos.hpp"
 #include "slam_types.hpp"
 
@@ -177,6 +179,22 @@ __device__ __forceinline__ void quad_sum2(double& a, double& b) {
     const double a2 = quad_shuffle<0x4E>(a), b2 = quad_shuffle<0x4E>(b);
     a += a2; b += b2;
 }
+// the two stages of quad_sum2 on their own, for a caller that puts other work between them (the same additions in the same order)
+__device__ __forceinline__ void quad_sum2_stage1(double& a, double& b) {
+    const double a1 = quad_shuffle<0xB1>(a), b1 = quad_shuffle<0xB1>(b);
+    a += a1; b += b1;
+}
+__device__ __forceinline__ void quad_sum2_stage2(double& a, double& b) {
+    const double a2 = quad_shuffle<0x4E>(a), b2 = quad_shuffle<0x4E>(b);
+    a += a2; b += b2;
+}
+// Independent work that a caller hands to eval_quad / h_matvec to be issued between an LDS request and its wait; NoFill: nothing
+struct NoFill {
+    __device__ __forceinline__ void operator()() const {}
+    __device__ __forceinline__ void operator()(double) const {}
+};
+template <class F>
+inline constexpr bool has_fill = !std::is_same<F, NoFill>::value;
 // max(|a|, |b|) in ONE instruction: fmax() canonicalises its operands first (IEEE sNaN semantics), an extra v_max_f64
 // x, x, x each; the callers' values are finite by construction
 __device__ __forceinline__ double max_abs(double a, double b) {
@@ -876,12 +894,13 @@ __device__ __forceinline__ void mk_loss_seed(const double (&wr)[4], const double
 // MK: MakhlinFunctionalCost instead (cost_kind is ignored, the target column is not read): mkt = the target's invariants g(T)
 // ROOMY (roomy_regs): the lane constants come in through lc, formed once per kernel (theta_bits is not looked at; cost_kind only
 // for the two coefficients that stay scalar)
-template <int K, bool HUGE_ARGS, int GC, bool MK = false, bool ROOMY = false>
+template <int K, bool HUGE_ARGS, int GC, bool MK = false, bool ROOMY = false, bool SPLIT = false, class UnderGrad = NoFill>
 __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const double* tcol,
                                           const double* gates, double* xq, double2* fh, const double2* tbl,
                                           int q, int theta_bits, int cost_kind, double& fout, double (&gd)[Cfg<K>::NA],
                                           double (&Wr)[4], double (&Wi)[4], const double* mkt = nullptr,
-                                          const EvalLaneConsts<Cfg<K>::NA>* lc = nullptr) {
+                                          const EvalLaneConsts<Cfg<K>::NA>* lc = nullptr, UnderGrad under_grad = {}) {
+    static_assert(!SPLIT || (!HUGE_ARGS && Cfg<K>::NA > 2), "the split trig exchange: the table-lookup form, layer 0 in slots 0 and 1");
     constexpr bool LEAN = lean_layout<K, GC>();
     constexpr bool PSQ = psq_layout<K, GC>();
     using C = Cfg<K, PSQ>;
@@ -901,6 +920,7 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
         }
     }
     // ---- 1. trig table: each lane handles its own parameter slots
+    U3t Bn, An;
     {
         double2* t2 = reinterpret_cast<double2*>(xt);
         if constexpr (HUGE_ARGS) {
@@ -934,11 +954,32 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
                 sincos_tbl_lookup<true>(arg, tbl, L, rr[a], kk[a], tt[a]);
             }
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (SPLIT) {
+                // layer 0 reads parameters 0..5 only: slots 0 and 1.  They are written first and layer 0's read-back is requested; the
+                // other slots' polynomials run while it is in flight (LDS is wave-private and in order: no wait in between)
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    double s, c;
+                    sincos_tbl_finish<true>(rr[a], kk[a], tt[a], L, s, c);
+                    t2[4 * a + q] = make_double2(c, s);
+                }
+                lds_fence();
+                Bn = load_u3(xt, 0);
+                An = load_u3(xt, 3);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int a = 2; a < C::NA; ++a) {
+                    double s, c;
+                    sincos_tbl_finish<true>(rr[a], kk[a], tt[a], L, s, c);
+                    t2[4 * a + q] = make_double2(c, s);
+                }
+            } else {
 #pragma unroll
             for (int a = 0; a < C::NA; ++a) {
                 double s, c;
                 sincos_tbl_finish<true>(rr[a], kk[a], tt[a], L, s, c);
                 t2[4 * a + q] = make_double2(c, s);
+            }
             }
         }
     }
@@ -969,7 +1010,10 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
         Fi[r] = 0.0;
     }
     // the next layer's trig entries are requested half a layer ahead (before the qubit-1 gate is applied)
-    U3t Bn = load_u3(xt, 0), An = load_u3(xt, 3);
+    if constexpr (!SPLIT) {
+        Bn = load_u3(xt, 0);
+        An = load_u3(xt, 3);
+    }
 #pragma unroll
     for (int j = 0; j <= K; ++j) {
         if (j > 0 && !LEAN) {
@@ -1262,6 +1306,14 @@ __device__ __forceinline__ void eval_quad(const double (&xd)[Cfg<K>::NA], const 
                 p2[a] = ps[4 * a + 2 * C::PSP];
                 p3[a] = ps[4 * a + 3 * C::PSP];
             }
+            if constexpr (has_fill<UnderGrad>) {
+                // the caller's loss-only decisions, issued under the owner reads' round trip
+                // (the loss as a value of its own: the caller's arithmetic is not contracted with the product that forms it)
+                asm volatile("" : "+v"(fout));
+                __builtin_amdgcn_sched_barrier(0);
+                under_grad(fout);
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int a = 0; a < C::NA; ++a) gd[a] = (4 * a + q < C::N) ? (p0[a] + p1[a]) + (p2[a] + p3[a]) : 0.0;
         } else {
@@ -1324,9 +1376,11 @@ __device__ __forceinline__ void h_set_identity(HMat<NA>& H, int q) {
 // Lane q holds row q of each upper block (a, b): it adds H[4a+q][4b+e] v[4b+e] to its own out[a]
 // and owes H[4a+q][4b+e] v[4a+q] to lane e's out[b]; those "transposed" sums go through LDS as soon
 // as column block b is finished, so only one 4-float accumulator is live at a time.
-template <int NA>
+// under_v / under_t: the caller's independent work, issued under the round trip of the broadcasts / of the transposed sums
+template <int NA, class UnderV = NoFill, class UnderT = NoFill>
 __device__ __forceinline__ void h_matvec(const HMat<NA>& H, const double (&vd)[NA], float* xq32, int q,
-                                         double (&out)[NA]) {
+                                         double (&out)[NA], UnderV under_v = {}, UnderT under_t = {}) {
+    static_assert((!has_fill<UnderV> && !has_fill<UnderT>) || NA <= 8, "the fills sit behind the batched requests");
     float v32[NA];
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
@@ -1346,6 +1400,10 @@ __device__ __forceinline__ void h_matvec(const HMat<NA>& H, const double (&vd)[N
 #pragma unroll
         for (int b = 0; b < NA; ++b) vall[b] = *reinterpret_cast<const f32x4*>(xq32 + 4 * b);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (has_fill<UnderV>) {
+            under_v();
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
 #pragma unroll
     for (int b = 0; b < NA; ++b) {
@@ -1375,6 +1433,10 @@ __device__ __forceinline__ void h_matvec(const HMat<NA>& H, const double (&vd)[N
 #pragma unroll
         for (int a = 1; a < NA; ++a) tall[a] = *reinterpret_cast<const f32x4*>(xt + (4 * a + q) * 4);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (has_fill<UnderT>) {
+            under_t();
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
 #pragma unroll
     for (int a = 0; a < NA; ++a) {

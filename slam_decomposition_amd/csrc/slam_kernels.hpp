@@ -238,6 +238,14 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
     constexpr bool kRoomy = roomy_regs<K, GC, MQ, WL>() && !MK;
     // (span 2, tried: the per-item values cost it 3 registers -- 251 of 256 -- for 6 of its 2800 instructions; not taken)
     constexpr bool kRoomyItem = kRoomy && !MQ;  // three more registers, per item (below); the multi-queue dense kernel has none left
+    // Round order (spans 1 and 2 of the structured classes; not the wave loop, not Makhlin): independent work is issued under three of the
+    // round's exposed LDS round trips.  Only the order of instructions changes: every floating-point operation is the one of the
+    // plain order, which the other instantiations keep.
+    //   kLossUnder   the state machine's loss-only decisions under the gradient's owner reads (eval_quad, under_grad)
+    //   kTrigSplit   layer 0's trig entries written and read back first, the other slots' polynomials under that read-back
+    //   kSumsUnder   the inputs of the p.g' / y.y reduction under the mat-vec's two round trips (span 1: at span 2 it measured nothing)
+    constexpr bool kOrder = K <= 2 && psq_layout<K, GC>() && !WL && !MK;
+    constexpr bool kLossUnder = kOrder, kTrigSplit = kOrder, kSumsUnder = kOrder && K == 1;
     EvalLaneConsts<NA> lane_consts;
     if constexpr (kRoomy) eval_lane_consts<K>(q, args.cost_kind, lane_consts);
     double* xq = xchg + quad * C::XSTRIDE;
@@ -589,20 +597,40 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
         //         fresh: alpha = 0, p = 0)
         double gt[NA];
         double ft, Wr[4], Wi[4];
+        const bool active = live;
+        // kLossUnder: what the state machine decides from the loss alone (ft, f, gp, alpha) is computed under the round trip of the gradient's
+        // owner reads at the end of the evaluation, into these, and consumed where the state machine stands
+        bool e_finite = false, e_acc = false, e_step = false;
+        double e_am = 0.0;
+        int e_nstall = 0;
         {
             double xt[NA];
 #pragma unroll
             for (int a = 0; a < NA; ++a) xt[a] = fma(alpha, p[a], x[a]);
             if constexpr (MK) {
                 eval_quad<K, false, GC, true>(xt, tcol, args.gates, xq, fh, tbl, q, theta_bits, 0, ft, gt, Wr, Wi, mkt);
+            } else if constexpr (kLossUnder) {
+                auto loss_only = [&](double ftv) {
+                    e_finite = isfinite(ftv);
+                    const bool armijo = e_finite && (ftv <= f + kArmijoC1 * alpha * gp);
+                    e_acc = active && (fresh ? e_finite : armijo);
+                    e_step = e_acc && !fresh;
+                    nev += active ? (e_acc ? 0x100001 : 1) : 0;
+                    e_am = e_step ? alpha : 0.0;
+#pragma unroll
+                    for (int a = 0; a < NA; ++a) x[a] += e_am * p[a];
+                    e_nstall = (e_step && (f - ftv) <= kStallDf) ? nstall + 1 : 0;
+                };
+                eval_quad<K, false, GC, false, kRoomy, kTrigSplit>(xt, tcol, MQ ? cold_args<K, MQ>(cur)->gates : args.gates, xq, fh, tbl, q, theta_bits,
+                                                                   WL ? __builtin_amdgcn_readfirstlane(args.cost_kind) : args.cost_kind, ft, gt, Wr, Wi,
+                                                                   nullptr, kRoomy ? &lane_consts : nullptr, loss_only);
             } else {
-                eval_quad<K, false, GC, false, kRoomy>(xt, tcol, MQ ? cold_args<K, MQ>(cur)->gates : args.gates, xq, fh, tbl, q, theta_bits,
-                                                       WL ? __builtin_amdgcn_readfirstlane(args.cost_kind) : args.cost_kind, ft, gt, Wr, Wi, nullptr,
-                                                       kRoomy ? &lane_consts : nullptr);
+                eval_quad<K, false, GC, false, kRoomy, kTrigSplit>(xt, tcol, MQ ? cold_args<K, MQ>(cur)->gates : args.gates, xq, fh, tbl, q, theta_bits,
+                                                                   WL ? __builtin_amdgcn_readfirstlane(args.cost_kind) : args.cost_kind, ft, gt, Wr, Wi,
+                                                                   nullptr, kRoomy ? &lane_consts : nullptr);
             }
         }
-        const bool active = live;
-        const bool finite = isfinite(ft);
+        const bool finite = kLossUnder ? e_finite : isfinite(ft);
         // a non-finite trial point is never accepted; its gradient is zeroed here once so that everything below
         // stays finite without per-element guards (0 * NaN would otherwise leak into H through w and v)
 #pragma unroll
@@ -615,30 +643,46 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
             }
         }
         const bool armijo = finite && (ft <= f + kArmijoC1 * alpha * gp);
-        const bool acc = active && (fresh ? finite : armijo);
-        const bool step = acc && !fresh;  // a real quasi-Newton step (not the initial evaluation)
+        const bool acc = kLossUnder ? e_acc : active && (fresh ? finite : armijo);
+        const bool step = kLossUnder ? e_step : acc && !fresh;  // a real quasi-Newton step (not the initial evaluation)
         // evaluation counters of the item, packed: bits 0..19 all evaluations, bits 20..31 the accepted ones
         // (at most maxiter + 1 <= 4095: the host caps maxiter)
-        nev += active ? (acc ? 0x100001 : 1) : 0;
+        if constexpr (!kLossUnder) nev += active ? (acc ? 0x100001 : 1) : 0;
 
         // ---- 3. quasi-Newton update.  s = am p and y = g' - g are formed on the fly; for quads that do not
         //         step, am = 0 and curv = false, hence rho = cf = 0 and w = v = 0: H is left unchanged (their
         //         y-dependent scalars are finite garbage that is multiplied by zero).
-        const double am = step ? alpha : 0.0;
+        const double am = kLossUnder ? e_am : (step ? alpha : 0.0);
         double qv[NA];
-        __builtin_amdgcn_sched_barrier(0);  // keep the phases apart: interleaving them only adds live registers
-        h_matvec<NA>(H, gt, xq32, q, qv);
-        __builtin_amdgcn_sched_barrier(0);
         // s = am p, so every product with s follows from p.g' (one reduction) and the direction's own p.g, p.p, which
         // the previous round left in gp and pp:  s.g' = am p.g',  s.y = am (p.g' - p.g),  s.s = am^2 p.p
         double pgt = 0.0, yy = 0.0;
+        __builtin_amdgcn_sched_barrier(0);  // keep the phases apart: interleaving them only adds live registers
+        if constexpr (kSumsUnder) {
+            // the reduction's inputs under the mat-vec's two round trips: the products under the broadcasts', the first shuffle
+            // stage under the transposed sums'
+            auto products = [&]() {
 #pragma unroll
-        for (int a = 0; a < NA; ++a) {
-            const double ya = gt[a] - g[a];
-            pgt = fma(p[a], gt[a], pgt);
-            yy = fma(ya, ya, yy);
+                for (int a = 0; a < NA; ++a) {
+                    const double ya = gt[a] - g[a];
+                    pgt = fma(p[a], gt[a], pgt);
+                    yy = fma(ya, ya, yy);
+                }
+            };
+            h_matvec<NA>(H, gt, xq32, q, qv, products, [&]() { quad_sum2_stage1(pgt, yy); });
+            __builtin_amdgcn_sched_barrier(0);
+            quad_sum2_stage2(pgt, yy);
+        } else {
+            h_matvec<NA>(H, gt, xq32, q, qv);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                const double ya = gt[a] - g[a];
+                pgt = fma(p[a], gt[a], pgt);
+                yy = fma(ya, ya, yy);
+            }
+            quad_sum2(pgt, yy);
         }
-        quad_sum2(pgt, yy);
         const double sg = am * pgt;
         const double sy = am * (pgt - gp);
         const double ss = (am * am) * pp;
@@ -686,11 +730,15 @@ __device__ __forceinline__ void minimize_body(const MinimizeArgs<K>& args, const
 
         // ---- 4. per-quad state machine
         // x <- x + s outside the branch: s = am p is zero unless the step was accepted, so no per-component select
+        // (kLossUnder: x was updated with the loss-only decisions, before p changes below)
+        if constexpr (!kLossUnder) {
 #pragma unroll
-        for (int a = 0; a < NA; ++a) x[a] += am * p[a];
+            for (int a = 0; a < NA; ++a) x[a] += am * p[a];
+        }
         bool done = false;
         if (acc) {
-            nstall = (step && (f - ft) <= kStallDf) ? nstall + 1 : 0;
+            if constexpr (kLossUnder) nstall = e_nstall;
+            else nstall = (step && (f - ft) <= kStallDf) ? nstall + 1 : 0;
             f = ft;
             if (step) ++iters;
             nback = 0;
