@@ -846,6 +846,40 @@ int slam_smush_minimize_stage_trace(slam_ctx* ctx, int k, const int32_t* gate_se
                                     double* trace_x);
 
 /*
+ * Three-qubit templates, 8x8 targets (csrc/slam_q3.hpp; the reference's CircuitTemplate(n_qubits=3, edge_params=...),
+ * src/slam/basis.py:52-169).  The circuit, in time order: a U3 on q0, on q1, on q2, then per two-qubit gate j = 0 .. k - 1 on the edge
+ * (a_j, b_j): the gate, a U3 on a_j, a U3 on b_j.  n = 9 + 6 k parameters in index order, (theta, phi, lambda) per U3;
+ * 1 <= k <= SLAM_Q3_MAX_SPAN (beyond: SLAM_ERR_UNSUPPORTED).  Matrices are qiskit little-endian 8x8, double[8][8][2] row-major, basis
+ * index q0 + 2 q1 + 4 q2; a gate's 4x4 on the edge (a, b) has qubit a as its bit 0 and qubit b as its bit 1.
+ * Both calls are self-contained: gates, targets and parameters come from the host with the call; the context lends its device and
+ * stream, and its resident 4x4 targets, gate table, results and statistics are not touched.
+ *   gates       double[n_gates][4][4][2]   the gate table
+ *   gate_index  int32[k]                   the table entry of position j
+ *   edges       int32[k][2]                (a_j, b_j): ordered pairs of distinct qubits from {0, 1, 2}
+ *   targets     double[n_targets][8][8][2]
+ *   cost_kind   SLAM_COST_BASIC  1 - |Tr(T^+ W)| / 8,  SLAM_COST_SQUARE  1 - (|Tr(T^+ W)|^2 + 8) / 72;
+ *               SLAM_COST_MAKHLIN returns SLAM_ERR_UNSUPPORTED (Weyl chamber only for 2Q gates, cost_function.py)
+ * slam_q3_eval: M items, item m = (x[m], target target_of[m]):
+ *   x double[M][n], target_of int32[M]; out: loss double[M], grad double[M][n] (may be NULL), unitary double[M][8][8][2] (may be NULL)
+ * slam_q3_minimize: one stage, as slam_minimize_stage -- for every target `restarts` quasi-Newton minimisations (one wavefront per
+ * item, restart-major queue, Philox start points keyed (pair, restart, target index + target_base, k) or explicit x0, ordered early
+ * exit at exit_loss); the stage result of a target is the lowest-index restart below exit_loss with SLAM_FLAG_ORDERED, the smallest
+ * loss otherwise and when no restart is below it:
+ *   x0 double[n_targets][R][n] or NULL; out (any may be NULL): best_loss double[n_targets], best_x double[n_targets][n],
+ *   best_restart int32[n_targets]; per item [n_targets][R]: item_loss, item_iters, item_status (SLAM_ST_*), item_evals,
+ *   item_x double[n_targets][R][n]; kernel_ms: device time of the optimizer kernel
+ * Arguments are checked before the context and before anything touches the device.
+ */
+#define SLAM_Q3_MAX_SPAN 15
+int slam_q3_eval(slam_ctx* ctx, const double* gates, int32_t n_gates, int32_t k, const int32_t* gate_index, const int32_t* edges,
+                 const double* targets, int64_t n_targets, const double* x, const int32_t* target_of, int64_t M, int32_t cost_kind,
+                 double* loss, double* grad, double* unitary);
+int slam_q3_minimize(slam_ctx* ctx, const double* gates, int32_t n_gates, int32_t k, const int32_t* gate_index, const int32_t* edges,
+                     const double* targets, int64_t n_targets, int32_t cost_kind, const slam_opt_params* params, double exit_loss,
+                     const double* x0, double* best_loss, double* best_x, int32_t* best_restart, double* item_loss, int32_t* item_iters,
+                     int32_t* item_status, int32_t* item_evals, double* item_x, double* kernel_ms);
+
+/*
  * Multi-GPU: one process per GPU, RCCL over xGMI, reached through this ABI (no torch, no MPI).  The path shards by
  * target, every rank keeps all restarts of its targets, so the only exchange is the FINAL min-all-reduce of the
  * best-loss vector -- the running minimum of TemplateOptimizer._run (src/slam/optimizer.py:281-284) taken over the
@@ -922,7 +956,8 @@ const char* slam_version(void);
  *      later: slam_approx_decompose and slam_approx_counts (new symbols only);
  *      later: slam_candidate_scores (a new symbol only);
  *      later: slam_sc_decompose and slam_sc_counts (new symbols only);
- *      later: slam_sqiswap_approx_decompose and slam_sqiswap_approx_counts (new symbols only).
+ *      later: slam_sqiswap_approx_decompose and slam_sqiswap_approx_counts (new symbols only);
+ *      later: slam_q3_eval and slam_q3_minimize (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -110,6 +110,8 @@ EXPORTED_SYMBOLS = (
     "slam_pd_extremes",
     "slam_pd_filter",
     "slam_region_lookup",
+    "slam_q3_eval",
+    "slam_q3_minimize",
     "slam_set_cost",
     "slam_synchronize",
     "slam_host_alloc",
@@ -313,6 +315,9 @@ def load_library() -> C.CDLL:
         lib.slam_pd_extremes.argtypes = [P, P, C.c_int32, P, P]
         lib.slam_pd_filter.argtypes = [P, P, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_int64), P, P]
         lib.slam_region_lookup.argtypes = [P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P, P, C.c_double, P]
+    if hasattr(lib, "slam_q3_eval"):
+        lib.slam_q3_eval.argtypes = [P, P, C.c_int32, C.c_int32, P, P, P, C.c_int64, P, P, C.c_int64, C.c_int32, P, P, P]
+        lib.slam_q3_minimize.argtypes = [P, P, C.c_int32, C.c_int32, P, P, P, C.c_int64, C.c_int32, C.POINTER(OptParams), C.c_double] + [P] * 10
     lib.slam_set_cost.argtypes = [P, C.c_int]
     lib.slam_synchronize.argtypes = [P]
     if hasattr(lib, "slam_host_alloc"):
@@ -1224,6 +1229,63 @@ class Context:
     ) -> dict:
         out = self._stage_call(self._lib.slam_minimize_stage, 0, gate_seq, params, active, x0, want_items=want_items)
         return {key: a for key, a in out.items() if a is not None}  # (without items: no item_* keys here, None in the V2 / smush form)
+
+    # -- three-qubit templates (slam_q3_*): self-contained calls, nothing resident -------------------------------------------
+    @staticmethod
+    def _q3_template(gates, gate_index, edges, targets):
+        g = _mat_to_ri(gates)
+        if g.ndim != 4:
+            raise ValueError("gates must have shape [G, 4, 4]")
+        gi = np.ascontiguousarray(gate_index, dtype=np.int32).reshape(-1)
+        ed = np.ascontiguousarray(edges, dtype=np.int32)
+        if ed.shape != (len(gi), 2):
+            raise ValueError(f"edges must have shape [{len(gi)}, 2]")
+        t = np.ascontiguousarray(np.asarray(targets, dtype=np.complex128))
+        if t.ndim != 3 or t.shape[1:] != (8, 8):
+            raise ValueError(f"expected targets of shape [N, 8, 8], got {t.shape}")
+        return g, gi, ed, t.view(np.float64).reshape(t.shape + (2,))
+
+    def q3_eval(self, gates, gate_index, edges, targets, x, target_of=None, cost_kind: int = 0, want_grad=True, want_unitary=False):
+        """``slam_q3_eval``: loss [M], gradient [M, n] (or None) and 8x8 unitary complex128 [M, 8, 8] (or None) of M parameter rows of
+        the three-qubit template (gate table [G, 4, 4], per position its table index and its edge (a, b)); n = 9 + 6 k."""
+        g, gi, ed, t = self._q3_template(gates, gate_index, edges, targets)
+        k = len(gi)
+        n = 9 + 6 * k
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != n:
+            raise ValueError(f"x must have shape [M, {n}]")
+        M = x.shape[0]
+        tof = np.zeros(M, np.int32) if target_of is None else np.ascontiguousarray(target_of, dtype=np.int32)
+        if tof.shape != (M,):
+            raise ValueError("target_of must have shape [M]")
+        loss = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, n), dtype=np.float64) if want_grad else None
+        w = np.empty((M, 8, 8, 2), dtype=np.float64) if want_unitary else None
+        _check(self._lib.slam_q3_eval(self._h, _ptr(g), g.shape[0], k, _ptr(gi), _ptr(ed), _ptr(t), t.shape[0], _ptr(x), _ptr(tof), M,
+                                      int(cost_kind), _ptr(loss), _ptr(grad), _ptr(w)))
+        return loss, grad, (None if w is None else w.view(np.complex128).reshape(M, 8, 8))
+
+    def q3_minimize(self, gates, gate_index, edges, targets, params: OptParams, exit_loss: float, cost_kind: int = 0, x0=None) -> dict:
+        """``slam_q3_minimize``: one stage over all targets x ``params.restarts``.  Returns ``best_loss`` [N], ``best_x`` [N, n],
+        ``best_restart`` [N], the per-item arrays [N, R] ``item_loss`` / ``item_iters`` / ``item_status`` / ``item_evals``, ``item_x``
+        [N, R, n] and ``kernel_ms``."""
+        g, gi, ed, t = self._q3_template(gates, gate_index, edges, targets)
+        k = len(gi)
+        n = 9 + 6 * k
+        N, R = t.shape[0], int(params.restarts)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (N, R, n):
+                raise ValueError(f"x0 must have shape [{N}, {R}, {n}]")
+        out = {"best_loss": np.empty(N, dtype=np.float64), "best_x": np.empty((N, n), dtype=np.float64),
+               "best_restart": np.empty(N, dtype=np.int32), "item_loss": np.empty((N, R), dtype=np.float64),
+               "item_iters": np.empty((N, R), dtype=np.int32), "item_status": np.empty((N, R), dtype=np.int32),
+               "item_evals": np.empty((N, R), dtype=np.int32), "item_x": np.empty((N, R, n), dtype=np.float64)}
+        ms = np.zeros(1, dtype=np.float64)
+        _check(self._lib.slam_q3_minimize(self._h, _ptr(g), g.shape[0], k, _ptr(gi), _ptr(ed), _ptr(t), N, int(cost_kind), C.byref(params),
+                                          float(exit_loss), _ptr(x0), *[_ptr(a) for a in out.values()], _ptr(ms)))
+        out["kernel_ms"] = float(ms[0])
+        return out
 
     # -- the whole span loop -------------------------------------------------
     @staticmethod

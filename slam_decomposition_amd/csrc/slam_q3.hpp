@@ -1,0 +1,563 @@
+// slam_q3.hpp -- three-qubit templates (8x8 targets): ONE WAVEFRONT per (target, restart) item, sibling of slam_long.hpp (gfx950 only).
+//
+// The circuit, in time order: U3 on q0, q1, q2 (parameters 0..8), then per two-qubit gate j = 0..k-1 on the edge (a_j, b_j): the gate, a
+// U3 on a_j, a U3 on b_j (parameters 9 + 6 j ..) -- n = 9 + 6 k parameters, k <= 15.  Matrices are qiskit little-endian: basis index
+// q0 + 2 q1 + 4 q2; a gate's 4x4 on (a, b) has qubit a as its bit 0 and qubit b as its bit 1.
+//   * lane l holds entry (r = l & 7, c = l >> 3) of the 8x8 running product P.  Left-multiplying by a U3 on qubit q mixes rows r and
+//     r ^ (1 << q), by a gate on (a, b) the four rows r ^ {0, 1 << a, 1 << b, both}: every exchange is a lane XOR of 1, 2 (DPP quad_perm)
+//     or 4 (ds_swizzle, bit mode) -- no LDS memory traffic, and the edge enters through two wave-uniform qubit numbers only;
+//   * backward, P_{l-1} = M_l^+ P_l undoes the factors (they are unitary: no prefix is stored) while the adjoint is carried TRANSPOSED,
+//     B^T_{l-1} = M_l^T B^T_l from B^T_L = z conj(T) (z = the loss seed), so right-multiplication is row mixing too;
+//   * the three derivatives of a U3 on qubit q come from the 2x2 block trace R[s', s] = sum_{r: bit_q(r) = s} sum_c P[r, c] B^T[r with
+//     bit q := s', c]: two complex products per lane (own entry, partner at XOR 1 << q) and masked wave sums:
+//         d/dphi = -Im R'[1, 1],  d/dtheta = 1/2 Re(e^{i phi} R'[1, 0] - e^{-i phi} R'[0, 1])   (P', B^T after the gate),
+//         d/dlam = -Im R[1, 1]                                                                  (P, B^T before it);
+//   * the optimizer is the iteration of slam_long_minimize.inc, its body copied for n = 9 + 6 k (n may be odd: slot n is padding):
+//     fp32 inverse metric in device memory (lane l owns columns 2 l, 2 l + 1), cautious update, Armijo backtracking, periodic restart,
+//     the same stopping tests and status codes, the restart-major work queue with ordered early exit, Philox start points.
+// Loss, gradient, parameters, steps: fp64.
+//
+// Reference behaviour: CircuitTemplate(n_qubits, edge_params) src/slam/basis.py:52-169; BasicCost / SquareCost
+// src/slam/cost_function.py:140-145,169-173; the restart loop src/slam/optimizer.py:253-295.
+#pragma once
+#include "slam_long.hpp"
+
+namespace slamdev {
+
+constexpr int kQ3MaxSpan = 15;
+constexpr int kQ3N = 9 + 6 * kQ3MaxSpan;  // 99 parameters at most
+constexpr int kQ3NP = 128;                // vector length in LDS: component i = 2 lane + a, a = 0, 1
+constexpr int kQ3Slots = 2;
+constexpr int kQ3HStride = kQ3NP;         // floats per row of the inverse Hessian in device memory
+constexpr int kQ3RowBatch = 16;
+
+// LDS of one wavefront, in doubles
+constexpr int kQ3OffTbl = 0;                                // sincos table (64 double2)
+constexpr int kQ3OffX = kQ3OffTbl + kSincosLdsDoubles;      // trial point x[NP]
+constexpr int kQ3OffG = kQ3OffX + kQ3NP;                    // gradient g[NP]
+constexpr int kQ3OffTrig = kQ3OffG + kQ3NP;                 // (cos, sin) of every (half-)angle: [100] double2
+constexpr int kQ3OffGate = kQ3OffTrig + 2 * (kQ3N + 1);     // per position j the 16 entries E_j[i][m] = G_j[i][i ^ m]: [k][16] double2
+constexpr int kQ3OffF32 = kQ3OffGate + 32 * kQ3MaxSpan;     // three fp32 vectors [NP] of the metric pass
+constexpr int kQ3LdsDoubles = kQ3OffF32 + 3 * kQ3NP / 2;
+constexpr size_t kQ3LdsBytes = (size_t)kQ3LdsDoubles * sizeof(double);
+static_assert(16 * kQ3LdsBytes <= 160 * 1024, "four wavefronts per SIMD need sixteen wavefronts' LDS per CU");
+
+struct Q3Args {
+    const double* targets;    // [n_active][8][8][2]
+    const double* x0;         // [M][n] or nullptr (Philox)
+    StageCtl* ctl;
+    int32_t restarts;
+    int32_t maxiter;
+    double gtol, stop_loss, gtol_far, far_loss, exit_loss;
+    uint64_t seed;
+    int64_t target_base;
+    uint32_t flags;           // SLAM_FLAG_EARLY_EXIT | SLAM_FLAG_ORDERED
+    int32_t cost_kind;
+    int32_t* solved;
+    ItemRec* item_rec;        // [M]
+    double* item_x;           // [M][n]
+    const double* gates;      // [k][4][4][2]: the gate of every position
+    uint64_t edges;           // position j: a = bits 4 j, 4 j + 1; b = bits 4 j + 2, 4 j + 3
+    int32_t k;
+    float* hmem;              // [gridDim.x][n][kQ3HStride]
+};
+
+struct Q3EvalArgs {
+    const double* targets;
+    const double* x;          // [M][n]
+    const int32_t* target_of; // [M]
+    int64_t n_items;
+    double* loss;
+    double* grad;             // [M][n] or nullptr
+    double* unitary;          // [M][8][8][2] or nullptr
+    int32_t cost_kind;
+    const double* gates;
+    uint64_t edges;
+    int32_t k;
+};
+
+// the value of lane (l ^ (1 << q)), q wave-uniform
+__device__ __forceinline__ double q3_xchg(double v, int q) {
+    if (q == 0) return dpp_f64<0xB1>(v);
+    if (q == 1) return dpp_f64<0x4E>(v);
+    // ds_swizzle bit mode: and 0x1F, or 0, xor 4 (within each half of the wavefront)
+    const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), 0x101F), hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), 0x101F);
+    return __hiloint2double(hi, lo);
+}
+
+// the 2x2 complex matrices of one U3: M[2 s' + s]
+struct Q3Mat {
+    double r[4], i[4];
+};
+// mode 0: U3; 1: its inverse U3^+; 2: its transpose
+template <int MODE>
+__device__ __forceinline__ Q3Mat q3_u3_mat(const U3t& t) {
+    const double epr = t.cp * t.cl - t.sp * t.sl, epi = t.sp * t.cl + t.cp * t.sl;  // e^{i (phi + lam)}
+    Q3Mat m;
+    m.r[0] = t.c; m.i[0] = 0.0;
+    const double u01r = -t.s * t.cl, u01i = -t.s * t.sl, u10r = t.s * t.cp, u10i = t.s * t.sp;
+    if (MODE == 0) {
+        m.r[1] = u01r; m.i[1] = u01i; m.r[2] = u10r; m.i[2] = u10i; m.r[3] = t.c * epr; m.i[3] = t.c * epi;
+    } else if (MODE == 1) {
+        m.r[1] = u10r; m.i[1] = -u10i; m.r[2] = u01r; m.i[2] = -u01i; m.r[3] = t.c * epr; m.i[3] = -(t.c * epi);
+    } else {
+        m.r[1] = u10r; m.i[1] = u10i; m.r[2] = u01r; m.i[2] = u01i; m.r[3] = t.c * epr; m.i[3] = t.c * epi;
+    }
+    return m;
+}
+// row mixing by a 2x2 on qubit q: (vr, vi) = this lane's entry, (wr, wi) = the partner's, bit = bit q of the lane's row
+__device__ __forceinline__ void q3_mix2(const Q3Mat& m, bool bit, double& vr, double& vi, double wr, double wi) {
+    const double ar = bit ? m.r[3] : m.r[0], ai = bit ? m.i[3] : m.i[0];
+    const double br = bit ? m.r[2] : m.r[1], bi = bit ? m.i[2] : m.i[1];
+    const double nr = fma(ar, vr, fma(-ai, vi, fma(br, wr, -(bi * wi))));
+    const double ni = fma(ar, vi, fma(ai, vr, fma(br, wi, bi * wr)));
+    vr = nr;
+    vi = ni;
+}
+// row mixing by the 4x4 of position `tab` on the edge (a, b); idx = bit a | bit b << 1 of the lane's row.
+// mode 0: G; 1: G^+; 2: G^T
+template <int MODE>
+__device__ __forceinline__ void q3_mix4(const double2* tab, int a, int b, int idx, double& vr, double& vi) {
+    double sr[4], si[4];
+    sr[0] = vr; si[0] = vi;
+    sr[1] = q3_xchg(vr, a); si[1] = q3_xchg(vi, a);
+    sr[2] = q3_xchg(vr, b); si[2] = q3_xchg(vi, b);
+    sr[3] = q3_xchg(sr[1], b); si[3] = q3_xchg(si[1], b);
+    double nr = 0.0, ni = 0.0;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const double2 e = tab[(MODE == 0 ? idx : (idx ^ m)) * 4 + m];
+        const double ei = MODE == 1 ? -e.y : e.y;
+        nr = fma(e.x, sr[m], fma(-ei, si[m], nr));
+        ni = fma(e.x, si[m], fma(ei, sr[m], ni));
+    }
+    vr = nr;
+    vi = ni;
+}
+
+// E_j[i][m] = G_j[i][i ^ m] of every position into LDS (once per launch); the caller fences
+__device__ __forceinline__ void q3_load_gates(double* lds, const double* gates, int k) {
+    double2* tab = reinterpret_cast<double2*>(lds + kQ3OffGate);
+    for (int e = threadIdx.x; e < 16 * k; e += kWave) {
+        const int pos = e >> 4, i = (e >> 2) & 3, m = e & 3;
+        tab[e] = *reinterpret_cast<const double2*>(gates + 32 * pos + (i * 4 + (i ^ m)) * 2);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Fused loss + gradient of one item by the whole wavefront.  In: the trial point in lds[kQ3OffX ..], this lane's target entry
+// T[r][c], the gate tables in LDS.  Out: the loss (wave-uniform), the gradient in lds[kQ3OffG ..], this lane's entry of W.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <bool HUGE_ARGS>
+__device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, int k, uint64_t edges, int cost_kind, double& wre, double& wim) {
+    const int lane = threadIdx.x;
+    const int n = 9 + 6 * k;
+    const double2* tbl = reinterpret_cast<const double2*>(lds + kQ3OffTbl);
+    const double* xs = lds + kQ3OffX;
+    double* gs = lds + kQ3OffG;
+    double2* trig = reinterpret_cast<double2*>(lds + kQ3OffTrig);
+    const double2* gtab = reinterpret_cast<const double2*>(lds + kQ3OffGate);
+    // ---- 1. trig entries: lane l handles parameters 2 l and 2 l + 1
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = 2 * lane + h;
+        if (i < n) {
+            const double xv = xs[i];
+            const double arg = (i % 3 == 0) ? 0.5 * xv : xv;
+            double s, co;
+            if constexpr (HUGE_ARGS) sincos_any(arg, tbl, s, co);
+            else sincos_tbl(arg, tbl, s, co);
+            trig[i] = make_double2(co, s);
+        }
+    }
+    lds_fence();
+    // ---- 2. forward: P = M_L ... M_1
+    double pr = ((lane & 7) == (lane >> 3)) ? 1.0 : 0.0, pi = 0.0;
+    auto u3_fwd = [&](int base, int q) {
+        const Q3Mat m = q3_u3_mat<0>(load_u3(reinterpret_cast<const double*>(trig), base));
+        q3_mix2(m, (lane >> q) & 1, pr, pi, q3_xchg(pr, q), q3_xchg(pi, q));
+    };
+    u3_fwd(0, 0);
+    u3_fwd(3, 1);
+    u3_fwd(6, 2);
+#pragma unroll 1
+    for (int j = 0; j < k; ++j) {
+        const int a = (int)(edges >> (4 * j)) & 3, b = (int)(edges >> (4 * j + 2)) & 3;
+        q3_mix4<0>(gtab + 16 * j, a, b, ((lane >> a) & 1) | (((lane >> b) & 1) << 1), pr, pi);
+        u3_fwd(9 + 6 * j, a);
+        u3_fwd(12 + 6 * j, b);
+    }
+    wre = pr;
+    wim = pi;
+    // ---- 3. t = Tr(T^+ W), the loss and its seed z: d loss = Re(z dt)
+    const double tr = wave_sum(fma(tre, pr, tim * pi));
+    const double ti = wave_sum(fma(tre, pi, -(tim * pr)));
+    const double at2 = tr * tr + ti * ti;
+    const double rat = (at2 > 1e-300) ? fast_rsqrt(at2) : 0.0;
+    const double at = at2 * rat;
+    const double basic = 1.0 - 0.125 * at;  // BasicCost, cost_function.py:140-145
+    const bool sq = (cost_kind == 1);       // SquareCost = 8/9 (2 L - L^2) of BasicCost L at d = 8 (cost_function.py:169-173)
+    const double c0 = sq ? 16.0 / 9.0 : 1.0, c1 = sq ? -8.0 / 9.0 : 0.0, d1 = sq ? -16.0 / 9.0 : 0.0;
+    const double fout = basic * fma(c1, basic, c0);
+    const double inv = (0.125 * rat) * fma(d1, basic, c0);
+    const double zr = -tr * inv, zi = ti * inv;
+    // B^T = z conj(T)
+    double br = zr * tre + zi * tim, bi = zi * tre - zr * tim;
+    // ---- 4. backward: every factor undone on P and carried (transposed) through B^T, its derivatives on the way
+    auto u3_bwd = [&](int base, int q) {
+        const U3t t = load_u3(reinterpret_cast<const double*>(trig), base);
+        const bool bit = (lane >> q) & 1;
+        const double pbr = q3_xchg(br, q), pbi = q3_xchg(bi, q);
+        const double oi = fma(pr, bi, pi * br);                                 // Im(P B^T), own entries
+        const double xr = fma(pr, pbr, -(pi * pbi)), xi = fma(pr, pbi, pi * pbr);  // P (B^T of the partner row)
+        double gph = bit ? -oi : 0.0;
+        double gth = bit ? -0.5 * fma(t.cp, xr, t.sp * xi) : 0.5 * fma(t.cp, xr, -(t.sp * xi));
+        const Q3Mat mi = q3_u3_mat<1>(t), mt = q3_u3_mat<2>(t);
+        q3_mix2(mi, bit, pr, pi, q3_xchg(pr, q), q3_xchg(pi, q));
+        q3_mix2(mt, bit, br, bi, pbr, pbi);
+        double gla = bit ? -fma(pr, bi, pi * br) : 0.0;
+        gth = wave_sum(gth);
+        gph = wave_sum(gph);
+        gla = wave_sum(gla);
+        if (lane == 0) {
+            gs[base] = gth;
+            gs[base + 1] = gph;
+            gs[base + 2] = gla;
+        }
+    };
+#pragma unroll 1
+    for (int j = k - 1; j >= 0; --j) {
+        const int a = (int)(edges >> (4 * j)) & 3, b = (int)(edges >> (4 * j + 2)) & 3;
+        u3_bwd(12 + 6 * j, b);
+        u3_bwd(9 + 6 * j, a);
+        const int idx = ((lane >> a) & 1) | (((lane >> b) & 1) << 1);
+        q3_mix4<1>(gtab + 16 * j, a, b, idx, pr, pi);
+        q3_mix4<2>(gtab + 16 * j, a, b, idx, br, bi);
+    }
+    u3_bwd(6, 2);
+    u3_bwd(3, 1);
+    u3_bwd(0, 0);
+    lds_fence();
+    return fout;
+}
+
+// the wavefront's LDS prologue
+__device__ __forceinline__ void q3_prologue(double* lds, const double* gates, int k) {
+    load_sincos_table(reinterpret_cast<double2*>(lds + kQ3OffTbl), threadIdx.x);
+    q3_load_gates(lds, gates, k);
+    lds_fence();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// slam_q3_eval: one item per wavefront, grid-stride
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kWave, 4) eval_q3_kernel(Q3EvalArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = threadIdx.x;
+    const int n = 9 + 6 * a.k;
+    q3_prologue(lds, a.gates, a.k);
+    const int ent = ((lane & 7) * 8 + (lane >> 3)) * 2;  // entry (r, c) of a row-major 8x8
+    for (int64_t m = blockIdx.x; m < a.n_items; m += gridDim.x) {
+#pragma unroll
+        for (int s = 0; s < kQ3Slots; ++s) {
+            const int i = 2 * lane + s;
+            lds[kQ3OffX + i] = i < n ? a.x[m * n + i] : 0.0;
+        }
+        lds_fence();
+        const double2 t = *reinterpret_cast<const double2*>(a.targets + (int64_t)a.target_of[m] * 128 + ent);
+        double wr, wi;
+        const double f = eval_q3<true>(lds, t.x, t.y, a.k, a.edges, a.cost_kind, wr, wi);
+        if (lane == 0) a.loss[m] = f;
+        if (a.grad) {
+#pragma unroll
+            for (int s = 0; s < kQ3Slots; ++s) {
+                const int i = 2 * lane + s;
+                if (i < n) a.grad[m * n + i] = lds[kQ3OffG + i];
+            }
+        }
+        if (a.unitary) *reinterpret_cast<double2*>(a.unitary + m * 128 + ent) = make_double2(wr, wi);
+        lds_fence();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// slam_q3_minimize: the quasi-Newton iteration of slam_long_minimize.inc (its body, copied) around eval_q3
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(Q3Args args) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = threadIdx.x;
+    const int k = args.k;
+    const int n = 9 + 6 * k;
+    float* f32a = reinterpret_cast<float*>(lds + kQ3OffF32);  // [NP] broadcast vector of the mat-vec: g'
+    float* f32b = f32a + kQ3NP;                               // [NP] pending update: s
+    float* f32c = f32b + kQ3NP;                               // [NP] pending update: v
+    float2* const Hm = reinterpret_cast<float2*>(args.hmem + (size_t)blockIdx.x * (size_t)n * kQ3HStride) + lane;  // + j * 64: row j
+    q3_prologue(lds, args.gates, k);
+    const unsigned n_act = (unsigned)args.ctl->n_active;
+    const unsigned n_items = n_act * (unsigned)args.restarts;
+    const bool early = args.flags & 1u, ordered = args.flags & 2u;
+    const int ent = ((lane & 7) * 8 + (lane >> 3)) * 2;
+    unsigned rounds = 0;
+    bool valid[kQ3Slots];
+#pragma unroll
+    for (int s = 0; s < kQ3Slots; ++s) valid[s] = 2 * lane + s < n;  // (n may be odd: slot n stays zero everywhere)
+    const bool lane_in = 2 * lane < n;
+
+    while (true) {
+        unsigned pos = 0;
+        if (lane == 0) pos = atomicAdd(&args.ctl->work_counter, 1u);
+        pos = (unsigned)__builtin_amdgcn_readfirstlane((int)pos);
+        if (pos >= n_items) break;
+        const unsigned rs = pos / n_act;         // restart (restart-major queue: every target's restart r before any r + 1)
+        const unsigned sl = pos - rs * n_act;    // target
+        const unsigned item = sl * (unsigned)args.restarts + rs;
+        const int mine = args.restarts - (int)rs;
+        if (early) {
+            const int fl = __hip_atomic_load(&args.solved[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (ordered ? (fl > mine) : (fl != 0)) {  // a sibling restart has already succeeded (ordered: one with a lower index)
+                if (lane == 0) item_rec_store_dropped(args.item_rec + item, ST_PREEMPTED);
+#pragma unroll
+                for (int s = 0; s < kQ3Slots; ++s)
+                    if (valid[s]) args.item_x[(int64_t)item * n + 2 * lane + s] = 0.0;
+                continue;
+            }
+        }
+        const double2 tt = *reinterpret_cast<const double2*>(args.targets + (int64_t)sl * 128 + ent);
+        const double tre = tt.x, tim = tt.y;
+        double wre, wim;  // (the unitary is not wanted here)
+        double x[kQ3Slots], g[kQ3Slots], p[kQ3Slots];
+        {
+            // start point: explicit, or Philox block `lane` = the parameter pair (2 lane, 2 lane + 1)
+            double x0v[2] = {0.0, 0.0};
+            if (lane_in) {
+                if (args.x0) {
+#pragma unroll
+                    for (int s = 0; s < kQ3Slots; ++s)
+                        if (valid[s]) x0v[s] = args.x0[(int64_t)item * n + 2 * lane + s];
+                } else {
+                    uint32_t w[4];
+                    philox4x32_10((uint32_t)lane, rs, (uint32_t)((int)sl + (int)args.target_base), (uint32_t)k, (uint32_t)args.seed, (uint32_t)(args.seed >> 32), w);
+                    x0v[0] = x0_from_words(w[0], w[1]);
+                    x0v[1] = x0_from_words(w[2], w[3]);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < kQ3Slots; ++s) {
+                x[s] = valid[s] ? x0v[s] : 0.0;
+                lds[kQ3OffX + 2 * lane + s] = x[s];
+            }
+        }
+        lds_fence();
+        double f = eval_q3<false>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim);
+        ++rounds;
+        int nev = 1, nacc = 0, iters = 0, nback = 0, nstall = 0, status = ST_MAXITER;
+        bool ident = true, scaled = false;  // ident: H is the identity (nothing of it is in memory yet)
+        // The rank-2 update of an accepted step is applied by the NEXT step's mat-vec pass: pend = an update is waiting; its s and v in
+        // LDS (f32b, f32c), this lane's components of w and s in registers
+        bool pend = false;
+        float pw0 = 0.0f, pw1 = 0.0f, ps0 = 0.0f, ps1 = 0.0f;
+        double hs1 = 0.0, grow = 1.0;       // the effective metric is H + hs1 I (the one-off scaling of the initial metric)
+        double gnorm = 0.0, gp = 0.0, pp = 0.0, alpha = 0.0;
+        bool done = false;
+        if (!isfinite(f)) {
+            status = ST_NONFINITE;
+            done = true;
+        } else {
+            nacc = 1;
+            double gg = 0.0, gm = 0.0;
+#pragma unroll
+            for (int s = 0; s < kQ3Slots; ++s) {
+                g[s] = valid[s] ? lds[kQ3OffG + 2 * lane + s] : 0.0;
+                p[s] = -(double)(float)g[s];  // (the first direction is -H g with H = 1 in fp32)
+                gm = max_abs(gm, g[s]);
+            }
+#pragma unroll
+            for (int s = 0; s < kQ3Slots; ++s) gg = fma(g[s], p[s], gg);
+            gp = wave_sum(gg);
+            double d2 = 0.0;
+#pragma unroll
+            for (int s = 0; s < kQ3Slots; ++s) d2 = fma(p[s], p[s], d2);
+            pp = wave_sum(d2);
+            gnorm = wave_max_abs(gm);
+            alpha = (pp > 1e-300) ? fmin(grow, kStepMax * fast_rsqrt(pp)) : grow;
+            if (f < args.stop_loss || gnorm < args.gtol || (gnorm < args.gtol_far && f > args.far_loss)) { status = ST_CONVERGED; done = true; }
+            else if (args.maxiter <= 0) { status = ST_MAXITER; done = true; }
+        }
+        while (!done) {
+            // ---- trial point
+            double xt[kQ3Slots];
+#pragma unroll
+            for (int s = 0; s < kQ3Slots; ++s) {
+                xt[s] = fma(alpha, p[s], x[s]);
+                lds[kQ3OffX + 2 * lane + s] = xt[s];
+            }
+            lds_fence();
+            const double ft = eval_q3<false>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim);
+            ++rounds;
+            ++nev;
+            const bool finite = isfinite(ft);
+            const bool armijo = finite && (ft <= f + kArmijoC1 * alpha * gp);
+            if (armijo) {
+                ++nacc;
+                double gt[kQ3Slots], qv[kQ3Slots];
+                double pgt = 0.0, yy = 0.0, gm = 0.0;
+#pragma unroll
+                for (int s = 0; s < kQ3Slots; ++s) {
+                    gt[s] = valid[s] ? lds[kQ3OffG + 2 * lane + s] : 0.0;
+                    const double ya = gt[s] - g[s];
+                    pgt = fma(p[s], gt[s], pgt);
+                    yy = fma(ya, ya, yy);
+                    gm = max_abs(gm, gt[s]);
+                }
+                pgt = wave_sum(pgt);
+                yy = wave_sum(yy);
+                // ---- q = H g' (fp32), H = the matrix in memory (or the identity) + the pending update: one pass over the rows
+                if (ident && !pend) {
+#pragma unroll
+                    for (int s = 0; s < kQ3Slots; ++s) qv[s] = (double)(float)gt[s];
+                } else {
+                    f32a[2 * lane] = (float)gt[0];
+                    f32a[2 * lane + 1] = (float)gt[1];
+                    lds_fence();
+                    float a0 = 0.0f, a1 = 0.0f, b0 = 0.0f, b1 = 0.0f;  // two accumulator pairs: even / odd rows
+                    if (lane_in) {
+                        for (int j0 = 0; j0 < n; j0 += kQ3RowBatch) {
+                            float2 h[kQ3RowBatch];
+#pragma unroll
+                            for (int u = 0; u < kQ3RowBatch; ++u) {
+                                const int j = j0 + u;
+                                if (ident) h[u] = make_float2(j == 2 * lane ? 1.0f : 0.0f, (j == 2 * lane + 1 && valid[1]) ? 1.0f : 0.0f);
+                                else if (j < n) h[u] = Hm[(size_t)j * 64];
+                                else h[u] = make_float2(0.0f, 0.0f);
+                            }
+                            if (pend) {
+#pragma unroll
+                                for (int u = 0; u < kQ3RowBatch; ++u) {
+                                    const int j = j0 + u;
+                                    const float sj = f32b[j], vj = f32c[j];
+                                    h[u].x = fmaf(vj, ps0, h[u].x); h[u].y = fmaf(vj, ps1, h[u].y);
+                                    h[u].x = fmaf(sj, pw0, h[u].x); h[u].y = fmaf(sj, pw1, h[u].y);
+                                    if (j < n) Hm[(size_t)j * 64] = h[u];
+                                }
+                            }
+#pragma unroll
+                            for (int u = 0; u < kQ3RowBatch; u += 2) {
+                                const float g0 = f32a[j0 + u], g1 = f32a[j0 + u + 1];  // (rows beyond n: g' = 0 there; the vectors have kQ3NP entries)
+                                a0 = fmaf(h[u].x, g0, a0); a1 = fmaf(h[u].y, g0, a1);
+                                b0 = fmaf(h[u + 1].x, g1, b0); b1 = fmaf(h[u + 1].y, g1, b1);
+                            }
+                        }
+                    }
+                    if (pend) ident = false;  // the matrix is in memory now
+                    pend = false;
+                    qv[0] = (double)(a0 + b0);
+                    qv[1] = (double)(a1 + b1);
+                    lds_fence();
+                }
+                const double sg = alpha * pgt;
+                const double sy = alpha * (pgt - gp);
+                const double ss = (alpha * alpha) * pp;
+                const bool too_short = sy < (1.0 - kWolfeC2) * alpha * (-gp);  // weak-Wolfe curvature condition violated
+                const bool curv = !too_short && sy > 0.0 && (sy * sy > (kCurvEps * kCurvEps) * (ss * yy));
+                const bool first = curv && !scaled;
+                scaled = scaled || curv;
+                // first update of an item: scale the initial metric (the identity) by s.y / y.y -- as the scalar hs1
+                const double fac = first ? (sy * fast_rcp(yy)) : 1.0;
+                hs1 = first ? fac - 1.0 : hs1;
+                double yu = 0.0;
+#pragma unroll
+                for (int s = 0; s < kQ3Slots; ++s) {
+                    qv[s] = fma(hs1, gt[s], qv[s]);  // q = H_eff g'
+                    const double ua = fma(fac, p[s], qv[s]);  // u = H_eff y = q + fac p   (p = -H_eff g before this round's scaling)
+                    yu = fma(gt[s] - g[s], ua, yu);
+                }
+                yu = wave_sum(yu);
+                const double rho = curv ? fast_rcp(sy) : 0.0;
+                const double cf = rho * (1.0 + rho * yu);
+                double wg = 0.0;
+                double sa[kQ3Slots], wa[kQ3Slots], va[kQ3Slots];
+#pragma unroll
+                for (int s = 0; s < kQ3Slots; ++s) {
+                    sa[s] = alpha * p[s];
+                    const double ua = fma(fac, p[s], qv[s]);
+                    wa[s] = cf * sa[s] - rho * ua;
+                    va[s] = -rho * ua;
+                    wg = fma(wa[s], gt[s], wg);
+                }
+                wg = wave_sum(wg);
+                // ---- H += s w^T + v s^T (fp32; row j gets s_j w + v_j s): left pending for the next accepted step's pass
+                if (curv) {
+                    f32b[2 * lane] = (float)sa[0];
+                    f32b[2 * lane + 1] = (float)sa[1];
+                    f32c[2 * lane] = (float)va[0];
+                    f32c[2 * lane + 1] = (float)va[1];
+                    pw0 = (float)wa[0]; pw1 = (float)wa[1];
+                    ps0 = (float)sa[0]; ps1 = (float)sa[1];
+                    pend = true;
+                    lds_fence();
+                }
+                nstall = (f - ft <= kStallDf) ? nstall + 1 : 0;
+                f = ft;
+                ++iters;
+                nback = 0;
+                grow = too_short ? fmin(grow * kGrowFactor, kGrowMax) : 1.0;
+                double d1 = 0.0, d2 = 0.0;
+#pragma unroll
+                for (int s = 0; s < kQ3Slots; ++s) {
+                    x[s] = xt[s];
+                    g[s] = gt[s];
+                    p[s] = -(qv[s] + sa[s] * wg + va[s] * sg);
+                    d1 = fma(g[s], p[s], d1);
+                    d2 = fma(p[s], p[s], d2);
+                }
+                gnorm = wave_max_abs(gm);
+                gp = wave_sum(d1);
+                pp = wave_sum(d2);
+                alpha = (pp > 1e-300) ? fmin(grow, kStepMax * fast_rsqrt(pp)) : grow;
+                if (f < args.stop_loss || gnorm < args.gtol || (gnorm < args.gtol_far && f > args.far_loss)) { status = ST_CONVERGED; done = true; }
+                else if (nstall >= 2) { status = ST_STALLED; done = true; }
+                else if (iters >= args.maxiter) { status = ST_MAXITER; done = true; }
+                // not a descent direction (H lost positive definiteness numerically), or the periodic restart: steepest descent again
+                const bool periodic = !done && ((iters & (kRestartPeriod - 1)) == 0);
+                if (!done && (!(gp < 0.0) || periodic)) {
+                    ident = true;
+                    pend = false;
+                    hs1 = 0.0;
+                    scaled = periodic ? false : scaled;
+                    double gg = 0.0;
+#pragma unroll
+                    for (int s = 0; s < kQ3Slots; ++s) {
+                        p[s] = -g[s];
+                        gg = fma(g[s], g[s], gg);
+                    }
+                    gg = wave_sum(gg);
+                    gp = -gg;
+                    pp = gg;
+                    alpha = periodic ? ((gg > 1e-300) ? fmin(grow, kStepMax * fast_rsqrt(gg)) : grow) : alpha;
+                }
+            } else {
+                // safeguarded quadratic interpolation backtrack
+                const double denom = 2.0 * (ft - f - gp * alpha);
+                const double anew = (finite && denom > 0.0 && isfinite(denom)) ? (-gp * alpha * alpha * fast_rcp(denom)) : 0.5 * alpha;
+                alpha = fmin(fmax(anew, 0.1 * alpha), 0.5 * alpha);
+                grow = 1.0;
+                ++nback;
+                if (nback > kMaxBacktrack) { status = (gnorm < kStallGnorm) ? ST_STALLED : ST_LINESEARCH; done = true; }
+            }
+            // ---- early exit across the restarts of one target (optimizer.py:287-295)
+            if (early && !done) {
+                const int fl = __hip_atomic_load(&args.solved[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (ordered ? (fl > mine) : (fl != 0)) { status = ST_PREEMPTED; done = true; }
+            }
+        }
+        if (early && status != ST_PREEMPTED && f < args.exit_loss && lane == 0)
+            __hip_atomic_fetch_max(&args.solved[sl], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0) item_rec_store(args.item_rec + item, f, iters, status, nev, nacc);
+#pragma unroll
+        for (int s = 0; s < kQ3Slots; ++s)
+            if (valid[s]) args.item_x[(int64_t)item * n + 2 * lane + s] = x[s];
+    }
+    if (lane == 0 && rounds) atomicAdd(&args.ctl->rounds, (unsigned long long)rounds);
+}
+
+}  // namespace slamdev

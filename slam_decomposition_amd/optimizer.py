@@ -28,6 +28,7 @@ import numpy as np
 from . import _ffi, runtime
 from .basis import CircuitTemplate
 from .basisv2 import CircuitTemplateV2
+from .basis3q import ThreeQubitCircuitTemplate
 from .basis_abc import DataDictEntry, LazyList, RowBlocks, TargetDataList, VariationalTemplate
 from .cost_function import BasicCost, MakhlinFunctionalCost, SquareCost, UnitaryCostFunction
 from .sampler import SampleFunction
@@ -116,7 +117,20 @@ class TemplateOptimizer:
         assert not (self.preseeding and self.override_fail)
         assert not (self.preseeding and self.basis.n_qubits != 2)
 
-        if not isinstance(basis, (CircuitTemplate, CircuitTemplateV2)):
+        self._q3 = isinstance(basis, ThreeQubitCircuitTemplate)
+        if self._q3:
+            # three-qubit templates (basis3q.py): BasicCost / SquareCost through the device's quasi-Newton loop, one device, ordered restarts
+            if isinstance(objective, MakhlinFunctionalCost):
+                raise NotImplementedError("MakhlinFunctionalCost on a three-qubit template: Weyl chamber only for 2Q gates")
+            if use_callback:
+                raise NotImplementedError("use_callback is not implemented for three-qubit templates")
+            if override_method not in (None, "BFGS"):
+                raise NotImplementedError(f"override_method={override_method!r} is not implemented for three-qubit templates (BFGS on the device)")
+            if devices is not None and len(list(devices)) > 1:
+                raise NotImplementedError("devices: three-qubit templates run on one device")
+            if not deterministic:
+                raise NotImplementedError("deterministic=False is not implemented for three-qubit templates")
+        elif not isinstance(basis, (CircuitTemplate, CircuitTemplateV2)):
             raise NotImplementedError("the HIP optimizer needs a slam_decomposition_amd CircuitTemplate / CircuitTemplateV2")
         self._v2 = isinstance(basis, CircuitTemplateV2)
         if isinstance(self.objective, SquareCost):
@@ -824,6 +838,80 @@ class TemplateOptimizer:
             raise ValueError("empty spanning range")
         return np.array(best), best_x, np.array(best_k, dtype=np.int32)
 
+    # ------------------------------------------------------------------------------------------
+    # Three-qubit templates (basis3q.ThreeQubitCircuitTemplate, csrc/slam_q3.hpp)
+    def _run_batch_3q(self, targets: np.ndarray, spanning_range):
+        """``_run`` (optimizer.py:233-303) for 8x8 targets: the spans in order, each one device stage (``slam_q3_minimize``) over the
+        targets that are still open x ``training_restarts``; a target closes when its best loss drops below the threshold, the result
+        of a span is the lowest-index restart below it, otherwise the best seen is kept (optimizer.py:281-303).  Returns
+        (best_loss [N], list of parameter vectors, best_cycles [N]); ``span_best_losses[k]`` = the stage's best loss per target (NaN
+        where the target was closed already)."""
+        ks = [int(k) for k in spanning_range]
+        if not ks:
+            raise ValueError("empty spanning range")
+        basis = self.basis
+        for k in ks:
+            basis._check_span(k)
+        n = len(targets)
+        prm = self._opt_params()
+        ctx = runtime.get_context(self.devices[0])
+        best_loss = np.full(n, np.inf)
+        best_xs = [None] * n
+        best_cycles = np.full(n, -1, dtype=np.int64)
+        self.span_best_losses = {}
+        stats = {"kernel_ms": 0.0, "kernel_launches": 0, "evals": [0] * (_ffi.MAX_SPAN_EVAL + 1), "items": [0] * (_ffi.MAX_SPAN_EVAL + 1),
+                 "kernel_ms_span": [0.0] * (_ffi.MAX_SPAN_EVAL + 1)}
+        open_idx = np.arange(n)
+        for k in ks:
+            if len(open_idx) == 0:
+                break
+            # (the stage gets the open targets only: the Philox key holds a target's index within that list)
+            out = ctx.q3_minimize(basis.gate_matrices, basis.gate_sequence(k), basis.edge_sequence(k), targets[open_idx], prm,
+                                  self.success_threshold, cost_kind=self._cost_kind)
+            stage = np.full(n, np.nan)
+            stage[open_idx] = out["best_loss"]
+            self.span_best_losses[k] = stage
+            for j, i in enumerate(open_idx):
+                if best_xs[i] is None or out["best_loss"][j] < best_loss[i]:  # optimizer.py:281-284
+                    best_loss[i] = out["best_loss"][j]
+                    best_xs[i] = out["best_x"][j].copy()
+                    best_cycles[i] = k
+            stats["kernel_ms"] += out["kernel_ms"]
+            stats["kernel_launches"] += 1
+            stats["evals"][k] += int(out["item_evals"].sum())
+            stats["items"][k] += int(out["item_evals"].size)
+            stats["kernel_ms_span"][k] += out["kernel_ms"]
+            open_idx = open_idx[best_loss[open_idx] >= self.success_threshold]  # optimizer.py:301-303
+        stats["total_ms"] = stats["kernel_ms"]
+        self._set_stats([stats])
+        return best_loss, best_xs, best_cycles
+
+    def _approximate_batch_3q(self, stacked: np.ndarray, log_index: bool):
+        n = len(stacked)
+        self.basis.assign_seed(None)
+        spanning_range = list(self.basis.get_spanning_range(stacked[0]))
+        best_loss, best_xs, best_cycles = self._run_batch_3q(stacked, spanning_range)
+        self.basis.build(n_repetitions=int(best_cycles[-1]))  # the reference leaves the template at the last size
+        invariant = self.basis.target_invariant(stacked[0])  # (-1, -1, -1, -1): no Weyl chamber for 8x8 targets (basis_abc.py:80-84)
+        out = []
+        for i in range(n):
+            if log_index:
+                logging.info(f"Starting sample iter {i}")
+            logging.info(f"Begin search: {invariant}")
+            running = np.inf
+            for k in spanning_range:
+                v = self.span_best_losses[k][i] if k in self.span_best_losses else np.nan
+                if np.isnan(v):
+                    continue
+                running = min(running, float(v))
+                logging.info(f"Starting opt on template size {k}")
+                logging.info(f"Cycle (k ={k}), Best Loss={running}")
+                if running < self.success_threshold:
+                    logging.info(f"Break on cycle {k}")
+                    break
+            out.append(self._finish_target(invariant, float(best_loss[i]), best_xs[i], int(best_cycles[i]), invariant, index=i))
+        return out
+
     def _log_span_loop(self, i: int, spans) -> None:
         """The per-span log lines of ``_run`` (optimizer.py:234,297,302) for target i, from the running best loss
         the device recorded after every span."""
@@ -920,12 +1008,23 @@ class TemplateOptimizer:
     def approximate_target_U(self, target_U) -> DataDictEntry:
         """Atomic training function (optimizer.py:65-119)."""
         t = np.asarray(target_U, dtype=np.complex128)
+        if self._q3:
+            if t.shape != (8, 8):
+                raise ValueError("targets of a three-qubit template must be 8x8 unitaries")
+            return self._approximate_batch_3q(t[None], log_index=False)[0]
         if t.shape != (4, 4):
             raise ValueError("targets must be 4x4 unitaries")
         return self._approximate_batch(t[None], log_index=False)[0]
 
     def approximate_from_distribution(self, sampler: SampleFunction):
         """optimizer.py:180-186; all targets of the sampler are optimised as one GPU batch."""
+        if self._q3:
+            targets = [np.asarray(t, dtype=np.complex128) for t in sampler]
+            for t in targets:
+                if t.shape != (8, 8):
+                    raise ValueError("targets of a three-qubit template must be 8x8 unitaries")
+            target_data = self._approximate_batch_3q(np.stack(targets), log_index=True) if targets else []
+            return self.training_loss, self.coordinate_list, target_data
         self._device_sampler = sampler if hasattr(sampler, "fill") else None  # sampler.DeviceHaarBatch
         try:
             if self._device_sampler is not None:

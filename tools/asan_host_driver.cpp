@@ -263,6 +263,48 @@ int main() {
         EXPECT(slam_smush_minimize_stage_trace(nullptr, 1, i32, nullptr, 1, nullptr, d, d, nullptr, nullptr, &prm, 1e-10, 4, d, d, i32, d, i32, i32, d,
                                                d) == SLAM_ERR_INVALID);
     }
+    {  // slam_q3_eval, slam_q3_minimize: the template, the cost kind and the pointers are checked before the context
+        const int32_t gi[2] = {0, 0}, ed[4] = {0, 1, 1, 2}, bad_gi[2] = {0, 1}, bad_ed[4] = {0, 1, 2, 2}, far_ed[4] = {0, 3, 1, 2};
+        static double t8[128] = {0}, x3[21] = {0}, g3[21], u3[128];
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, ed, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 0, gi, ed, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3_eval(nullptr, d, 1, SLAM_Q3_MAX_SPAN + 1, gi, ed, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(std::strstr(slam_last_error(), "1..15") != nullptr);
+        EXPECT(slam_q3_eval(nullptr, nullptr, 1, 2, gi, ed, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, nullptr, ed, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, nullptr, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, bad_gi, ed, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "gate_index[1]") != nullptr);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, bad_ed, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "edges[1]") != nullptr);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, far_ed, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "edges[0]") != nullptr);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, ed, t8, 1, x3, i32, 1, SLAM_COST_MAKHLIN, d, g3, u3) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(std::strstr(slam_last_error(), "Weyl chamber only for 2Q gates") != nullptr);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, ed, t8, 1, x3, i32, 1, 7, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, ed, nullptr, 1, x3, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, ed, t8, 1, nullptr, i32, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, ed, t8, 1, x3, i32, 0, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID);
+        { const int32_t tof[1] = {1}; EXPECT(slam_q3_eval(nullptr, d, 1, 2, gi, ed, t8, 1, x3, tof, 1, SLAM_COST_BASIC, d, g3, u3) == SLAM_ERR_INVALID); }
+        EXPECT(std::strstr(slam_last_error(), "target_of[0]") != nullptr);
+        EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, t8, 1, SLAM_COST_SQUARE, &prm, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
+               SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_q3_minimize(nullptr, d, 1, 16, gi, ed, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
+               SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, bad_ed, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
+               SLAM_ERR_INVALID);
+        EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, t8, 1, SLAM_COST_MAKHLIN, &prm, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
+               SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, t8, 1, SLAM_COST_BASIC, nullptr, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
+               SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "params is NULL") != nullptr);
+        EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, nullptr, 1, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
+               SLAM_ERR_INVALID);
+        EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, t8, 0, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
+               SLAM_ERR_INVALID);
+    }
     EXPECT(slam_set_cost(nullptr, 0) == SLAM_ERR_INVALID);
     EXPECT(slam_synchronize(nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_get_stats(nullptr, &st) == SLAM_ERR_INVALID);
