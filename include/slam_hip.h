@@ -880,6 +880,33 @@ int slam_q3_minimize(slam_ctx* ctx, const double* gates, int32_t n_gates, int32_
                      int32_t* item_status, int32_t* item_evals, double* item_x, double* kernel_ms);
 
 /*
+ * Mixed templates: positions that hold a three-qubit gate (the reference's `circuit.append(gate, edge)` with an edge of three qubits,
+ * src/slam/basis.py:152-169; its CirculatorSNAILGate, VSwap, DeltaSwap, CCZGate, Peres ...).  A position of arity 3 on the ordered
+ * triple (a, b, c) -- all three qubits; gate-local bit 0 is qubit a, bit 1 is b, bit 2 is c -- is the gate, then a U3 on a, on b, on c;
+ * a position of arity 2 is as above.  n = 9 + 3 * sum(arity_j) parameters, in circuit order.  Caps: 1 <= k <= SLAM_Q3_MAX_SPAN,
+ * n <= 99 and n_gates3 <= SLAM_Q3_MAX_GATES3 distinct three-qubit gates (the kernel keeps one 1 KB table per distinct gate in LDS);
+ * beyond any of them: SLAM_ERR_UNSUPPORTED.
+ *   gates2      double[n_gates2][4][4][2]  the two-qubit gate table (n_gates2 may be 0, gates2 NULL then)
+ *   gates3      double[n_gates3][8][8][2]  the three-qubit gate table, basis index bit_a + 2 bit_b + 4 bit_c (n_gates3 may be 0)
+ *   arity       int32[k]                   2 or 3
+ *   gate_index  int32[k]                   the entry of position j in the table of its arity
+ *   qubits      int32[k][3]                (a_j, b_j, c_j): distinct qubits from {0, 1, 2}; c_j is ignored at arity 2
+ * Everything else is as in slam_q3_eval / slam_q3_minimize (the Philox key keeps k, the number of positions).  A template without a
+ * position of arity 3 runs the kernels of that pair and returns bit for bit what it returns; the mixed kernel instantiations
+ * run only when a position has arity 3.  Arguments are checked before the context and before anything touches
+ * the device.
+ */
+#define SLAM_Q3_MAX_GATES3 3
+int slam_q3m_eval(slam_ctx* ctx, const double* gates2, int32_t n_gates2, const double* gates3, int32_t n_gates3, int32_t k, const int32_t* arity,
+                  const int32_t* gate_index, const int32_t* qubits, const double* targets, int64_t n_targets, const double* x,
+                  const int32_t* target_of, int64_t M, int32_t cost_kind, double* loss, double* grad, double* unitary);
+int slam_q3m_minimize(slam_ctx* ctx, const double* gates2, int32_t n_gates2, const double* gates3, int32_t n_gates3, int32_t k,
+                      const int32_t* arity, const int32_t* gate_index, const int32_t* qubits, const double* targets, int64_t n_targets,
+                      int32_t cost_kind, const slam_opt_params* params, double exit_loss, const double* x0, double* best_loss, double* best_x,
+                      int32_t* best_restart, double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals, double* item_x,
+                      double* kernel_ms);
+
+/*
  * Multi-GPU: one process per GPU, RCCL over xGMI, reached through this ABI (no torch, no MPI).  The path shards by
  * target, every rank keeps all restarts of its targets, so the only exchange is the FINAL min-all-reduce of the
  * best-loss vector -- the running minimum of TemplateOptimizer._run (src/slam/optimizer.py:281-284) taken over the
@@ -957,7 +984,8 @@ const char* slam_version(void);
  *      later: slam_candidate_scores (a new symbol only);
  *      later: slam_sc_decompose and slam_sc_counts (new symbols only);
  *      later: slam_sqiswap_approx_decompose and slam_sqiswap_approx_counts (new symbols only);
- *      later: slam_q3_eval and slam_q3_minimize (new symbols only).
+ *      later: slam_q3_eval and slam_q3_minimize (new symbols only);
+ *      later: slam_q3m_eval and slam_q3m_minimize (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -112,6 +112,8 @@ EXPORTED_SYMBOLS = (
     "slam_region_lookup",
     "slam_q3_eval",
     "slam_q3_minimize",
+    "slam_q3m_eval",
+    "slam_q3m_minimize",
     "slam_set_cost",
     "slam_synchronize",
     "slam_host_alloc",
@@ -318,6 +320,10 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "slam_q3_eval"):
         lib.slam_q3_eval.argtypes = [P, P, C.c_int32, C.c_int32, P, P, P, C.c_int64, P, P, C.c_int64, C.c_int32, P, P, P]
         lib.slam_q3_minimize.argtypes = [P, P, C.c_int32, C.c_int32, P, P, P, C.c_int64, C.c_int32, C.POINTER(OptParams), C.c_double] + [P] * 10
+    if hasattr(lib, "slam_q3m_eval"):
+        lib.slam_q3m_eval.argtypes = [P, P, C.c_int32, P, C.c_int32, C.c_int32, P, P, P, P, C.c_int64, P, P, C.c_int64, C.c_int32, P, P, P]
+        lib.slam_q3m_minimize.argtypes = ([P, P, C.c_int32, P, C.c_int32, C.c_int32, P, P, P, P, C.c_int64, C.c_int32, C.POINTER(OptParams),
+                                           C.c_double] + [P] * 10)
     lib.slam_set_cost.argtypes = [P, C.c_int]
     lib.slam_synchronize.argtypes = [P]
     if hasattr(lib, "slam_host_alloc"):
@@ -1284,6 +1290,67 @@ class Context:
         ms = np.zeros(1, dtype=np.float64)
         _check(self._lib.slam_q3_minimize(self._h, _ptr(g), g.shape[0], k, _ptr(gi), _ptr(ed), _ptr(t), N, int(cost_kind), C.byref(params),
                                           float(exit_loss), _ptr(x0), *[_ptr(a) for a in out.values()], _ptr(ms)))
+        out["kernel_ms"] = float(ms[0])
+        return out
+
+    # -- mixed three-qubit templates (slam_q3m_*): positions of arity 2 or 3 -----------------------------------------------------
+    @staticmethod
+    def _q3m_template(gates2, gates3, arity, gate_index, qubits, targets):
+        g2 = np.ascontiguousarray(np.asarray(gates2, dtype=np.complex128))
+        g3 = np.ascontiguousarray(np.asarray(gates3, dtype=np.complex128))
+        if g2.ndim != 3 or g2.shape[1:] != (4, 4):
+            raise ValueError("gates2 must have shape [G2, 4, 4]")
+        if g3.ndim != 3 or g3.shape[1:] != (8, 8):
+            raise ValueError("gates3 must have shape [G3, 8, 8]")
+        ar = np.ascontiguousarray(arity, dtype=np.int32).reshape(-1)
+        gi = np.ascontiguousarray(gate_index, dtype=np.int32).reshape(-1)
+        qb = np.ascontiguousarray(qubits, dtype=np.int32)
+        if gi.shape != ar.shape or qb.shape != (len(ar), 3):
+            raise ValueError(f"gate_index must have shape [{len(ar)}], qubits [{len(ar)}, 3]")
+        t = np.ascontiguousarray(np.asarray(targets, dtype=np.complex128))
+        if t.ndim != 3 or t.shape[1:] != (8, 8):
+            raise ValueError(f"expected targets of shape [N, 8, 8], got {t.shape}")
+        n = 9 + 3 * int(ar.sum())
+        return (g2.view(np.float64).reshape(g2.shape + (2,)), g3.view(np.float64).reshape(g3.shape + (2,)), ar, gi, qb,
+                t.view(np.float64).reshape(t.shape + (2,)), n)
+
+    def q3m_eval(self, gates2, gates3, arity, gate_index, qubits, targets, x, target_of=None, cost_kind: int = 0, want_grad=True,
+                 want_unitary=False):
+        """``slam_q3m_eval``: as ``q3_eval`` for a template whose position j has ``arity[j]`` qubits, the gate ``gate_index[j]`` of the
+        table of that arity (gates2 [G2, 4, 4], gates3 [G3, 8, 8]) on ``qubits[j]`` = (a, b, c) (c ignored at arity 2);
+        n = 9 + 3 sum(arity)."""
+        g2, g3, ar, gi, qb, t, n = self._q3m_template(gates2, gates3, arity, gate_index, qubits, targets)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != n:
+            raise ValueError(f"x must have shape [M, {n}]")
+        M = x.shape[0]
+        tof = np.zeros(M, np.int32) if target_of is None else np.ascontiguousarray(target_of, dtype=np.int32)
+        if tof.shape != (M,):
+            raise ValueError("target_of must have shape [M]")
+        loss = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, n), dtype=np.float64) if want_grad else None
+        w = np.empty((M, 8, 8, 2), dtype=np.float64) if want_unitary else None
+        _check(self._lib.slam_q3m_eval(self._h, _ptr(g2), g2.shape[0], _ptr(g3), g3.shape[0], len(ar), _ptr(ar), _ptr(gi), _ptr(qb), _ptr(t),
+                                       t.shape[0], _ptr(x), _ptr(tof), M, int(cost_kind), _ptr(loss), _ptr(grad), _ptr(w)))
+        return loss, grad, (None if w is None else w.view(np.complex128).reshape(M, 8, 8))
+
+    def q3m_minimize(self, gates2, gates3, arity, gate_index, qubits, targets, params: OptParams, exit_loss: float, cost_kind: int = 0,
+                     x0=None) -> dict:
+        """``slam_q3m_minimize``: ``q3_minimize`` for the template description of ``q3m_eval``; the same keys."""
+        g2, g3, ar, gi, qb, t, n = self._q3m_template(gates2, gates3, arity, gate_index, qubits, targets)
+        N, R = t.shape[0], int(params.restarts)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (N, R, n):
+                raise ValueError(f"x0 must have shape [{N}, {R}, {n}]")
+        out = {"best_loss": np.empty(N, dtype=np.float64), "best_x": np.empty((N, n), dtype=np.float64),
+               "best_restart": np.empty(N, dtype=np.int32), "item_loss": np.empty((N, R), dtype=np.float64),
+               "item_iters": np.empty((N, R), dtype=np.int32), "item_status": np.empty((N, R), dtype=np.int32),
+               "item_evals": np.empty((N, R), dtype=np.int32), "item_x": np.empty((N, R, n), dtype=np.float64)}
+        ms = np.zeros(1, dtype=np.float64)
+        _check(self._lib.slam_q3m_minimize(self._h, _ptr(g2), g2.shape[0], _ptr(g3), g3.shape[0], len(ar), _ptr(ar), _ptr(gi), _ptr(qb),
+                                           _ptr(t), N, int(cost_kind), C.byref(params), float(exit_loss), _ptr(x0),
+                                           *[_ptr(a) for a in out.values()], _ptr(ms)))
         out["kernel_ms"] = float(ms[0])
         return out
 

@@ -43,7 +43,10 @@ class CircuitTemplate(VariationalTemplate):
         self.n_qubits = n_qubits
         self.no_exterior_1q = no_exterior_1q
         self.base_gates = list(base_gates)
-        self.gate_matrices = np.stack([gate_matrix(g) for g in self.base_gates])
+        mats = [gate_matrix(g) for g in self.base_gates]
+        if any(m.shape != (4, 4) for m in mats):
+            raise ValueError("a 2-qubit template takes 4x4 basis gates (three-qubit gates: ThreeQubitCircuitTemplate)")
+        self.gate_matrices = np.stack(mats)
         self.edge_params = edge_params
         self.device = device
         # compliant with the reference's optimizer (basis.py:77-80)

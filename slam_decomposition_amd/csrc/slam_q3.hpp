@@ -17,6 +17,18 @@
 //     the same stopping tests and status codes, the restart-major work queue with ordered early exit, Philox start points.
 // Loss, gradient, parameters, steps: fp64.
 //
+// Mixed templates (eval_q3_kernel<true>, minimize_q3_kernel<true>): a position may hold a three-qubit gate on the ordered triple
+// (a, b, c) -- gate-local bit 0 is qubit a, bit 1 is b, bit 2 is c -- followed by a U3 on a, on b, on c: n = 9 + 3 sum(arity_j) <= 99.
+//   * such a gate mixes all eight rows: the new entry is sum_m G[idx][idx ^ m] P[row ^ x(m)], idx = bit_a | bit_b << 1 | bit_c << 2 of
+//     the lane's row, x(m) = (m & 1) << a | (m >> 1 & 1) << b | (m >> 2) << c.  (a, b, c) is a permutation of (0, 1, 2), so x runs over
+//     all seven lane XORs: the partners come from ONE fixed chain of exchanges in Gray-code order of the LANE mask (XOR 1, 2, 1, 4, 1,
+//     2, 1: seven exchanges per real component, DPP and ds_swizzle, no LDS data traffic), and the edge enters through the table column
+//     m = x^-1(mask) only -- wave-uniform integer work, no branch on the qubit numbers;
+//   * the table E[i][m] = G[i][i ^ m] (64 double2 = 1 KB) is kept once per DISTINCT three-qubit gate (at most kQ3MaxGates3) behind the
+//     wavefront's other LDS and reached through the position's gate index; backward uses the modes of q3_mix4 (G, G^+ on P, G^T on B^T);
+//   * parameter offsets come from a running base (positions have 6 or 9 parameters).
+// The two-qubit-only kernels are the MIXED = false instantiations of the same bodies: nothing of the above is compiled into them.
+//
 // Reference behaviour: CircuitTemplate(n_qubits, edge_params) src/slam/basis.py:52-169; BasicCost / SquareCost
 // src/slam/cost_function.py:140-145,169-173; the restart loop src/slam/optimizer.py:253-295.
 #pragma once
@@ -41,6 +53,12 @@ constexpr int kQ3OffF32 = kQ3OffGate + 32 * kQ3MaxSpan;     // three fp32 vector
 constexpr int kQ3LdsDoubles = kQ3OffF32 + 3 * kQ3NP / 2;
 constexpr size_t kQ3LdsBytes = (size_t)kQ3LdsDoubles * sizeof(double);
 static_assert(16 * kQ3LdsBytes <= 160 * 1024, "four wavefronts per SIMD need sixteen wavefronts' LDS per CU");
+// mixed templates: the tables of the distinct three-qubit gates behind everything else, E_g[i][m] = G_g[i][i ^ m]: [g][64] double2
+constexpr int kQ3MaxGates3 = 3;
+constexpr int kQ3OffGate3 = kQ3LdsDoubles;
+constexpr int kQ3MLdsDoubles = kQ3OffGate3 + 128 * kQ3MaxGates3;
+constexpr size_t kQ3MLdsBytes = (size_t)kQ3MLdsDoubles * sizeof(double);
+static_assert(12 * kQ3MLdsBytes <= 160 * 1024, "minimize_q3_kernel<true>: three wavefronts per SIMD need twelve wavefronts' LDS per CU");
 
 struct Q3Args {
     const double* targets;    // [n_active][8][8][2]
@@ -74,6 +92,20 @@ struct Q3EvalArgs {
     const double* gates;
     uint64_t edges;
     int32_t k;
+};
+
+// mixed templates: what the two-qubit structures do not carry
+struct Q3MArgs : Q3Args {
+    const double* gates3;     // [n_gates3][8][8][2]: the distinct three-qubit gates
+    uint64_t ext;             // position j: bits 4 j, 4 j + 1 = qubit c (3: a two-qubit position); bits 4 j + 2, 4 j + 3 = its entry of gates3
+    int32_t n_gates3;
+    int32_t n;                // 9 + 3 sum(arity)
+};
+struct Q3MEvalArgs : Q3EvalArgs {
+    const double* gates3;
+    uint64_t ext;
+    int32_t n_gates3;
+    int32_t n;
 };
 
 // the value of lane (l ^ (1 << q)), q wave-uniform
@@ -144,14 +176,48 @@ __device__ __forceinline__ void q3_load_gates(double* lds, const double* gates, 
     }
 }
 
+// row mixing by the 8x8 whose table is `tab` on the triple (a, b, c); idx = bit a | bit b << 1 | bit c << 2 of the lane's row.
+// The running value walks the lane masks 0, 1, 3, 2, 6, 7, 5, 4; mask x pairs with the gate-local m = x^-1(mask).  Modes as q3_mix4.
+template <int MODE>
+__device__ __forceinline__ void q3_mix8(const double2* tab, int a, int b, int c, int idx, double& vr, double& vi) {
+    double cr = vr, ci = vi, nr = 0.0, ni = 0.0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int x = t ^ (t >> 1);  // Gray code: the lane mask of step t
+        const int m = ((x >> a) & 1) | (((x >> b) & 1) << 1) | (((x >> c) & 1) << 2);
+        const double2 e = tab[(MODE == 0 ? idx : (idx ^ m)) * 8 + m];
+        const double ei = MODE == 1 ? -e.y : e.y;
+        nr = fma(e.x, cr, fma(-ei, ci, nr));
+        ni = fma(e.x, ci, fma(ei, cr, ni));
+        if (t < 7) {
+            const int q = (t & 1) == 0 ? 0 : (t == 3 ? 2 : 1);  // the bit in which the masks of steps t and t + 1 differ
+            cr = q3_xchg(cr, q);
+            ci = q3_xchg(ci, q);
+        }
+    }
+    vr = nr;
+    vi = ni;
+}
+// E_g[i][m] = G_g[i][i ^ m] of every distinct three-qubit gate into LDS (once per launch); the caller fences
+__device__ __forceinline__ void q3_load_gates3(double* lds, const double* gates3, int n_gates3) {
+    double2* tab = reinterpret_cast<double2*>(lds + kQ3OffGate3);
+    for (int e = threadIdx.x; e < 64 * n_gates3; e += kWave) {
+        const int g = e >> 6, i = (e >> 3) & 7, m = e & 7;
+        tab[e] = *reinterpret_cast<const double2*>(gates3 + 128 * g + (i * 8 + (i ^ m)) * 2);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Fused loss + gradient of one item by the whole wavefront.  In: the trial point in lds[kQ3OffX ..], this lane's target entry
 // T[r][c], the gate tables in LDS.  Out: the loss (wave-uniform), the gradient in lds[kQ3OffG ..], this lane's entry of W.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <bool HUGE_ARGS>
-__device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, int k, uint64_t edges, int cost_kind, double& wre, double& wim) {
+// MIXED: `ext` and `n_mixed` are Q3MArgs' ext and n.
+template <bool HUGE_ARGS, bool MIXED = false>
+__device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, int k, uint64_t edges, int cost_kind, double& wre, double& wim,
+                                          uint64_t ext = 0, int n_mixed = 0) {
     const int lane = threadIdx.x;
-    const int n = 9 + 6 * k;
+    const int n = MIXED ? n_mixed : 9 + 6 * k;
+    const double2* gtab3 = reinterpret_cast<const double2*>(lds + kQ3OffGate3);
     const double2* tbl = reinterpret_cast<const double2*>(lds + kQ3OffTbl);
     const double* xs = lds + kQ3OffX;
     double* gs = lds + kQ3OffG;
@@ -180,12 +246,30 @@ __device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, i
     u3_fwd(0, 0);
     u3_fwd(3, 1);
     u3_fwd(6, 2);
+    int base = 9;  // (MIXED only: the first parameter of the position's U3s)
 #pragma unroll 1
     for (int j = 0; j < k; ++j) {
         const int a = (int)(edges >> (4 * j)) & 3, b = (int)(edges >> (4 * j + 2)) & 3;
-        q3_mix4<0>(gtab + 16 * j, a, b, ((lane >> a) & 1) | (((lane >> b) & 1) << 1), pr, pi);
-        u3_fwd(9 + 6 * j, a);
-        u3_fwd(12 + 6 * j, b);
+        if constexpr (MIXED) {
+            const int c = (int)(ext >> (4 * j)) & 3;
+            if (c != 3) {
+                const int idx = ((lane >> a) & 1) | (((lane >> b) & 1) << 1) | (((lane >> c) & 1) << 2);
+                q3_mix8<0>(gtab3 + 64 * ((int)(ext >> (4 * j + 2)) & 3), a, b, c, idx, pr, pi);
+                u3_fwd(base, a);
+                u3_fwd(base + 3, b);
+                u3_fwd(base + 6, c);
+                base += 9;
+            } else {
+                q3_mix4<0>(gtab + 16 * j, a, b, ((lane >> a) & 1) | (((lane >> b) & 1) << 1), pr, pi);
+                u3_fwd(base, a);
+                u3_fwd(base + 3, b);
+                base += 6;
+            }
+        } else {
+            q3_mix4<0>(gtab + 16 * j, a, b, ((lane >> a) & 1) | (((lane >> b) & 1) << 1), pr, pi);
+            u3_fwd(9 + 6 * j, a);
+            u3_fwd(12 + 6 * j, b);
+        }
     }
     wre = pr;
     wim = pi;
@@ -228,11 +312,32 @@ __device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, i
 #pragma unroll 1
     for (int j = k - 1; j >= 0; --j) {
         const int a = (int)(edges >> (4 * j)) & 3, b = (int)(edges >> (4 * j + 2)) & 3;
-        u3_bwd(12 + 6 * j, b);
-        u3_bwd(9 + 6 * j, a);
-        const int idx = ((lane >> a) & 1) | (((lane >> b) & 1) << 1);
-        q3_mix4<1>(gtab + 16 * j, a, b, idx, pr, pi);
-        q3_mix4<2>(gtab + 16 * j, a, b, idx, br, bi);
+        if constexpr (MIXED) {
+            const int c = (int)(ext >> (4 * j)) & 3;
+            if (c != 3) {
+                base -= 9;
+                u3_bwd(base + 6, c);
+                u3_bwd(base + 3, b);
+                u3_bwd(base, a);
+                const int idx = ((lane >> a) & 1) | (((lane >> b) & 1) << 1) | (((lane >> c) & 1) << 2);
+                const double2* tab = gtab3 + 64 * ((int)(ext >> (4 * j + 2)) & 3);
+                q3_mix8<1>(tab, a, b, c, idx, pr, pi);
+                q3_mix8<2>(tab, a, b, c, idx, br, bi);
+            } else {
+                base -= 6;
+                u3_bwd(base + 3, b);
+                u3_bwd(base, a);
+                const int idx = ((lane >> a) & 1) | (((lane >> b) & 1) << 1);
+                q3_mix4<1>(gtab + 16 * j, a, b, idx, pr, pi);
+                q3_mix4<2>(gtab + 16 * j, a, b, idx, br, bi);
+            }
+        } else {
+            u3_bwd(12 + 6 * j, b);
+            u3_bwd(9 + 6 * j, a);
+            const int idx = ((lane >> a) & 1) | (((lane >> b) & 1) << 1);
+            q3_mix4<1>(gtab + 16 * j, a, b, idx, pr, pi);
+            q3_mix4<2>(gtab + 16 * j, a, b, idx, br, bi);
+        }
     }
     u3_bwd(6, 2);
     u3_bwd(3, 1);
@@ -242,20 +347,29 @@ __device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, i
 }
 
 // the wavefront's LDS prologue
-__device__ __forceinline__ void q3_prologue(double* lds, const double* gates, int k) {
+template <bool MIXED, class Args>
+__device__ __forceinline__ void q3_prologue(double* lds, const Args& a) {
     load_sincos_table(reinterpret_cast<double2*>(lds + kQ3OffTbl), threadIdx.x);
-    q3_load_gates(lds, gates, k);
+    q3_load_gates(lds, a.gates, a.k);
+    if constexpr (MIXED) q3_load_gates3(lds, a.gates3, a.n_gates3);
     lds_fence();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// slam_q3_eval: one item per wavefront, grid-stride
+// slam_q3_eval / slam_q3m_eval: one item per wavefront, grid-stride
 // ---------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kWave, 4) eval_q3_kernel(Q3EvalArgs a) {
+// (MIXED: LDS lets twelve of these wavefronts onto a CU, not sixteen -- see kQ3MLdsBytes)
+template <bool MIXED>
+__global__ void __launch_bounds__(kWave, 4) eval_q3_kernel(std::conditional_t<MIXED, Q3MEvalArgs, Q3EvalArgs> a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x;
-    const int n = 9 + 6 * a.k;
-    q3_prologue(lds, a.gates, a.k);
+    int n = 9 + 6 * a.k;
+    uint64_t ext = 0;
+    if constexpr (MIXED) {
+        n = a.n;
+        ext = a.ext;
+    }
+    q3_prologue<MIXED>(lds, a);
     const int ent = ((lane & 7) * 8 + (lane >> 3)) * 2;  // entry (r, c) of a row-major 8x8
     for (int64_t m = blockIdx.x; m < a.n_items; m += gridDim.x) {
 #pragma unroll
@@ -266,7 +380,7 @@ __global__ void __launch_bounds__(kWave, 4) eval_q3_kernel(Q3EvalArgs a) {
         lds_fence();
         const double2 t = *reinterpret_cast<const double2*>(a.targets + (int64_t)a.target_of[m] * 128 + ent);
         double wr, wi;
-        const double f = eval_q3<true>(lds, t.x, t.y, a.k, a.edges, a.cost_kind, wr, wi);
+        const double f = eval_q3<true, MIXED>(lds, t.x, t.y, a.k, a.edges, a.cost_kind, wr, wi, ext, n);
         if (lane == 0) a.loss[m] = f;
         if (a.grad) {
 #pragma unroll
@@ -281,18 +395,25 @@ __global__ void __launch_bounds__(kWave, 4) eval_q3_kernel(Q3EvalArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// slam_q3_minimize: the quasi-Newton iteration of slam_long_minimize.inc (its body, copied) around eval_q3
+// slam_q3_minimize: the quasi-Newton iteration of slam_long_minimize.inc (its body, copied) around eval_q3; one body, instantiated for
+// the two-qubit-only templates (MIXED = false) and the mixed ones
 // ---------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(Q3Args args) {
+template <bool MIXED>
+__global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(std::conditional_t<MIXED, Q3MArgs, Q3Args> args) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x;
     const int k = args.k;
-    const int n = 9 + 6 * k;
+    int n = 9 + 6 * k;
+    uint64_t ext = 0;
+    if constexpr (MIXED) {
+        n = args.n;
+        ext = args.ext;
+    }
     float* f32a = reinterpret_cast<float*>(lds + kQ3OffF32);  // [NP] broadcast vector of the mat-vec: g'
     float* f32b = f32a + kQ3NP;                               // [NP] pending update: s
     float* f32c = f32b + kQ3NP;                               // [NP] pending update: v
     float2* const Hm = reinterpret_cast<float2*>(args.hmem + (size_t)blockIdx.x * (size_t)n * kQ3HStride) + lane;  // + j * 64: row j
-    q3_prologue(lds, args.gates, k);
+    q3_prologue<MIXED>(lds, args);
     const unsigned n_act = (unsigned)args.ctl->n_active;
     const unsigned n_items = n_act * (unsigned)args.restarts;
     const bool early = args.flags & 1u, ordered = args.flags & 2u;
@@ -348,7 +469,7 @@ __global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(Q3Args args) {
             }
         }
         lds_fence();
-        double f = eval_q3<false>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim);
+        double f = eval_q3<false, MIXED>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim, ext, n);
         ++rounds;
         int nev = 1, nacc = 0, iters = 0, nback = 0, nstall = 0, status = ST_MAXITER;
         bool ident = true, scaled = false;  // ident: H is the identity (nothing of it is in memory yet)
@@ -392,7 +513,7 @@ __global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(Q3Args args) {
                 lds[kQ3OffX + 2 * lane + s] = xt[s];
             }
             lds_fence();
-            const double ft = eval_q3<false>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim);
+            const double ft = eval_q3<false, MIXED>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim, ext, n);
             ++rounds;
             ++nev;
             const bool finite = isfinite(ft);

@@ -248,13 +248,180 @@ class ConversionGainSmushGate(Gate2Q):
         return smush_matrix(pc, pg, gc, gg, self.gx, self.gy, float(self.params[-1]))
 
 
+# ---- three-qubit gates (basis3q.ThreeQubitCircuitTemplate only) ----------------------------------------------------------------
+class Gate3Q(Gate2Q):
+    """Sibling of ``Gate2Q`` for three qubits: ``to_matrix()`` is 8x8 complex128, qiskit little-endian -- basis index
+    q0 + 2 q1 + 4 q2 of the gate's own three qubits.  ``U|j> = |pi(j)>`` below means the permutation matrix with U[pi(j), j] = 1."""
+
+    num_qubits = 3
+
+
+def _permutation8(pi: Sequence[int]) -> np.ndarray:
+    m = np.zeros((8, 8), dtype=np.complex128)
+    for j, pj in enumerate(pi):
+        m[pj, j] = 1.0
+    return m
+
+
+def _swapped(*pairs) -> list:
+    pi = list(range(8))
+    for i, j in pairs:
+        pi[i], pi[j] = j, i
+    return pi
+
+
+class _FixedGate3Q(Gate3Q):
+    NAME = ""
+
+    def __init__(self):
+        super().__init__(self.NAME, [])
+
+
+class CCZGate(_FixedGate3Q):
+    """-1 on |7>."""
+
+    NAME = "ccz"
+
+    def _matrix(self):
+        m = np.eye(8, dtype=np.complex128)
+        m[7, 7] = -1.0
+        return m
+
+
+class CCXGate(_FixedGate3Q):
+    """Toffoli, controls q0 and q1, target q2: |3> <-> |7>."""
+
+    NAME = "ccx"
+
+    def _matrix(self):
+        return _permutation8(_swapped((3, 7)))
+
+
+class CSwapGate(_FixedGate3Q):
+    """Fredkin, control q0, swaps q1 and q2: |3> <-> |5>."""
+
+    NAME = "cswap"
+
+    def _matrix(self):
+        return _permutation8(_swapped((3, 5)))
+
+
+def _ix_on_pair(i: int, j: int) -> np.ndarray:
+    m = np.eye(8, dtype=np.complex128)
+    m[i, i] = m[j, j] = 0.0
+    m[i, j] = m[j, i] = 1j
+    return m
+
+
+class CCiXGate(_FixedGate3Q):
+    """i X on the pair {|6>, |7>} (custom_gates.py:316-486 holds the reference's fixed three-qubit gates)."""
+
+    NAME = "ccix"
+
+    def _matrix(self):
+        return _ix_on_pair(6, 7)
+
+
+class CiSwap(_FixedGate3Q):
+    """i X on the pair {|5>, |6>}: the iSWAP of q0 and q1 while q2 = 1."""
+
+    NAME = "ciswap"
+
+    def _matrix(self):
+        return _ix_on_pair(5, 6)
+
+
+class Peres(_FixedGate3Q):
+    """As the reference has it: for q2 = 1, X on q0 and on q1 -- |4> <-> |7>, |5> <-> |6>."""
+
+    NAME = "peres"
+
+    def _matrix(self):
+        return _permutation8(_swapped((4, 7), (5, 6)))
+
+
+class Margolus(_FixedGate3Q):
+    """-1 on |5>, |6> <-> |7>."""
+
+    NAME = "margolus"
+
+    def _matrix(self):
+        m = _permutation8(_swapped((6, 7)))
+        m[5, 5] = -1.0
+        return m
+
+
+class CParitySwap(_FixedGate3Q):
+    """Two 3-cycles of basis states: 1 -> 2 -> 4 -> 1 and 3 -> 5 -> 6 -> 3."""
+
+    NAME = "cpswap"
+
+    def _matrix(self):
+        pi = list(range(8))
+        for cyc in ((1, 2, 4), (3, 5, 6)):
+            for i in range(3):
+                pi[cyc[i]] = cyc[(i + 1) % 3]
+        return _permutation8(pi)
+
+
+def circulator_hamiltonian(p_ab: float, p_ac: float, p_bc: float, g_ab: float, g_ac: float, g_bc: float) -> np.ndarray:
+    """H = g_ab (e^{i p_ab} A B^+ + h.c.) + g_ac (e^{i p_ac} A C^+ + h.c.) + g_bc (e^{i p_bc} B C^+ + h.c.) with A, B, C the 2x2 raising
+    operator [[0, 0], [1, 0]] on the left, middle and right Kronecker factor: mode a is bit 2, mode c is bit 0 (the reference's
+    CirculatorHamiltonian, hamiltonian.py:244-272)."""
+    up = np.array([[0, 0], [1, 0]], dtype=np.complex128)
+    one = np.eye(2, dtype=np.complex128)
+    A = np.kron(up, np.kron(one, one))
+    B = np.kron(one, np.kron(up, one))
+    Cm = np.kron(one, np.kron(one, up))
+    h = np.zeros((8, 8), dtype=np.complex128)
+    for p, g, x, y in ((p_ab, g_ab, A, B), (p_ac, g_ac, A, Cm), (p_bc, g_bc, B, Cm)):
+        term = g * np.exp(1j * p) * (x @ y.conj().T)
+        h += term + term.conj().T
+    return h
+
+
+class CirculatorSNAILGate(Gate3Q):
+    """``CirculatorSNAILGate(p1, p2, p3, g1, g2, g3, t_el=1)`` = exp(-i t H), H = ``circulator_hamiltonian`` of the phases
+    (p_ab, p_ac, p_bc) and strengths (g_ab, g_ac, g_bc) (custom_gates.py:95-160).  Computed from ``numpy.linalg.eigh`` of the 8x8
+    Hermitian H."""
+
+    def __init__(self, p1, p2, p3, g1, g2, g3, t_el=1.0, name: str = "3QGate"):
+        super().__init__(name, [p1, p2, p3, g1, g2, g3, t_el])
+        self.duration = self.cost()
+
+    def cost(self) -> float:
+        """sum |g| * t / (pi / 2)"""
+        return sum(abs(float(g)) for g in self.params[3:6]) * float(self.params[6]) / (math.pi / 2)
+
+    def fidelity(self) -> float:
+        return max(1.0 - 0.001 * self.cost(), 0.0)
+
+    def _matrix(self):
+        w, v = np.linalg.eigh(circulator_hamiltonian(*(float(p) for p in self.params[:6])))
+        return (v * np.exp(-1j * float(self.params[6]) * w)) @ v.conj().T
+
+
+class VSwap(CirculatorSNAILGate):
+    def __init__(self, t_el=1.0):
+        v = 4.0 / math.sqrt(2.0)
+        super().__init__(math.pi / 2, math.pi / 2, 0.0, math.pi / v, math.pi / v, 0.0, t_el, name="vswap")
+
+
+class DeltaSwap(CirculatorSNAILGate):
+    def __init__(self, t_el=1.0):
+        v = 3.0 * math.sqrt(3.0) / 2.0
+        super().__init__(math.pi / 2, -math.pi / 2, math.pi / 2, math.pi / v, math.pi / v, math.pi / v, t_el, name="deltaswap")
+
+
 def gate_matrix(gate) -> np.ndarray:
-    """4x4 complex128 matrix of a gate object / array."""
+    """4x4 (two-qubit gate) or 8x8 (three-qubit gate) complex128 matrix of a gate object / array."""
     if hasattr(gate, "to_matrix"):
         m = gate.to_matrix()
     else:
         m = np.asarray(gate)
     m = np.asarray(m, dtype=np.complex128)
+    if m.shape == (8, 8):
+        return m
     if m.shape != (4, 4):
         raise ValueError(f"2Q basis gate must be a 4x4 matrix, got shape {m.shape}")
     return m

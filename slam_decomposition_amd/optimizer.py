@@ -851,7 +851,7 @@ class TemplateOptimizer:
             raise ValueError("empty spanning range")
         basis = self.basis
         for k in ks:
-            basis._check_span(k)
+            basis._check_size(k)
         n = len(targets)
         prm = self._opt_params()
         ctx = runtime.get_context(self.devices[0])
@@ -866,8 +866,12 @@ class TemplateOptimizer:
             if len(open_idx) == 0:
                 break
             # (the stage gets the open targets only: the Philox key holds a target's index within that list)
-            out = ctx.q3_minimize(basis.gate_matrices, basis.gate_sequence(k), basis.edge_sequence(k), targets[open_idx], prm,
-                                  self.success_threshold, cost_kind=self._cost_kind)
+            if basis.has_three_qubit_position(k):  # the mixed entry point only where a position needs it
+                out = ctx.q3m_minimize(basis.gate_matrices, basis.gate_matrices3, *basis.mixed_description(k), targets[open_idx], prm,
+                                       self.success_threshold, cost_kind=self._cost_kind)
+            else:
+                out = ctx.q3_minimize(basis.gate_matrices, basis.table_sequence(k), basis.edge_sequence(k), targets[open_idx], prm,
+                                      self.success_threshold, cost_kind=self._cost_kind)
             stage = np.full(n, np.nan)
             stage[open_idx] = out["best_loss"]
             self.span_best_losses[k] = stage

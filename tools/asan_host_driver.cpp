@@ -305,6 +305,53 @@ int main() {
         EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, t8, 0, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
                SLAM_ERR_INVALID);
     }
+    {  // slam_q3m_eval, slam_q3m_minimize: arities, qubits, table indices and the caps are checked before the context
+        const int32_t ar[2] = {3, 2}, gi[2] = {1, 0}, qb[6] = {0, 1, 2, 1, 2, 7}, bad_ar[2] = {3, 4}, bad_gi[2] = {2, 0}, bad_qb[6] = {0, 1, 1, 1, 2, 0};
+        static double g3m[SLAM_Q3_MAX_GATES3 + 1][128] = {{0}}, t8[128] = {0}, x3[24] = {0}, gr[24], u3[128];
+        const double* g3 = &g3m[0][0];
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 0, ar, gi, qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, SLAM_Q3_MAX_SPAN + 1, ar, gi, qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, SLAM_Q3_MAX_GATES3 + 1, 2, ar, gi, qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(std::strstr(slam_last_error(), "distinct three-qubit gates") != nullptr);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, bad_ar, gi, qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "arity[1]") != nullptr);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, ar, bad_gi, qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "gate_index[0]") != nullptr);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, ar, gi, bad_qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "qubits[0]") != nullptr);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, nullptr, 2, 2, ar, gi, qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, nullptr, gi, qb, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, ar, gi, nullptr, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, x3, i32, 1, SLAM_COST_MAKHLIN, d, gr, u3) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, nullptr, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3m_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, x3, i32, 0, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+        {  // eleven three-qubit positions: 108 parameters
+            int32_t ar11[11], gi11[11], qb11[33];
+            for (int j = 0; j < 11; ++j) { ar11[j] = 3; gi11[j] = 0; qb11[3 * j] = 2; qb11[3 * j + 1] = 0; qb11[3 * j + 2] = 1; }
+            EXPECT(slam_q3m_eval(nullptr, nullptr, 0, g3, 1, 11, ar11, gi11, qb11, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_UNSUPPORTED);
+            EXPECT(std::strstr(slam_last_error(), "108") != nullptr);
+            EXPECT(slam_q3m_eval(nullptr, nullptr, 0, g3, 1, 10, ar11, gi11, qb11, t8, 1, x3, i32, 1, SLAM_COST_BASIC, d, gr, u3) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        }
+        EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, SLAM_COST_SQUARE, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 16, ar, gi, qb, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, bad_ar, gi, qb, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, bad_qb, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, SLAM_COST_MAKHLIN, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, SLAM_COST_BASIC, nullptr, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "params is NULL") != nullptr);
+        EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 0, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_INVALID);
+    }
     EXPECT(slam_set_cost(nullptr, 0) == SLAM_ERR_INVALID);
     EXPECT(slam_synchronize(nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_get_stats(nullptr, &st) == SLAM_ERR_INVALID);
