@@ -865,7 +865,8 @@ int slam_smush_minimize_stage_trace(slam_ctx* ctx, int k, const int32_t* gate_se
  * item, restart-major queue, Philox start points keyed (pair, restart, target index + target_base, k) or explicit x0, ordered early
  * exit at exit_loss); the stage result of a target is the lowest-index restart below exit_loss with SLAM_FLAG_ORDERED, the smallest
  * loss otherwise and when no restart is below it:
- *   x0 double[n_targets][R][n] or NULL; out (any may be NULL): best_loss double[n_targets], best_x double[n_targets][n],
+ *   x0 double[n_targets][R][n] or NULL (every entry finite with |x| < 1e8, as slam_minimize_stage asks of its seeds: SLAM_ERR_INVALID
+ *   otherwise); out (any may be NULL): best_loss double[n_targets], best_x double[n_targets][n],
  *   best_restart int32[n_targets]; per item [n_targets][R]: item_loss, item_iters, item_status (SLAM_ST_*), item_evals,
  *   item_x double[n_targets][R][n]; kernel_ms: device time of the optimizer kernel
  * Arguments are checked before the context and before anything touches the device.

@@ -135,6 +135,15 @@ int check_minimize_stage(const slam_opt_params* params, const double* targets, i
     return SLAM_OK;
 }
 
+// explicit start points x0[n_targets * restarts * n], as the two-qubit stage checks them (slam_hip.hip, upload_stage_x0): the
+// optimizer's evaluation takes its sines and cosines from the table path, which is valid for |x| < 2e8 only
+int check_stage_x0(const double* x0, int64_t count) {
+    if (!x0) return SLAM_OK;
+    for (int64_t i = 0; i < count; ++i)
+        if (!(x0[i] > -1e8 && x0[i] < 1e8)) return fail(SLAM_ERR_INVALID, "x0[%lld] = %g: explicit seeds must be finite with |x| < 1e8", (long long)i, x0[i]);
+    return SLAM_OK;
+}
+
 int upload(slam_ctx* c, DevBuf& d, const void* src, size_t bytes) {
     HIP_TRY(d.reserve(bytes));
     HIP_TRY(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, c->stream));
@@ -318,6 +327,7 @@ int slam_q3_minimize(slam_ctx* ctx, const double* gates, int32_t n_gates, int32_
     { int rc = check_template(gates, n_gates, k, gate_index, edges, &edge_bits); if (rc) return rc; }
     { int rc = check_cost(cost_kind); if (rc) return rc; }
     { int rc = check_minimize_stage(params, targets, n_targets, exit_loss); if (rc) return rc; }
+    { int rc = check_stage_x0(x0, n_targets * (int64_t)params->restarts * (9 + 6 * k)); if (rc) return rc; }
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
     Q3Plan plan;
     fill_plan(plan, gates, k, gate_index, edge_bits);
@@ -334,6 +344,7 @@ int slam_q3m_minimize(slam_ctx* ctx, const double* gates2, int32_t n_gates2, con
     { int rc = check_mixed(gates2, n_gates2, gates3, n_gates3, k, arity, gate_index, qubits, &plan); if (rc) return rc; }
     { int rc = check_cost(cost_kind); if (rc) return rc; }
     { int rc = check_minimize_stage(params, targets, n_targets, exit_loss); if (rc) return rc; }
+    { int rc = check_stage_x0(x0, n_targets * (int64_t)params->restarts * plan.n); if (rc) return rc; }
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
     return drained(ctx, q3_minimize(ctx, plan, targets, n_targets, cost_kind, params, exit_loss, x0, best_loss, best_x, best_restart, item_loss,
                                     item_iters, item_status, item_evals, item_x, kernel_ms));

@@ -19,7 +19,9 @@ One ``REPLAY`` line per group (pytest -s; DESIGN.md has the table).
 
 Outside the trace facility: the wave-local, speculative and multi-queue forms of the loop are not traced.  test_gpu_refill_paths.py,
 test_gpu_span_bookkeeping.py and test_gpu_round4.py / test_gpu_round5.py tie them bit for bit to the per-span launches, which are
-what this module pins.  The V2 and parallel-drive optimizers have their own port (oracle/pqn_port.py) and no replay yet.
+what this module pins.  The three-qubit kernels (csrc/slam_q3.hpp, a re-laid copy of the long kernels' body) have no trace export;
+tests/test_gpu_q3_replay.py replays them along trajectories it collects from one launch per ``maxiter``.  The V2 and parallel-drive
+optimizers have their own port (oracle/pqn_port.py) and no replay yet.
 """
 import numpy as np
 import pytest

@@ -332,9 +332,9 @@ def test_validation_errors_need_no_gpu():
     assert ev(**only3) == (INVALID, "ctx is NULL")
     prm = _ffi.OptParams(restarts=2)
 
-    def mn(k=2, ar_=ar, qb_=qb, cost=0, prm_=prm, t_=t, nt=1, n3=2):
+    def mn(k=2, ar_=ar, qb_=qb, cost=0, prm_=prm, t_=t, nt=1, n3=2, x0_=None):
         rc = lib.slam_q3m_minimize(None, p(g2), 1, p(g3), n3, k, p(ar_), p(gi), p(qb_), p(t_), nt, cost,
-                                   C.byref(prm_) if prm_ is not None else None, 1e-10, *([None] * 10))
+                                   C.byref(prm_) if prm_ is not None else None, 1e-10, p(x0_), *([None] * 9))
         return rc, lib.slam_last_error().decode()
 
     assert mn() == (INVALID, "ctx is NULL")
@@ -347,3 +347,13 @@ def test_validation_errors_need_no_gpu():
     assert rc == INVALID and "params is NULL" in msg
     assert mn(prm_=_ffi.OptParams(restarts=0))[0] == INVALID
     assert mn(t_=None)[0] == INVALID and mn(nt=0)[0] == INVALID
+    # explicit start points [1, 2, 24]: finite with |x| < 1e8 (the optimizer's sincos table path), checked before the context
+    for at in (0, 47):
+        for bad in (np.nan, np.inf, -np.inf, 1e12, -1e12, 1e8):
+            x0 = np.zeros((1, 2, 24))
+            x0.flat[at] = bad
+            rc, msg = mn(x0_=x0)
+            assert rc == INVALID and f"x0[{at}]" in msg and "explicit seeds must be finite with |x| < 1e8" in msg, (at, bad, msg)
+        x0 = np.zeros((1, 2, 24))
+        x0.flat[at] = 9.9e7 if at else -9.9e7
+        assert mn(x0_=x0) == (INVALID, "ctx is NULL")

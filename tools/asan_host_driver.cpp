@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <thread>
 #include <vector>
 
@@ -304,6 +305,24 @@ int main() {
                SLAM_ERR_INVALID);
         EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, t8, 0, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
                SLAM_ERR_INVALID);
+        {  // explicit start points [1][restarts = 1][21]: every entry is read, the first and the last are refused unless finite with |x| < 1e8
+            const double bad[3] = {std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::infinity(), 1e12};
+            for (int at : {0, 20})
+                for (double v : bad) {
+                    double xb[21] = {0};
+                    xb[at] = v;
+                    EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, xb, d, g3, i32, d, i32, i32, i32, nullptr,
+                                            nullptr) == SLAM_ERR_INVALID);
+                    EXPECT(std::strstr(slam_last_error(), "explicit seeds must be finite with |x| < 1e8") != nullptr);
+                    EXPECT(std::strstr(slam_last_error(), at ? "x0[20]" : "x0[0]") != nullptr);
+                }
+            double ok[21] = {0};
+            ok[0] = 9.9e7;
+            ok[20] = -9.9e7;
+            EXPECT(slam_q3_minimize(nullptr, d, 1, 2, gi, ed, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, ok, d, g3, i32, d, i32, i32, i32, nullptr, nullptr) ==
+                   SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        }
     }
     {  // slam_q3m_eval, slam_q3m_minimize: arities, qubits, table indices and the caps are checked before the context
         const int32_t ar[2] = {3, 2}, gi[2] = {1, 0}, qb[6] = {0, 1, 2, 1, 2, 7}, bad_ar[2] = {3, 4}, bad_gi[2] = {2, 0}, bad_qb[6] = {0, 1, 1, 1, 2, 0};
@@ -351,6 +370,24 @@ int main() {
         EXPECT(std::strstr(slam_last_error(), "params is NULL") != nullptr);
         EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 0, SLAM_COST_BASIC, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
                                  nullptr) == SLAM_ERR_INVALID);
+        {  // explicit start points [1][1][24] (n from the arities), as above
+            const double bad[3] = {std::numeric_limits<double>::quiet_NaN(), -std::numeric_limits<double>::infinity(), -1e12};
+            for (int at : {0, 23})
+                for (double v : bad) {
+                    double xb[24] = {0};
+                    xb[at] = v;
+                    EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, xb, d, gr, i32, d, i32, i32, i32,
+                                             nullptr, nullptr) == SLAM_ERR_INVALID);
+                    EXPECT(std::strstr(slam_last_error(), "explicit seeds must be finite with |x| < 1e8") != nullptr);
+                    EXPECT(std::strstr(slam_last_error(), at ? "x0[23]" : "x0[0]") != nullptr);
+                }
+            double ok[24] = {0};
+            ok[0] = -9.9e7;
+            ok[23] = 9.9e7;
+            EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, ok, d, gr, i32, d, i32, i32, i32, nullptr,
+                                     nullptr) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        }
     }
     EXPECT(slam_set_cost(nullptr, 0) == SLAM_ERR_INVALID);
     EXPECT(slam_synchronize(nullptr) == SLAM_ERR_INVALID);
