@@ -908,6 +908,34 @@ int slam_q3m_minimize(slam_ctx* ctx, const double* gates2, int32_t n_gates2, con
                       double* kernel_ms);
 
 /*
+ * State objectives of the three-qubit templates (the reference's EntanglementCostFunction, src/slam/cost_function.py:44-99, the second
+ * branch of its objective, src/slam/optimizer.py:203-205): a start state psi -- 8 amplitudes, basis index q0 + 2 q1 + 4 q2, of unit norm
+ * -- goes through the template, v = W(x) psi, and the loss is the entanglement left in v, in bits:
+ *   SLAM_COST_MUTUAL_INFO         I(1:2) + I(0:2) + I(0:1),  I(a:b) = S(rho_a) + S(rho_b) - S(rho_ab)   (MutualInformation)
+ *   SLAM_COST_MUTUAL_INFO_SQUARE  the sum of the three squares                                        (MutualInformationSquare)
+ * Both are zero exactly on product states.  The template description, the caps, the Philox keying (a state's index takes the
+ * target's place), the ordered early exit, the outputs and kernel_ms are those of slam_q3m_eval / slam_q3m_minimize; a template
+ * without a position of arity 3 runs the non-mixed kernel.
+ *   states      double[n_states][8][2]     every entry finite, | |psi|^2 - 1 | <= 1e-9 (SLAM_ERR_INVALID otherwise)
+ *   state_of    int32[M]                   the state of item m
+ *   cost_kind   one of the two above; anything else, SLAM_COST_BASIC / SQUARE / MAKHLIN included: SLAM_ERR_INVALID
+ *   out_state   double[M][8][2]            v of every item (may be NULL)
+ * Loss and gradient are finite for every such state and every finite x: where a reduced state is maximally mixed the derivative is
+ * taken from its series, and a qubit whose reduced state is pure to rounding contributes zero to both.
+ * Arguments are checked before the context and before anything touches the device.  slam_set_cost does not take these kinds.
+ */
+#define SLAM_COST_MUTUAL_INFO 3
+#define SLAM_COST_MUTUAL_INFO_SQUARE 4 /* accepted by the two calls below only */
+int slam_q3s_eval(slam_ctx* ctx, const double* gates2, int32_t n_gates2, const double* gates3, int32_t n_gates3, int32_t k, const int32_t* arity,
+                  const int32_t* gate_index, const int32_t* qubits, const double* states, int64_t n_states, const double* x,
+                  const int32_t* state_of, int64_t M, int32_t cost_kind, double* loss, double* grad, double* out_state);
+int slam_q3s_minimize(slam_ctx* ctx, const double* gates2, int32_t n_gates2, const double* gates3, int32_t n_gates3, int32_t k,
+                      const int32_t* arity, const int32_t* gate_index, const int32_t* qubits, const double* states, int64_t n_states,
+                      int32_t cost_kind, const slam_opt_params* params, double exit_loss, const double* x0, double* best_loss, double* best_x,
+                      int32_t* best_restart, double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals, double* item_x,
+                      double* kernel_ms);
+
+/*
  * Multi-GPU: one process per GPU, RCCL over xGMI, reached through this ABI (no torch, no MPI).  The path shards by
  * target, every rank keeps all restarts of its targets, so the only exchange is the FINAL min-all-reduce of the
  * best-loss vector -- the running minimum of TemplateOptimizer._run (src/slam/optimizer.py:281-284) taken over the
@@ -986,7 +1014,8 @@ const char* slam_version(void);
  *      later: slam_sc_decompose and slam_sc_counts (new symbols only);
  *      later: slam_sqiswap_approx_decompose and slam_sqiswap_approx_counts (new symbols only);
  *      later: slam_q3_eval and slam_q3_minimize (new symbols only);
- *      later: slam_q3m_eval and slam_q3m_minimize (new symbols only).
+ *      later: slam_q3m_eval and slam_q3m_minimize (new symbols only);
+ *      later: slam_q3s_eval and slam_q3s_minimize (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

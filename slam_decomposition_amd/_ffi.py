@@ -37,6 +37,7 @@ SMUSH_MAX_N = 128
 OP_SUM, OP_MAX, OP_MIN = 0, 2, 3
 COMM_ID_BYTES = 128
 COST_BASIC, COST_SQUARE, COST_MAKHLIN = 0, 1, 2
+COST_MUTUAL_INFO, COST_MUTUAL_INFO_SQUARE = 3, 4  # the state objectives: slam_q3s_eval / slam_q3s_minimize only
 PD_MAX_SPAN = 8  # SLAM_PD_MAX_SPAN
 PD_MAX_SLICES = 16  # SLAM_PD_MAX_SLICES
 PD_MAX_DIRS = 1024  # SLAM_PD_MAX_DIRS
@@ -114,6 +115,8 @@ EXPORTED_SYMBOLS = (
     "slam_q3_minimize",
     "slam_q3m_eval",
     "slam_q3m_minimize",
+    "slam_q3s_eval",
+    "slam_q3s_minimize",
     "slam_set_cost",
     "slam_synchronize",
     "slam_host_alloc",
@@ -324,6 +327,9 @@ def load_library() -> C.CDLL:
         lib.slam_q3m_eval.argtypes = [P, P, C.c_int32, P, C.c_int32, C.c_int32, P, P, P, P, C.c_int64, P, P, C.c_int64, C.c_int32, P, P, P]
         lib.slam_q3m_minimize.argtypes = ([P, P, C.c_int32, P, C.c_int32, C.c_int32, P, P, P, P, C.c_int64, C.c_int32, C.POINTER(OptParams),
                                            C.c_double] + [P] * 10)
+    if hasattr(lib, "slam_q3s_eval"):
+        lib.slam_q3s_eval.argtypes = lib.slam_q3m_eval.argtypes
+        lib.slam_q3s_minimize.argtypes = lib.slam_q3m_minimize.argtypes
     lib.slam_set_cost.argtypes = [P, C.c_int]
     lib.slam_synchronize.argtypes = [P]
     if hasattr(lib, "slam_host_alloc"):
@@ -1350,6 +1356,56 @@ class Context:
         ms = np.zeros(1, dtype=np.float64)
         _check(self._lib.slam_q3m_minimize(self._h, _ptr(g2), g2.shape[0], _ptr(g3), g3.shape[0], len(ar), _ptr(ar), _ptr(gi), _ptr(qb),
                                            _ptr(t), N, int(cost_kind), C.byref(params), float(exit_loss), _ptr(x0),
+                                           *[_ptr(a) for a in out.values()], _ptr(ms)))
+        out["kernel_ms"] = float(ms[0])
+        return out
+
+    # -- state objectives of the three-qubit templates (slam_q3s_*): mutual information of a start state ------------------------
+    @staticmethod
+    def _q3s_states(states):
+        st = np.ascontiguousarray(np.asarray(states, dtype=np.complex128))
+        if st.ndim != 2 or st.shape[1] != 8:
+            raise ValueError(f"expected states of shape [N, 8], got {st.shape}")
+        return st.view(np.float64).reshape(st.shape + (2,))
+
+    def q3s_eval(self, gates2, gates3, arity, gate_index, qubits, states, x, state_of=None, cost_kind: int = COST_MUTUAL_INFO, want_grad=True,
+                 want_state=False):
+        """``slam_q3s_eval``: loss [M], gradient [M, n] (or None) and final state complex128 [M, 8] (or None) of M parameter rows of
+        the template of ``q3m_eval``, item m starting from ``states[state_of[m]]``; ``cost_kind``: ``COST_MUTUAL_INFO`` or
+        ``COST_MUTUAL_INFO_SQUARE``."""
+        st = self._q3s_states(states)
+        g2, g3, ar, gi, qb, _, n = self._q3m_template(gates2, gates3, arity, gate_index, qubits, np.zeros((1, 8, 8)))
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != n:
+            raise ValueError(f"x must have shape [M, {n}]")
+        M = x.shape[0]
+        sof = np.zeros(M, np.int32) if state_of is None else np.ascontiguousarray(state_of, dtype=np.int32)
+        if sof.shape != (M,):
+            raise ValueError("state_of must have shape [M]")
+        loss = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, n), dtype=np.float64) if want_grad else None
+        v = np.empty((M, 8, 2), dtype=np.float64) if want_state else None
+        _check(self._lib.slam_q3s_eval(self._h, _ptr(g2), g2.shape[0], _ptr(g3), g3.shape[0], len(ar), _ptr(ar), _ptr(gi), _ptr(qb), _ptr(st),
+                                       st.shape[0], _ptr(x), _ptr(sof), M, int(cost_kind), _ptr(loss), _ptr(grad), _ptr(v)))
+        return loss, grad, (None if v is None else v.view(np.complex128).reshape(M, 8))
+
+    def q3s_minimize(self, gates2, gates3, arity, gate_index, qubits, states, params: OptParams, exit_loss: float,
+                     cost_kind: int = COST_MUTUAL_INFO, x0=None) -> dict:
+        """``slam_q3s_minimize``: ``q3m_minimize`` with one start state [8] in each target's place; the same keys."""
+        st = self._q3s_states(states)
+        g2, g3, ar, gi, qb, _, n = self._q3m_template(gates2, gates3, arity, gate_index, qubits, np.zeros((1, 8, 8)))
+        N, R = st.shape[0], int(params.restarts)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (N, R, n):
+                raise ValueError(f"x0 must have shape [{N}, {R}, {n}]")
+        out = {"best_loss": np.empty(N, dtype=np.float64), "best_x": np.empty((N, n), dtype=np.float64),
+               "best_restart": np.empty(N, dtype=np.int32), "item_loss": np.empty((N, R), dtype=np.float64),
+               "item_iters": np.empty((N, R), dtype=np.int32), "item_status": np.empty((N, R), dtype=np.int32),
+               "item_evals": np.empty((N, R), dtype=np.int32), "item_x": np.empty((N, R, n), dtype=np.float64)}
+        ms = np.zeros(1, dtype=np.float64)
+        _check(self._lib.slam_q3s_minimize(self._h, _ptr(g2), g2.shape[0], _ptr(g3), g3.shape[0], len(ar), _ptr(ar), _ptr(gi), _ptr(qb),
+                                           _ptr(st), N, int(cost_kind), C.byref(params), float(exit_loss), _ptr(x0),
                                            *[_ptr(a) for a in out.values()], _ptr(ms)))
         out["kernel_ms"] = float(ms[0])
         return out

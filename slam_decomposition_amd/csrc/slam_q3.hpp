@@ -29,8 +29,14 @@
 //   * parameter offsets come from a running base (positions have 6 or 9 parameters).
 // The two-qubit-only kernels are the MIXED = false instantiations of the same bodies: nothing of the above is compiled into them.
 //
+// State objectives (eval_q3_kernel<MIXED, true>, minimize_q3_kernel<MIXED, true>; slam_q3s_*): the mutual information left in
+// v = W(x) psi for a start state psi.  P starts as the matrix with psi in column 0, step 3 of eval_q3 forms the three one-qubit reduced
+// states from column 0 and seeds the backward pass with the loss's derivative there; everything else is the same code, and nothing of
+// it is compiled into the STATE = false instantiations.  Seven of the eight columns idle (accepted: the optimizer body is wave-wide).
+//
 // Reference behaviour: CircuitTemplate(n_qubits, edge_params) src/slam/basis.py:52-169; BasicCost / SquareCost
-// src/slam/cost_function.py:140-145,169-173; the restart loop src/slam/optimizer.py:253-295.
+// src/slam/cost_function.py:140-145,169-173; MutualInformation / MutualInformationSquare src/slam/cost_function.py:44-99; the restart
+// loop src/slam/optimizer.py:253-295.
 #pragma once
 #include "slam_long.hpp"
 
@@ -207,12 +213,55 @@ __device__ __forceinline__ void q3_load_gates3(double* lds, const double* gates3
     }
 }
 
+// the sum over the 8 lanes of this lane's column (lanes 8 c .. 8 c + 7), in each of them: the first three steps of wave_sum
+__device__ __forceinline__ double q3_col_sum(double v) {
+    v += dpp_f64<0xB1>(v);
+    v += dpp_f64<0x4E>(v);
+    v += dpp_f64<0x141>(v);
+    return v;
+}
+
+// Entropy (base 2) of a one-qubit reduced state of unit trace from its determinant D, and dS/dD.  With s = sqrt(1 - 4 D) the
+// eigenvalues are (1 -+ s) / 2; the small one is taken as lam = 2 D / (1 + s) (no cancellation near D = 0), and
+// dS/dD = log2((1 - lam) / lam) / s = (2 / ln 2) atanh(s) / s.  The two singular points:
+//   * D = 1/4 (s = 0, the maximally mixed state: every qubit of GHZ): the quotient is 0/0 with the limit 2 / ln 2 -- below s^2 = 1e-2
+//     it is the series (2 / ln 2) sum_n s^(2 n) / (2 n + 1), nine terms (the first one left out is below 1e-20);
+//   * D = 0 (lam = 0, a product state: every successful minimum): dS/dD diverges while dD vanishes -- where the clamped eigenvalue is
+//     0 the qubit gives 0 to the loss and 0 to the gradient.
+// D is clamped to [0, 1/4] (rounding puts it outside), so both outputs are finite for every finite D.
+__device__ __forceinline__ double q3_qubit_entropy(double D, double& dSdD) {
+    D = fmin(fmax(D, 0.0), 0.25);
+    const double u = fma(-4.0, D, 1.0);
+    const double s = sqrt(u);
+    const double lam = 2.0 * D / (1.0 + s);
+    if (!(lam > 0.0)) {
+        dSdD = 0.0;
+        return 0.0;
+    }
+    const double om = 1.0 - lam;
+    const double l0 = log2(lam), l1 = log2(om);
+    const double S = -(lam * l0 + om * l1);
+    if (u < 1e-2) {
+        double p = 1.0 / 19.0;
+#pragma unroll
+        for (int m = 17; m >= 1; m -= 2) p = fma(p, u, 1.0 / (double)m);
+        dSdD = 2.8853900817779268 * p;  // 2 / ln 2
+    } else {
+        dSdD = (l1 - l0) / s;  // (s >= 0.1 here: the difference is at least 0.29, nothing cancels)
+    }
+    return S;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Fused loss + gradient of one item by the whole wavefront.  In: the trial point in lds[kQ3OffX ..], this lane's target entry
 // T[r][c], the gate tables in LDS.  Out: the loss (wave-uniform), the gradient in lds[kQ3OffG ..], this lane's entry of W.
 // ---------------------------------------------------------------------------------------------------------------------------
 // MIXED: `ext` and `n_mixed` are Q3MArgs' ext and n.
-template <bool HUGE_ARGS, bool MIXED = false>
+// STATE: the mutual-information objectives of a start state psi (SLAM_COST_MUTUAL_INFO, SLAM_COST_MUTUAL_INFO_SQUARE).  (tre, tim) is
+// this lane's entry of the 8x8 whose column 0 is psi and whose other columns are zero; P starts there, so column 0 of P is the state
+// v = W psi all the way (the other seven columns stay zero and idle), and (wre, wim) is this lane's entry of that matrix.  Only the
+// seed of the backward pass differs: B^T has column 0 only, 2 conj(dL / d conj(v)) -- d loss = Re(sum B^T dP) as for the trace.
+template <bool HUGE_ARGS, bool MIXED = false, bool STATE = false>
 __device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, int k, uint64_t edges, int cost_kind, double& wre, double& wim,
                                           uint64_t ext = 0, int n_mixed = 0) {
     const int lane = threadIdx.x;
@@ -239,6 +288,10 @@ __device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, i
     lds_fence();
     // ---- 2. forward: P = M_L ... M_1
     double pr = ((lane & 7) == (lane >> 3)) ? 1.0 : 0.0, pi = 0.0;
+    if constexpr (STATE) {  // P_0 = psi in column 0
+        pr = tre;
+        pi = tim;
+    }
     auto u3_fwd = [&](int base, int q) {
         const Q3Mat m = q3_u3_mat<0>(load_u3(reinterpret_cast<const double*>(trig), base));
         q3_mix2(m, (lane >> q) & 1, pr, pi, q3_xchg(pr, q), q3_xchg(pi, q));
@@ -273,6 +326,51 @@ __device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, i
     }
     wre = pr;
     wim = pi;
+    double fout, br, bi;
+    if constexpr (STATE) {
+        // ---- 3 (STATE). rho_q[s][s'] = sum over the rows with bit q = s of v conj(v at bit q := s'): the lane's entry, its partner
+        // at XOR 1 << q, masked sums over the lane's own column -- three exchanges each, not a wave sum's four and eight lane reads:
+        // the lanes of column 0 get rho_q, the others (all zeros) a zero matrix, S = 0 and a zero seed; S_q from D_q = det rho_q
+        // per qubit its entropy, dS/dD and dD_q / d conj(v): at a row with bit q = t that is rho_q[1-t][1-t] v - rho_q[t][1-t] (v of
+        // the partner row)
+        const double m2 = fma(pr, pr, pi * pi);
+        double S[3], dS[3], dr[3], di[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const bool bit = (lane >> q) & 1;
+            const double wr = q3_xchg(pr, q), wi = q3_xchg(pi, q);
+            const double r00 = q3_col_sum(bit ? 0.0 : m2), r11 = q3_col_sum(bit ? m2 : 0.0);
+            const double cr = q3_col_sum(bit ? 0.0 : fma(pr, wr, pi * wi));  // rho_q[0][1] = sum v[bit 0] conj(v[bit 1])
+            const double ci = q3_col_sum(bit ? 0.0 : fma(pi, wr, -(pr * wi)));
+            S[q] = q3_qubit_entropy(fma(r00, r11, -fma(cr, cr, ci * ci)), dS[q]);
+            const double dd = bit ? r00 : r11, oi = bit ? -ci : ci;
+            dr[q] = fma(dd, pr, -fma(cr, wr, -(oi * wi)));
+            di[q] = fma(dd, pi, -fma(cr, wi, oi * wr));
+        }
+        // a pure state: S(rho_ab) = S(rho_c), so I(a:b) = S_a + S_b - S_c = T - 2 S_c with T = S_0 + S_1 + S_2.
+        // MutualInformation = sum_c I = T; MutualInformationSquare = sum_c (T - 2 S_c)^2, d/dS_q = 2 (4 S_q - T)
+        const double T = S[0] + S[1] + S[2];
+        const bool sq = (cost_kind == 4);
+        if (sq) {
+            double acc = 0.0;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) acc = fma(fma(-2.0, S[q], T), fma(-2.0, S[q], T), acc);
+            fout = acc;
+        } else {
+            fout = T;
+        }
+        fout = long_readlane(fout, 0);  // (lane 0 is in column 0)
+        // B^T = 2 conj(dL / d conj(v))
+        double gr = 0.0, gi = 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const double w = (sq ? 2.0 * fma(4.0, S[q], -T) : 1.0) * dS[q];
+            gr = fma(w, dr[q], gr);
+            gi = fma(w, di[q], gi);
+        }
+        br = 2.0 * gr;
+        bi = -2.0 * gi;
+    } else {
     // ---- 3. t = Tr(T^+ W), the loss and its seed z: d loss = Re(z dt)
     const double tr = wave_sum(fma(tre, pr, tim * pi));
     const double ti = wave_sum(fma(tre, pi, -(tim * pr)));
@@ -282,11 +380,13 @@ __device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, i
     const double basic = 1.0 - 0.125 * at;  // BasicCost, cost_function.py:140-145
     const bool sq = (cost_kind == 1);       // SquareCost = 8/9 (2 L - L^2) of BasicCost L at d = 8 (cost_function.py:169-173)
     const double c0 = sq ? 16.0 / 9.0 : 1.0, c1 = sq ? -8.0 / 9.0 : 0.0, d1 = sq ? -16.0 / 9.0 : 0.0;
-    const double fout = basic * fma(c1, basic, c0);
+    fout = basic * fma(c1, basic, c0);
     const double inv = (0.125 * rat) * fma(d1, basic, c0);
     const double zr = -tr * inv, zi = ti * inv;
     // B^T = z conj(T)
-    double br = zr * tre + zi * tim, bi = zi * tre - zr * tim;
+    br = zr * tre + zi * tim;
+    bi = zi * tre - zr * tim;
+    }
     // ---- 4. backward: every factor undone on P and carried (transposed) through B^T, its derivatives on the way
     auto u3_bwd = [&](int base, int q) {
         const U3t t = load_u3(reinterpret_cast<const double*>(trig), base);
@@ -346,6 +446,13 @@ __device__ __forceinline__ double eval_q3(double* lds, double tre, double tim, i
     return fout;
 }
 
+// this lane's entry of the item's 8x8: the target's T[r][c], or (STATE) of the matrix whose column 0 is the state [8][2] of that index
+template <bool STATE>
+__device__ __forceinline__ double2 q3_item_entry(const double* base, int64_t index, int lane, int ent) {
+    if constexpr (STATE) return lane < 8 ? *reinterpret_cast<const double2*>(base + index * 16 + 2 * lane) : make_double2(0.0, 0.0);
+    else return *reinterpret_cast<const double2*>(base + index * 128 + ent);
+}
+
 // the wavefront's LDS prologue
 template <bool MIXED, class Args>
 __device__ __forceinline__ void q3_prologue(double* lds, const Args& a) {
@@ -359,7 +466,8 @@ __device__ __forceinline__ void q3_prologue(double* lds, const Args& a) {
 // slam_q3_eval / slam_q3m_eval: one item per wavefront, grid-stride
 // ---------------------------------------------------------------------------------------------------------------------------
 // (MIXED: LDS lets twelve of these wavefronts onto a CU, not sixteen -- see kQ3MLdsBytes)
-template <bool MIXED>
+// STATE (slam_q3s_eval): `targets` holds the start states [n][8][2], `unitary` the final states [M][8][2]
+template <bool MIXED, bool STATE = false>
 __global__ void __launch_bounds__(kWave, 4) eval_q3_kernel(std::conditional_t<MIXED, Q3MEvalArgs, Q3EvalArgs> a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x;
@@ -378,9 +486,9 @@ __global__ void __launch_bounds__(kWave, 4) eval_q3_kernel(std::conditional_t<MI
             lds[kQ3OffX + i] = i < n ? a.x[m * n + i] : 0.0;
         }
         lds_fence();
-        const double2 t = *reinterpret_cast<const double2*>(a.targets + (int64_t)a.target_of[m] * 128 + ent);
+        const double2 t = q3_item_entry<STATE>(a.targets, (int64_t)a.target_of[m], lane, ent);
         double wr, wi;
-        const double f = eval_q3<true, MIXED>(lds, t.x, t.y, a.k, a.edges, a.cost_kind, wr, wi, ext, n);
+        const double f = eval_q3<true, MIXED, STATE>(lds, t.x, t.y, a.k, a.edges, a.cost_kind, wr, wi, ext, n);
         if (lane == 0) a.loss[m] = f;
         if (a.grad) {
 #pragma unroll
@@ -389,16 +497,20 @@ __global__ void __launch_bounds__(kWave, 4) eval_q3_kernel(std::conditional_t<MI
                 if (i < n) a.grad[m * n + i] = lds[kQ3OffG + i];
             }
         }
-        if (a.unitary) *reinterpret_cast<double2*>(a.unitary + m * 128 + ent) = make_double2(wr, wi);
+        if constexpr (STATE) {
+            if (a.unitary && lane < 8) *reinterpret_cast<double2*>(a.unitary + m * 16 + 2 * lane) = make_double2(wr, wi);
+        } else {
+            if (a.unitary) *reinterpret_cast<double2*>(a.unitary + m * 128 + ent) = make_double2(wr, wi);
+        }
         lds_fence();
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // slam_q3_minimize: the quasi-Newton iteration of slam_long_minimize.inc (its body, copied) around eval_q3; one body, instantiated for
-// the two-qubit-only templates (MIXED = false) and the mixed ones
+// the two-qubit-only templates (MIXED = false) and the mixed ones; STATE (slam_q3s_minimize): `targets` holds the start states [n][8][2]
 // ---------------------------------------------------------------------------------------------------------------------------
-template <bool MIXED>
+template <bool MIXED, bool STATE = false>
 __global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(std::conditional_t<MIXED, Q3MArgs, Q3Args> args) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x;
@@ -443,7 +555,7 @@ __global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(std::conditional_
                 continue;
             }
         }
-        const double2 tt = *reinterpret_cast<const double2*>(args.targets + (int64_t)sl * 128 + ent);
+        const double2 tt = q3_item_entry<STATE>(args.targets, (int64_t)sl, lane, ent);
         const double tre = tt.x, tim = tt.y;
         double wre, wim;  // (the unitary is not wanted here)
         double x[kQ3Slots], g[kQ3Slots], p[kQ3Slots];
@@ -469,7 +581,7 @@ __global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(std::conditional_
             }
         }
         lds_fence();
-        double f = eval_q3<false, MIXED>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim, ext, n);
+        double f = eval_q3<false, MIXED, STATE>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim, ext, n);
         ++rounds;
         int nev = 1, nacc = 0, iters = 0, nback = 0, nstall = 0, status = ST_MAXITER;
         bool ident = true, scaled = false;  // ident: H is the identity (nothing of it is in memory yet)
@@ -513,7 +625,7 @@ __global__ void __launch_bounds__(kWave, 3) minimize_q3_kernel(std::conditional_
                 lds[kQ3OffX + 2 * lane + s] = xt[s];
             }
             lds_fence();
-            const double ft = eval_q3<false, MIXED>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim, ext, n);
+            const double ft = eval_q3<false, MIXED, STATE>(lds, tre, tim, k, args.edges, args.cost_kind, wre, wim, ext, n);
             ++rounds;
             ++nev;
             const bool finite = isfinite(ft);

@@ -1,5 +1,6 @@
 // slam_q3_host.hip -- host side of the three-qubit templates (slam_q3.hpp): slam_q3_eval, slam_q3_minimize and their mixed-arity
-// siblings slam_q3m_eval, slam_q3m_minimize.  All are self-contained: gates, targets and parameters come from the host with every
+// siblings slam_q3m_eval, slam_q3m_minimize, and the state objectives slam_q3s_eval, slam_q3s_minimize (mutual information of a start
+// state carried through the template: the STATE instantiations of the same kernels).  All are self-contained: gates, targets and parameters come from the host with every
 // call, the context lends its device and its stream, and its resident 4x4 targets, gate table, results and statistics are not touched.
 // A checked template is a Q3Plan; the mixed kernels run only for a plan with a three-qubit position.
 #include "slam_host.hpp"
@@ -14,6 +15,7 @@ static_assert(SLAM_Q3_MAX_SPAN == kQ3MaxSpan, "header and kernel disagree");
 struct Q3Plan {
     int k = 0, n = 0;
     bool mixed = false;           // a position has arity 3
+    bool state = false;           // slam_q3s_*: the items are 8-vectors (start states), not 8x8 targets
     uint64_t edge_bits = 0;       // Q3Args::edges
     uint64_t ext_bits = 0;        // Q3MArgs::ext
     std::vector<double> gates2;   // [k][4][4][2]: the 4x4 of every position (zeros at a three-qubit position)
@@ -105,6 +107,29 @@ int check_cost(int32_t cost_kind) {
     return SLAM_OK;
 }
 
+int check_state_cost(int32_t cost_kind) {
+    if (cost_kind != SLAM_COST_MUTUAL_INFO && cost_kind != SLAM_COST_MUTUAL_INFO_SQUARE)
+        return fail(SLAM_ERR_INVALID, "cost kind %d: the state objectives are SLAM_COST_MUTUAL_INFO (%d) and SLAM_COST_MUTUAL_INFO_SQUARE (%d)", cost_kind,
+                    SLAM_COST_MUTUAL_INFO, SLAM_COST_MUTUAL_INFO_SQUARE);
+    return SLAM_OK;
+}
+
+// start states [n_states][8][2]: finite, of unit norm to 1e-9
+int check_states(const double* states, int64_t n_states) {
+    if (!states || n_states <= 0) return fail(SLAM_ERR_INVALID, "states: at least one state of 8 amplitudes is required");
+    if (n_states > 0x7fff0000LL) return fail(SLAM_ERR_INVALID, "too many states (%lld)", (long long)n_states);
+    for (int64_t s = 0; s < n_states; ++s) {
+        double norm2 = 0.0;
+        for (int i = 0; i < 16; ++i) {
+            const double v = states[s * 16 + i];
+            if (!std::isfinite(v)) return fail(SLAM_ERR_INVALID, "states[%lld]: entry %d is not finite", (long long)s, i);
+            norm2 += v * v;
+        }
+        if (!(std::fabs(norm2 - 1.0) <= 1e-9)) return fail(SLAM_ERR_INVALID, "states[%lld]: |psi|^2 = %.17g is not 1 to 1e-9", (long long)s, norm2);
+    }
+    return SLAM_OK;
+}
+
 // the 4x4 of every position, in order: [k][4][4][2] on the device; for a mixed plan the table of three-qubit gates too
 int stage_q3_gates(slam_ctx* c, DevBuf& d, DevBuf& d3, const Q3Plan& p) {
     HIP_TRY(d.reserve(p.gates2.size() * sizeof(double)));
@@ -153,18 +178,20 @@ int upload(slam_ctx* c, DevBuf& d, const void* src, size_t bytes) {
 int q3_eval(slam_ctx* c, const Q3Plan& plan, const double* targets, int64_t n_targets, const double* x, const int32_t* target_of, int64_t M,
             int32_t cost_kind, double* loss, double* grad, double* unitary) {
     const int n = plan.n;
-    const void* kernel = plan.mixed ? reinterpret_cast<const void*>(&eval_q3_kernel<true>) : reinterpret_cast<const void*>(&eval_q3_kernel<false>);
+    const void* kernel = plan.state ? (plan.mixed ? reinterpret_cast<const void*>(&eval_q3_kernel<true, true>) : reinterpret_cast<const void*>(&eval_q3_kernel<false, true>))
+                                    : (plan.mixed ? reinterpret_cast<const void*>(&eval_q3_kernel<true>) : reinterpret_cast<const void*>(&eval_q3_kernel<false>));
     const size_t lds_bytes = plan.mixed ? kQ3MLdsBytes : kQ3LdsBytes;
+    const size_t item_doubles = plan.state ? 16 : 128;  // a state [8][2] or a target / unitary [8][8][2]
     HIP_TRY(hipSetDevice(c->device));
     { int rc = kernel_per_cu(c, kernel, lds_bytes, nullptr); if (rc) return rc; }
     DevBuf d_gates, d_gates3, d_targets, d_x, d_tof, d_loss, d_grad, d_unitary;
     { int rc = stage_q3_gates(c, d_gates, d_gates3, plan); if (rc) return rc; }
-    { int rc = upload(c, d_targets, targets, (size_t)n_targets * 128 * sizeof(double)); if (rc) return rc; }
+    { int rc = upload(c, d_targets, targets, (size_t)n_targets * item_doubles * sizeof(double)); if (rc) return rc; }
     { int rc = upload(c, d_x, x, (size_t)M * n * sizeof(double)); if (rc) return rc; }
     { int rc = upload(c, d_tof, target_of, (size_t)M * sizeof(int32_t)); if (rc) return rc; }
     HIP_TRY(d_loss.reserve((size_t)M * sizeof(double)));
     if (grad) HIP_TRY(d_grad.reserve((size_t)M * n * sizeof(double)));
-    if (unitary) HIP_TRY(d_unitary.reserve((size_t)M * 128 * sizeof(double)));
+    if (unitary) HIP_TRY(d_unitary.reserve((size_t)M * item_doubles * sizeof(double)));
     Q3MEvalArgs a{};
     a.targets = d_targets.as<double>();
     a.x = d_x.as<double>();
@@ -184,12 +211,14 @@ int q3_eval(slam_ctx* c, const Q3Plan& plan, const double* targets, int64_t n_ta
     int64_t blocks = M;
     const int64_t cap = (int64_t)16 * c->compute_units;
     if (blocks > cap) blocks = cap;
-    if (plan.mixed) hipLaunchKernelGGL(eval_q3_kernel<true>, dim3((unsigned)blocks), dim3(kWave), kQ3MLdsBytes, c->stream, a);
+    if (plan.state && plan.mixed) hipLaunchKernelGGL((eval_q3_kernel<true, true>), dim3((unsigned)blocks), dim3(kWave), kQ3MLdsBytes, c->stream, a);
+    else if (plan.state) hipLaunchKernelGGL((eval_q3_kernel<false, true>), dim3((unsigned)blocks), dim3(kWave), kQ3LdsBytes, c->stream, static_cast<const Q3EvalArgs&>(a));
+    else if (plan.mixed) hipLaunchKernelGGL(eval_q3_kernel<true>, dim3((unsigned)blocks), dim3(kWave), kQ3MLdsBytes, c->stream, a);
     else hipLaunchKernelGGL(eval_q3_kernel<false>, dim3((unsigned)blocks), dim3(kWave), kQ3LdsBytes, c->stream, static_cast<const Q3EvalArgs&>(a));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(loss, d_loss.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (grad) HIP_TRY(hipMemcpyAsync(grad, d_grad.p, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (unitary) HIP_TRY(hipMemcpyAsync(unitary, d_unitary.p, (size_t)M * 128 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (unitary) HIP_TRY(hipMemcpyAsync(unitary, d_unitary.p, (size_t)M * item_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SLAM_OK;
 }
@@ -198,7 +227,8 @@ int q3_minimize(slam_ctx* c, const Q3Plan& plan, const double* targets, int64_t 
                 int32_t* best_restart, double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals, double* item_x,
                 double* kernel_ms) {
     const int n = plan.n;
-    const void* kernel = plan.mixed ? reinterpret_cast<const void*>(&minimize_q3_kernel<true>) : reinterpret_cast<const void*>(&minimize_q3_kernel<false>);
+    const void* kernel = plan.state ? (plan.mixed ? reinterpret_cast<const void*>(&minimize_q3_kernel<true, true>) : reinterpret_cast<const void*>(&minimize_q3_kernel<false, true>))
+                                    : (plan.mixed ? reinterpret_cast<const void*>(&minimize_q3_kernel<true>) : reinterpret_cast<const void*>(&minimize_q3_kernel<false>));
     const size_t lds_bytes = plan.mixed ? kQ3MLdsBytes : kQ3LdsBytes;
     const int R = prm->restarts;
     const int64_t M = N * (int64_t)R;
@@ -210,7 +240,7 @@ int q3_minimize(slam_ctx* c, const Q3Plan& plan, const double* targets, int64_t 
     if (blocks < 1) blocks = 1;
     DevBuf d_gates, d_gates3, d_targets, d_x0, d_ctl, d_solved, d_rec, d_x, d_hmem;
     { int rc = stage_q3_gates(c, d_gates, d_gates3, plan); if (rc) return rc; }
-    { int rc = upload(c, d_targets, targets, (size_t)N * 128 * sizeof(double)); if (rc) return rc; }
+    { int rc = upload(c, d_targets, targets, (size_t)N * (plan.state ? 16 : 128) * sizeof(double)); if (rc) return rc; }
     if (x0) { int rc = upload(c, d_x0, x0, (size_t)M * n * sizeof(double)); if (rc) return rc; }
     StageCtl h_ctl{};
     h_ctl.n_active = (int32_t)N;
@@ -250,7 +280,9 @@ int q3_minimize(slam_ctx* c, const Q3Plan& plan, const double* targets, int64_t 
     HIP_TRY(hipEventCreate(&e0.h));
     HIP_TRY(hipEventCreate(&e1.h));
     HIP_TRY(hipEventRecord(e0, c->stream));
-    if (plan.mixed) hipLaunchKernelGGL(minimize_q3_kernel<true>, dim3((unsigned)blocks), dim3(kWave), kQ3MLdsBytes, c->stream, a);
+    if (plan.state && plan.mixed) hipLaunchKernelGGL((minimize_q3_kernel<true, true>), dim3((unsigned)blocks), dim3(kWave), kQ3MLdsBytes, c->stream, a);
+    else if (plan.state) hipLaunchKernelGGL((minimize_q3_kernel<false, true>), dim3((unsigned)blocks), dim3(kWave), kQ3LdsBytes, c->stream, static_cast<const Q3Args&>(a));
+    else if (plan.mixed) hipLaunchKernelGGL(minimize_q3_kernel<true>, dim3((unsigned)blocks), dim3(kWave), kQ3MLdsBytes, c->stream, a);
     else hipLaunchKernelGGL(minimize_q3_kernel<false>, dim3((unsigned)blocks), dim3(kWave), kQ3LdsBytes, c->stream, static_cast<const Q3Args&>(a));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e1, c->stream));
@@ -347,6 +379,36 @@ int slam_q3m_minimize(slam_ctx* ctx, const double* gates2, int32_t n_gates2, con
     { int rc = check_stage_x0(x0, n_targets * (int64_t)params->restarts * plan.n); if (rc) return rc; }
     if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
     return drained(ctx, q3_minimize(ctx, plan, targets, n_targets, cost_kind, params, exit_loss, x0, best_loss, best_x, best_restart, item_loss,
+                                    item_iters, item_status, item_evals, item_x, kernel_ms));
+}
+
+int slam_q3s_eval(slam_ctx* ctx, const double* gates2, int32_t n_gates2, const double* gates3, int32_t n_gates3, int32_t k, const int32_t* arity,
+                  const int32_t* gate_index, const int32_t* qubits, const double* states, int64_t n_states, const double* x,
+                  const int32_t* state_of, int64_t M, int32_t cost_kind, double* loss, double* grad, double* out_state) {
+    Q3Plan plan;
+    { int rc = check_mixed(gates2, n_gates2, gates3, n_gates3, k, arity, gate_index, qubits, &plan); if (rc) return rc; }
+    { int rc = check_state_cost(cost_kind); if (rc) return rc; }
+    { int rc = check_states(states, n_states); if (rc) return rc; }
+    { int rc = check_eval_items(states, n_states, x, state_of, M, loss); if (rc) return rc; }
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    plan.state = true;
+    return drained(ctx, q3_eval(ctx, plan, states, n_states, x, state_of, M, cost_kind, loss, grad, out_state));
+}
+
+int slam_q3s_minimize(slam_ctx* ctx, const double* gates2, int32_t n_gates2, const double* gates3, int32_t n_gates3, int32_t k,
+                      const int32_t* arity, const int32_t* gate_index, const int32_t* qubits, const double* states, int64_t n_states,
+                      int32_t cost_kind, const slam_opt_params* params, double exit_loss, const double* x0, double* best_loss, double* best_x,
+                      int32_t* best_restart, double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals, double* item_x,
+                      double* kernel_ms) {
+    Q3Plan plan;
+    { int rc = check_mixed(gates2, n_gates2, gates3, n_gates3, k, arity, gate_index, qubits, &plan); if (rc) return rc; }
+    { int rc = check_state_cost(cost_kind); if (rc) return rc; }
+    { int rc = check_states(states, n_states); if (rc) return rc; }
+    { int rc = check_minimize_stage(params, states, n_states, exit_loss); if (rc) return rc; }
+    { int rc = check_stage_x0(x0, n_states * (int64_t)params->restarts * plan.n); if (rc) return rc; }
+    if (!ctx) return fail(SLAM_ERR_INVALID, "ctx is NULL");
+    plan.state = true;
+    return drained(ctx, q3_minimize(ctx, plan, states, n_states, cost_kind, params, exit_loss, x0, best_loss, best_x, best_restart, item_loss,
                                     item_iters, item_status, item_evals, item_x, kernel_ms));
 }
 

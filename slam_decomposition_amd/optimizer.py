@@ -30,7 +30,8 @@ from .basis import CircuitTemplate
 from .basisv2 import CircuitTemplateV2
 from .basis3q import ThreeQubitCircuitTemplate
 from .basis_abc import DataDictEntry, LazyList, RowBlocks, TargetDataList, VariationalTemplate
-from .cost_function import BasicCost, MakhlinFunctionalCost, SquareCost, UnitaryCostFunction
+from .cost_function import (BasicCost, EntanglementCostFunction, MakhlinFunctionalCost, MutualInformation, MutualInformationSquare, SquareCost,
+                            UnitaryCostFunction)
 from .sampler import SampleFunction
 
 SUCCESS_THRESHOLD = 1e-10  # optimizer.py:18
@@ -133,7 +134,18 @@ class TemplateOptimizer:
         elif not isinstance(basis, (CircuitTemplate, CircuitTemplateV2)):
             raise NotImplementedError("the HIP optimizer needs a slam_decomposition_amd CircuitTemplate / CircuitTemplateV2")
         self._v2 = isinstance(basis, CircuitTemplateV2)
-        if isinstance(self.objective, SquareCost):
+        # the reference's second branch (optimizer.py:203-205): the objective's start state through the template, the target ignored
+        self._state_objective = isinstance(self.objective, EntanglementCostFunction)
+        if self._state_objective:
+            if not isinstance(self.objective, (MutualInformation, MutualInformationSquare)):
+                raise NotImplementedError(f"{type(self.objective).__name__}: the reference's entanglement_monotone returns nothing for it; "
+                                          "implemented are MutualInformation and MutualInformationSquare")
+            if not self._q3:
+                raise NotImplementedError("MutualInformation / MutualInformationSquare take three-qubit states: they need a "
+                                          "ThreeQubitCircuitTemplate")
+            self._cost_kind = (_ffi.COST_MUTUAL_INFO_SQUARE if isinstance(self.objective, MutualInformationSquare)
+                               else _ffi.COST_MUTUAL_INFO)
+        elif isinstance(self.objective, SquareCost):
             self._cost_kind = _ffi.COST_SQUARE
         elif isinstance(self.objective, BasicCost):
             self._cost_kind = _ffi.COST_BASIC
@@ -866,7 +878,11 @@ class TemplateOptimizer:
             if len(open_idx) == 0:
                 break
             # (the stage gets the open targets only: the Philox key holds a target's index within that list)
-            if basis.has_three_qubit_position(k):  # the mixed entry point only where a position needs it
+            if self._state_objective:  # one start state per sample; the kernel without three-qubit rows where no position needs them
+                out = ctx.q3s_minimize(basis.gate_matrices, basis.gate_matrices3, *basis.mixed_description(k),
+                                       np.tile(self.objective.state_vector, (len(open_idx), 1)), prm, self.success_threshold,
+                                       cost_kind=self._cost_kind)
+            elif basis.has_three_qubit_position(k):  # the mixed entry point only where a position needs it
                 out = ctx.q3m_minimize(basis.gate_matrices, basis.gate_matrices3, *basis.mixed_description(k), targets[open_idx], prm,
                                        self.success_threshold, cost_kind=self._cost_kind)
             else:
@@ -1011,6 +1027,8 @@ class TemplateOptimizer:
     # ------------------------------------------------------------------------------------------
     def approximate_target_U(self, target_U) -> DataDictEntry:
         """Atomic training function (optimizer.py:65-119)."""
+        if self._state_objective:  # the objective does not look at the target (optimizer.py:203-205): None is fine
+            return self._approximate_batch_3q(np.eye(8, dtype=np.complex128)[None], log_index=False)[0]
         t = np.asarray(target_U, dtype=np.complex128)
         if self._q3:
             if t.shape != (8, 8):
@@ -1022,6 +1040,10 @@ class TemplateOptimizer:
 
     def approximate_from_distribution(self, sampler: SampleFunction):
         """optimizer.py:180-186; all targets of the sampler are optimised as one GPU batch."""
+        if self._state_objective:  # one run per sample, whatever the sample is
+            count = sum(1 for _ in sampler)
+            target_data = self._approximate_batch_3q(np.tile(np.eye(8, dtype=np.complex128), (count, 1, 1)), log_index=True) if count else []
+            return self.training_loss, self.coordinate_list, target_data
         if self._q3:
             targets = [np.asarray(t, dtype=np.complex128) for t in sampler]
             for t in targets:

@@ -5,6 +5,7 @@
 #include "../include/slam_hip.h"
 
 #include <cstdio>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
@@ -385,6 +386,67 @@ int main() {
             ok[0] = -9.9e7;
             ok[23] = 9.9e7;
             EXPECT(slam_q3m_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, t8, 1, SLAM_COST_BASIC, &prm, 1e-10, ok, d, gr, i32, d, i32, i32, i32, nullptr,
+                                     nullptr) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        }
+    }
+    {  // slam_q3s_eval, slam_q3s_minimize: the cost kind and the states (finite, unit norm to 1e-9) too are checked before the context
+        const int32_t ar[2] = {3, 2}, gi[2] = {1, 0}, qb[6] = {0, 1, 2, 1, 2, 7}, bad_ar[2] = {3, 4}, bad_qb[6] = {0, 1, 1, 1, 2, 0};
+        static double g3m[2][128] = {{0}}, x3[24] = {0}, gr[24], vout[16];
+        const double* g3 = &g3m[0][0];
+        double st2[2][16] = {{0}};
+        st2[0][6] = 1.0;                               // |011>
+        st2[1][1] = st2[1][15] = std::sqrt(0.5);       // (i |000> + i |111>) / sqrt 2
+        const double* st = &st2[0][0];
+        for (int32_t kind : {SLAM_COST_MUTUAL_INFO, SLAM_COST_MUTUAL_INFO_SQUARE}) {
+            EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, x3, i32, 1, kind, d, gr, vout) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        }
+        for (int32_t kind : {SLAM_COST_BASIC, SLAM_COST_SQUARE, SLAM_COST_MAKHLIN, 5, -1}) {
+            EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, x3, i32, 1, kind, d, gr, vout) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "SLAM_COST_MUTUAL_INFO") != nullptr);
+            EXPECT(slam_q3s_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, kind, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                     nullptr) == SLAM_ERR_INVALID);
+        }
+        for (double v : {std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::infinity(), 1.0 + 1e-8, 0.0}) {
+            double sb[2][16];
+            std::memcpy(sb, st2, sizeof sb);
+            sb[1][15] = v;  // (the last entry of the last state: all of the array is read)
+            EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, &sb[0][0], 2, x3, i32, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "states[1]") != nullptr);
+            EXPECT(slam_q3s_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, &sb[0][0], 2, SLAM_COST_MUTUAL_INFO, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32,
+                                     i32, nullptr, nullptr) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "states[1]") != nullptr);
+        }
+        EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, nullptr, 2, x3, i32, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 0, x3, i32, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, nullptr, i32, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, x3, i32, 0, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID);
+        { const int32_t sof[1] = {2}; EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, x3, sof, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID); }
+        // what the mixed pair checks
+        EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, SLAM_Q3_MAX_SPAN + 1, ar, gi, qb, st, 2, x3, i32, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, bad_ar, gi, qb, st, 2, x3, i32, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "arity[1]") != nullptr);
+        EXPECT(slam_q3s_eval(nullptr, d, 1, g3, 2, 2, ar, gi, bad_qb, st, 2, x3, i32, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3s_eval(nullptr, d, 1, nullptr, 2, 2, ar, gi, qb, st, 2, x3, i32, 1, SLAM_COST_MUTUAL_INFO, d, gr, vout) == SLAM_ERR_INVALID);
+        EXPECT(slam_q3s_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, SLAM_COST_MUTUAL_INFO_SQUARE, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32,
+                                 nullptr, nullptr) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        EXPECT(slam_q3s_minimize(nullptr, d, 1, g3, 2, 16, ar, gi, qb, st, 2, SLAM_COST_MUTUAL_INFO, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(slam_q3s_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, SLAM_COST_MUTUAL_INFO, nullptr, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "params is NULL") != nullptr);
+        EXPECT(slam_q3s_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, nullptr, 2, SLAM_COST_MUTUAL_INFO, &prm, 1e-10, nullptr, d, gr, i32, d, i32, i32, i32, nullptr,
+                                 nullptr) == SLAM_ERR_INVALID);
+        {  // explicit start points [2][restarts = 1][24]: the last entry is read
+            double xb[48] = {0};
+            xb[47] = 1e12;
+            EXPECT(slam_q3s_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, SLAM_COST_MUTUAL_INFO, &prm, 1e-10, xb, d, gr, i32, d, i32, i32, i32, nullptr,
+                                     nullptr) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "x0[47]") != nullptr);
+            xb[47] = 9.9e7;
+            EXPECT(slam_q3s_minimize(nullptr, d, 1, g3, 2, 2, ar, gi, qb, st, 2, SLAM_COST_MUTUAL_INFO, &prm, 1e-10, xb, d, gr, i32, d, i32, i32, i32, nullptr,
                                      nullptr) == SLAM_ERR_INVALID);
             EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
         }
