@@ -936,6 +936,36 @@ int slam_q3s_minimize(slam_ctx* ctx, const double* gates2, int32_t n_gates2, con
                       double* kernel_ms);
 
 /*
+ * Hamiltonian templates (csrc/slam_ham.hpp; the reference's HamiltonianTemplate, src/slam/basis.py:24-48, over src/slam/hamiltonian.py):
+ * the parameters x are the drive strengths and phases (and possibly the time) of
+ *   H(x) = sum_k c_k M_k + h.c.,   c_k = x[s_index[k]] exp(i x[phi_index[k]])   (phi_index[k] = -1: phase 0),
+ * and the template's unitary is exp(-i t H(x)), t = x[t_index] (t_index = -1: t = 1).  dim is 4 or 8; matrices are row-major.
+ *   matrices    double[n_terms][dim][dim][2]   the M_k; n_terms <= SLAM_HAM_MAX_TERMS, n_params <= SLAM_HAM_MAX_PARAMS, and no entry of
+ *                                              H may take more than two contributions (beyond any of them: SLAM_ERR_UNSUPPORTED)
+ *   s_index     int32[n_terms]                 in 0 .. n_params - 1
+ *   phi_index   int32[n_terms]                 in -1 .. n_params - 1
+ *   targets     double[n_targets][dim][dim][2] any finite matrices (they need not be unitary)
+ *   cost_kind   SLAM_COST_BASIC  1 - |Tr(T^+ U)| / dim,  SLAM_COST_SQUARE  1 - (|Tr(T^+ U)|^2 + dim) / (dim (dim + 1)); others:
+ *               SLAM_ERR_INVALID
+ * slam_ham_eval: M items, item m = (x[m], target target_of[m]); x double[M][n_params], every entry finite; out: loss double[M],
+ *   grad double[M][n_params] (may be NULL), unitary double[M][dim][dim][2] (may be NULL).
+ * slam_ham_minimize: one stage as slam_q3_minimize -- the same quasi-Newton iteration, status codes, restart-major queue, ordered
+ *   early exit at exit_loss, reduction over the restarts, outputs and kernel_ms -- except that x0 double[n_targets][R][n_params] is
+ *   REQUIRED (every entry finite with |x| < 1e8): the start points are drawn on the host, the device draws none.
+ * Both calls are self-contained (nothing of the context is touched or kept), and dimensions, index arrays, caps, matrices, targets,
+ * start points and the cost kind are checked before the context and before anything touches the device.
+ */
+#define SLAM_HAM_MAX_TERMS 16
+#define SLAM_HAM_MAX_PARAMS 32
+int slam_ham_eval(slam_ctx* ctx, int32_t dim, int32_t n_params, int32_t n_terms, const double* matrices, const int32_t* s_index,
+                  const int32_t* phi_index, int32_t t_index, const double* targets, int64_t n_targets, const double* x, const int32_t* target_of,
+                  int64_t M, int32_t cost_kind, double* loss, double* grad, double* unitary);
+int slam_ham_minimize(slam_ctx* ctx, int32_t dim, int32_t n_params, int32_t n_terms, const double* matrices, const int32_t* s_index,
+                      const int32_t* phi_index, int32_t t_index, const double* targets, int64_t n_targets, int32_t cost_kind,
+                      const slam_opt_params* params, double exit_loss, const double* x0, double* best_loss, double* best_x, int32_t* best_restart,
+                      double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals, double* item_x, double* kernel_ms);
+
+/*
  * Multi-GPU: one process per GPU, RCCL over xGMI, reached through this ABI (no torch, no MPI).  The path shards by
  * target, every rank keeps all restarts of its targets, so the only exchange is the FINAL min-all-reduce of the
  * best-loss vector -- the running minimum of TemplateOptimizer._run (src/slam/optimizer.py:281-284) taken over the
@@ -1015,7 +1045,8 @@ const char* slam_version(void);
  *      later: slam_sqiswap_approx_decompose and slam_sqiswap_approx_counts (new symbols only);
  *      later: slam_q3_eval and slam_q3_minimize (new symbols only);
  *      later: slam_q3m_eval and slam_q3m_minimize (new symbols only);
- *      later: slam_q3s_eval and slam_q3s_minimize (new symbols only).
+ *      later: slam_q3s_eval and slam_q3s_minimize (new symbols only);
+ *      later: slam_ham_eval and slam_ham_minimize (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

@@ -117,6 +117,8 @@ EXPORTED_SYMBOLS = (
     "slam_q3m_minimize",
     "slam_q3s_eval",
     "slam_q3s_minimize",
+    "slam_ham_eval",
+    "slam_ham_minimize",
     "slam_set_cost",
     "slam_synchronize",
     "slam_host_alloc",
@@ -330,6 +332,10 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "slam_q3s_eval"):
         lib.slam_q3s_eval.argtypes = lib.slam_q3m_eval.argtypes
         lib.slam_q3s_minimize.argtypes = lib.slam_q3m_minimize.argtypes
+    if hasattr(lib, "slam_ham_eval"):
+        ham = [P, C.c_int32, C.c_int32, C.c_int32, P, P, P, C.c_int32, P, C.c_int64]
+        lib.slam_ham_eval.argtypes = ham + [P, P, C.c_int64, C.c_int32, P, P, P]
+        lib.slam_ham_minimize.argtypes = ham + [C.c_int32, C.POINTER(OptParams), C.c_double] + [P] * 10
     lib.slam_set_cost.argtypes = [P, C.c_int]
     lib.slam_synchronize.argtypes = [P]
     if hasattr(lib, "slam_host_alloc"):
@@ -1296,6 +1302,59 @@ class Context:
         ms = np.zeros(1, dtype=np.float64)
         _check(self._lib.slam_q3_minimize(self._h, _ptr(g), g.shape[0], k, _ptr(gi), _ptr(ed), _ptr(t), N, int(cost_kind), C.byref(params),
                                           float(exit_loss), _ptr(x0), *[_ptr(a) for a in out.values()], _ptr(ms)))
+        out["kernel_ms"] = float(ms[0])
+        return out
+
+    # -- Hamiltonian templates (slam_ham_*): self-contained calls, nothing resident ----------------------------------------------
+    @staticmethod
+    def _ham_description(terms, targets):
+        d, n = int(terms["dim"]), int(terms["n_params"])
+        m = np.ascontiguousarray(np.asarray(terms["matrices"], dtype=np.complex128))
+        if m.ndim != 3 or m.shape[1:] != (d, d):
+            raise ValueError(f"terms['matrices'] must have shape [K, {d}, {d}]")
+        si = np.ascontiguousarray(terms["s_index"], dtype=np.int32).reshape(-1)
+        pi = np.ascontiguousarray(terms["phi_index"], dtype=np.int32).reshape(-1)
+        if len(si) != len(m) or len(pi) != len(m):
+            raise ValueError("terms: one s_index and one phi_index per matrix")
+        t = np.ascontiguousarray(np.asarray(targets, dtype=np.complex128))
+        if t.ndim != 3 or t.shape[1:] != (d, d):
+            raise ValueError(f"expected targets of shape [N, {d}, {d}], got {t.shape}")
+        head = (d, n, len(m), _ptr(m.view(np.float64)), _ptr(si), _ptr(pi), int(terms["t_index"]))
+        return head, (m, si, pi), t.view(np.float64).reshape(t.shape + (2,)), d, n
+
+    def ham_eval(self, terms, targets, x, target_of=None, cost_kind: int = 0, want_grad=True, want_unitary=False):
+        """``slam_ham_eval``: loss [M], gradient [M, n] (or None) and unitary complex128 [M, dim, dim] (or None) of M parameter rows of
+        the Hamiltonian described by ``terms`` (``hamiltonian.Hamiltonian.device_terms()``), item m against ``targets[target_of[m]]``."""
+        head, keep, t, d, n = self._ham_description(terms, targets)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != n:
+            raise ValueError(f"x must have shape [M, {n}]")
+        M = x.shape[0]
+        tof = np.zeros(M, np.int32) if target_of is None else np.ascontiguousarray(target_of, dtype=np.int32)
+        if tof.shape != (M,):
+            raise ValueError("target_of must have shape [M]")
+        loss = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, n), dtype=np.float64) if want_grad else None
+        w = np.empty((M, d, d, 2), dtype=np.float64) if want_unitary else None
+        _check(self._lib.slam_ham_eval(self._h, *head, _ptr(t), t.shape[0], _ptr(x), _ptr(tof), M, int(cost_kind), _ptr(loss), _ptr(grad),
+                                       _ptr(w)))
+        return loss, grad, (None if w is None else w.view(np.complex128).reshape(M, d, d))
+
+    def ham_minimize(self, terms, targets, params: OptParams, exit_loss: float, x0, cost_kind: int = 0) -> dict:
+        """``slam_ham_minimize``: one stage over all targets x ``params.restarts`` from the start points ``x0`` [N, R, n]; the keys of
+        ``q3_minimize``."""
+        head, keep, t, d, n = self._ham_description(terms, targets)
+        N, R = t.shape[0], int(params.restarts)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0.shape != (N, R, n):
+            raise ValueError(f"x0 must have shape [{N}, {R}, {n}]")
+        out = {"best_loss": np.empty(N, dtype=np.float64), "best_x": np.empty((N, n), dtype=np.float64),
+               "best_restart": np.empty(N, dtype=np.int32), "item_loss": np.empty((N, R), dtype=np.float64),
+               "item_iters": np.empty((N, R), dtype=np.int32), "item_status": np.empty((N, R), dtype=np.int32),
+               "item_evals": np.empty((N, R), dtype=np.int32), "item_x": np.empty((N, R, n), dtype=np.float64)}
+        ms = np.zeros(1, dtype=np.float64)
+        _check(self._lib.slam_ham_minimize(self._h, *head, _ptr(t), N, int(cost_kind), C.byref(params), float(exit_loss), _ptr(x0),
+                                           *[_ptr(a) for a in out.values()], _ptr(ms)))
         out["kernel_ms"] = float(ms[0])
         return out
 

@@ -448,3 +448,42 @@ class MixedOrderBasisCircuitTemplate(CircuitTemplate):
                 self._sequence = None
                 return range(len(e), len(e) + 1)
         raise ValueError("Monodromy did not find a polytope containing U")  # polytope_wrap.py:91-93
+
+
+class HamiltonianTemplate(VariationalTemplate):
+    """``HamiltonianTemplate(h)`` (basis.py:24-48): no circuit -- the parameters are the arguments of ``h.construct_U`` (drive strengths,
+    phases, possibly the time) and the template's unitary is ``h.construct_U(*Xk)`` = exp(-i t H).  ``h`` is a
+    ``hamiltonian.Hamiltonian`` with a device description; ``TemplateOptimizer`` fits it on the GPU (csrc/slam_ham.hpp), every restart
+    from a start point drawn uniformly in [``start_low``, ``start_high``) -- scalars or per-parameter arrays; the reference's
+    ``np.random.random`` is the default [0, 1)."""
+
+    def __init__(self, h, start_low=0.0, start_high=1.0, device=0):
+        self.filename = None
+        self.h = h
+        self.device_terms = h.device_terms()  # (NotImplementedError for the host-only Hamiltonians)
+        self.n_params = int(h.n_params)
+        self.n_qubits = {4: 2, 8: 3}[int(h.dim)]
+        self.start_low = np.broadcast_to(np.asarray(start_low, dtype=np.float64), (self.n_params,)).copy()
+        self.start_high = np.broadcast_to(np.asarray(start_high, dtype=np.float64), (self.n_params,)).copy()
+        if not (np.all(np.isfinite(self.start_low)) and np.all(np.isfinite(self.start_high)) and np.all(self.start_low <= self.start_high)):
+            raise ValueError("start_low / start_high: finite, start_low <= start_high")
+        self.device = device
+        self.spanning_range = range(1)
+        self.using_bounds = False
+        self.using_constraints = False
+        self.bounds_list = None
+        self.constraint_func = None
+        super().__init__(preseed=False, use_polytopes=False)
+
+    def get_spanning_range(self, target_u):
+        return range(1, 2)  # only need to build once, in lieu of a circuit template
+
+    def eval(self, Xk):
+        return np.asarray(self.h.construct_U(*Xk))
+
+    def parameter_guess(self, t=1):
+        return np.random.uniform(self.start_low, self.start_high)
+
+    def start_points(self, seed, n_targets: int, restarts: int) -> np.ndarray:
+        """The start points of a batch, [n_targets, restarts, n_params]: ``default_rng(seed).uniform(low, high, ...)``."""
+        return np.random.default_rng(seed).uniform(self.start_low, self.start_high, (int(n_targets), int(restarts), self.n_params))

@@ -26,7 +26,7 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _ffi, runtime
-from .basis import CircuitTemplate
+from .basis import CircuitTemplate, HamiltonianTemplate
 from .basisv2 import CircuitTemplateV2
 from .basis3q import ThreeQubitCircuitTemplate
 from .basis_abc import DataDictEntry, LazyList, RowBlocks, TargetDataList, VariationalTemplate
@@ -118,6 +118,18 @@ class TemplateOptimizer:
         assert not (self.preseeding and self.override_fail)
         assert not (self.preseeding and self.basis.n_qubits != 2)
 
+        self._ham = isinstance(basis, HamiltonianTemplate)
+        if self._ham:
+            # Hamiltonian templates (basis.HamiltonianTemplate): BasicCost / SquareCost through the device's quasi-Newton loop, one stage,
+            # one device, start points drawn on the host
+            if not isinstance(objective, (BasicCost, SquareCost)):
+                raise NotImplementedError(f"{type(objective).__name__} on a HamiltonianTemplate: implemented are BasicCost and SquareCost")
+            if use_callback:
+                raise NotImplementedError("use_callback is not implemented for Hamiltonian templates")
+            if override_method not in (None, "BFGS"):
+                raise NotImplementedError(f"override_method={override_method!r} is not implemented for Hamiltonian templates (BFGS on the device)")
+            if devices is not None and len(list(devices)) > 1:
+                raise NotImplementedError("devices: Hamiltonian templates run on one device")
         self._q3 = isinstance(basis, ThreeQubitCircuitTemplate)
         if self._q3:
             # three-qubit templates (basis3q.py): BasicCost / SquareCost through the device's quasi-Newton loop, one device, ordered restarts
@@ -131,7 +143,7 @@ class TemplateOptimizer:
                 raise NotImplementedError("devices: three-qubit templates run on one device")
             if not deterministic:
                 raise NotImplementedError("deterministic=False is not implemented for three-qubit templates")
-        elif not isinstance(basis, (CircuitTemplate, CircuitTemplateV2)):
+        elif not self._ham and not isinstance(basis, (CircuitTemplate, CircuitTemplateV2)):
             raise NotImplementedError("the HIP optimizer needs a slam_decomposition_amd CircuitTemplate / CircuitTemplateV2")
         self._v2 = isinstance(basis, CircuitTemplateV2)
         # the reference's second branch (optimizer.py:203-205): the objective's start state through the template, the target ignored
@@ -932,6 +944,59 @@ class TemplateOptimizer:
             out.append(self._finish_target(invariant, float(best_loss[i]), best_xs[i], int(best_cycles[i]), invariant, index=i))
         return out
 
+    # ------------------------------------------------------------------------------------------
+    # Hamiltonian templates (basis.HamiltonianTemplate, csrc/slam_ham.hpp)
+    def _ham_targets(self, targets) -> np.ndarray:
+        d = int(self.basis.h.dim)
+        t = np.asarray(targets, dtype=np.complex128)
+        if t.ndim == 2:
+            t = t[None]
+        if t.ndim != 3 or t.shape[1:] != (d, d):
+            raise ValueError(f"targets of this Hamiltonian template must be {d}x{d} matrices")
+        return t
+
+    def _run_batch_ham(self, targets: np.ndarray):
+        """``_run`` (optimizer.py:233-303) for a Hamiltonian template: its spanning range is range(1, 2), so ONE device stage
+        (``slam_ham_minimize``) over the targets x ``training_restarts``, from the start points
+        ``default_rng(seed).uniform(start_low, start_high, (N, R, n))``; the result of a target is the lowest-index restart below the
+        threshold, otherwise the best seen (optimizer.py:281-303).  Returns (best_loss [N], list of parameter vectors, best_cycles
+        [N], all 1); the stage's per-item records stay in ``last_ham_stage``."""
+        n = len(targets)
+        prm = self._opt_params()
+        x0 = self.basis.start_points(self.seed, n, int(prm.restarts))
+        ctx = runtime.get_context(self.devices[0])
+        out = ctx.ham_minimize(self.basis.device_terms, targets, prm, self.success_threshold, x0, cost_kind=self._cost_kind)
+        self.last_ham_stage = out
+        self.span_best_losses = {1: np.array(out["best_loss"], dtype=np.float64)}
+        stats = {"kernel_ms": out["kernel_ms"], "kernel_launches": 1, "evals": [0] * (_ffi.MAX_SPAN_EVAL + 1),
+                 "items": [0] * (_ffi.MAX_SPAN_EVAL + 1), "kernel_ms_span": [0.0] * (_ffi.MAX_SPAN_EVAL + 1)}
+        stats["evals"][1] = int(out["item_evals"].sum())
+        stats["items"][1] = int(out["item_evals"].size)
+        stats["kernel_ms_span"][1] = out["kernel_ms"]
+        stats["total_ms"] = stats["kernel_ms"]
+        self._set_stats([stats])
+        return np.array(out["best_loss"], dtype=np.float64), [np.array(row) for row in out["best_x"]], np.ones(n, dtype=np.int64)
+
+    def _approximate_batch_ham(self, stacked: np.ndarray, log_index: bool):
+        from .weyl import c1c2c3
+
+        self.basis.assign_seed(None)
+        best_loss, best_xs, best_cycles = self._run_batch_ham(stacked)
+        two_qubit = stacked.shape[1:] == (4, 4)  # Weyl coordinates exist for 4x4 targets only (basis_abc.py:80-84)
+        out = []
+        for i in range(len(stacked)):
+            if log_index:
+                logging.info(f"Starting sample iter {i}")
+            invariant = self.basis.target_invariant(stacked[i])
+            logging.info(f"Begin search: {invariant}")
+            logging.info("Starting opt on template size 1")
+            logging.info(f"Cycle (k =1), Best Loss={float(best_loss[i])}")
+            if best_loss[i] < self.success_threshold:
+                logging.info("Break on cycle 1")
+            found = c1c2c3(self.basis.eval(best_xs[i])) if two_qubit else invariant
+            out.append(self._finish_target(invariant, float(best_loss[i]), best_xs[i], int(best_cycles[i]), found, index=i))
+        return out
+
     def _log_span_loop(self, i: int, spans) -> None:
         """The per-span log lines of ``_run`` (optimizer.py:234,297,302) for target i, from the running best loss
         the device recorded after every span."""
@@ -1029,6 +1094,10 @@ class TemplateOptimizer:
         """Atomic training function (optimizer.py:65-119)."""
         if self._state_objective:  # the objective does not look at the target (optimizer.py:203-205): None is fine
             return self._approximate_batch_3q(np.eye(8, dtype=np.complex128)[None], log_index=False)[0]
+        if self._ham:  # one target, or a list / array of them
+            t = self._ham_targets(target_U)
+            data = self._approximate_batch_ham(t, log_index=False)
+            return data[0] if np.ndim(target_U) == 2 else data
         t = np.asarray(target_U, dtype=np.complex128)
         if self._q3:
             if t.shape != (8, 8):
@@ -1043,6 +1112,10 @@ class TemplateOptimizer:
         if self._state_objective:  # one run per sample, whatever the sample is
             count = sum(1 for _ in sampler)
             target_data = self._approximate_batch_3q(np.tile(np.eye(8, dtype=np.complex128), (count, 1, 1)), log_index=True) if count else []
+            return self.training_loss, self.coordinate_list, target_data
+        if self._ham:  # a sampler, a list or an array of targets
+            targets = [np.asarray(t, dtype=np.complex128) for t in sampler]
+            target_data = self._approximate_batch_ham(self._ham_targets(np.stack(targets)), log_index=True) if targets else []
             return self.training_loss, self.coordinate_list, target_data
         if self._q3:
             targets = [np.asarray(t, dtype=np.complex128) for t in sampler]

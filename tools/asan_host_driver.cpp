@@ -451,6 +451,105 @@ int main() {
             EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
         }
     }
+    {  // slam_ham_eval, slam_ham_minimize: the description, the cost kind, targets, items and start points are checked before the context
+        static double mats[17][64][2] = {{{0}}}, tg[2][64][2] = {{{0}}}, xh[3][2] = {{0}}, x0h[2][3][2] = {{{0}}}, lossh[3], gradh[6], uh[3][64][2];
+        mats[0][2 * 4 + 1][0] = 1.0;  // (dim = 4: M_0[2][1]; read as dim = 8 the same doubles are M_0[1][1])
+        mats[1][3 * 4 + 0][0] = 1.0;
+        const double* m = &mats[0][0][0];
+        const double* t = &tg[0][0][0];
+        const double* x = &xh[0][0];
+        const double* x0 = &x0h[0][0][0];
+        const int32_t si[17] = {0, 1}, pi[17] = {-1, -1}, tof[3] = {0, 1, 0};
+        slam_opt_params hp = prm;
+        hp.restarts = 3;
+        hp.maxiter = 10;
+        auto ev = [&](int32_t dim, int32_t n, int32_t k, const double* mm, const int32_t* s, const int32_t* p, int32_t ti, const double* tt, int64_t nt,
+                      const double* xx, const int32_t* to, int64_t M, int32_t cost) {
+            return slam_ham_eval(nullptr, dim, n, k, mm, s, p, ti, tt, nt, xx, to, M, cost, lossh, gradh, &uh[0][0][0]);
+        };
+        auto mn = [&](int32_t dim, int32_t n, int32_t k, const double* mm, const int32_t* s, const int32_t* p, int32_t ti, const double* tt, int64_t nt,
+                      int32_t cost, const slam_opt_params* pp, const double* xx0) {
+            return slam_ham_minimize(nullptr, dim, n, k, mm, s, p, ti, tt, nt, cost, pp, 1e-10, xx0, d, gradh, i32, d, i32, i32, i32, nullptr, nullptr);
+        };
+        for (int32_t dim : {4, 8})
+            for (int32_t cost : {SLAM_COST_BASIC, SLAM_COST_SQUARE}) {
+                EXPECT(ev(dim, 2, 2, m, si, pi, -1, t, 2, x, tof, 3, cost) == SLAM_ERR_INVALID);
+                EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+                EXPECT(mn(dim, 2, 2, m, si, pi, 1, t, 2, cost, &hp, x0) == SLAM_ERR_INVALID);
+                EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+            }
+        for (int32_t dim : {0, 2, 5, 16}) {
+            EXPECT(ev(dim, 2, 2, m, si, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "dim must be") != nullptr);
+            EXPECT(mn(dim, 2, 2, m, si, pi, -1, t, 2, 0, &hp, x0) == SLAM_ERR_INVALID);
+        }
+        EXPECT(ev(4, SLAM_HAM_MAX_PARAMS + 1, 2, m, si, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(mn(4, SLAM_HAM_MAX_PARAMS + 1, 2, m, si, pi, -1, t, 2, 0, &hp, x0) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(ev(4, 2, SLAM_HAM_MAX_TERMS + 1, m, si, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(mn(4, 2, SLAM_HAM_MAX_TERMS + 1, m, si, pi, -1, t, 2, 0, &hp, x0) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(ev(4, 0, 2, m, si, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 2, 0, m, si, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 2, 2, nullptr, si, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 2, 2, m, nullptr, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 2, 2, m, si, nullptr, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+        {  // index arrays out of range
+            const int32_t s_hi[2] = {0, 2}, s_lo[2] = {-1, 0}, p_hi[2] = {-1, 2}, p_lo[2] = {-2, 0};
+            EXPECT(ev(4, 2, 2, m, s_hi, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "s_index[1]") != nullptr);
+            EXPECT(ev(4, 2, 2, m, s_lo, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(ev(4, 2, 2, m, si, p_hi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "phi_index[1]") != nullptr);
+            EXPECT(mn(4, 2, 2, m, si, p_lo, -1, t, 2, 0, &hp, x0) == SLAM_ERR_INVALID);
+            EXPECT(ev(4, 2, 2, m, si, pi, 2, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(mn(4, 2, 2, m, si, pi, -2, t, 2, 0, &hp, x0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "t_index") != nullptr);
+            const int32_t to_bad[3] = {0, 2, 0};
+            EXPECT(ev(4, 2, 2, m, si, pi, -1, t, 2, x, to_bad, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "target_of[1]") != nullptr);
+        }
+        for (double v : {std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::infinity()}) {
+            static double mb[2][64][2], tb[2][64][2], xb[3][2], x0b[2][3][2];
+            std::memcpy(mb, mats, sizeof mb);
+            mb[1][63][1] = v;  // (the last entry read at dim = 8: all of the array is looked at)
+            EXPECT(ev(8, 2, 2, &mb[0][0][0], si, pi, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "matrices") != nullptr);
+            EXPECT(mn(8, 2, 2, &mb[0][0][0], si, pi, -1, t, 2, 0, &hp, x0) == SLAM_ERR_INVALID);
+            std::memcpy(tb, tg, sizeof tb);
+            tb[1][63][1] = v;
+            EXPECT(ev(8, 2, 2, m, si, pi, -1, &tb[0][0][0], 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "targets") != nullptr);
+            EXPECT(mn(8, 2, 2, m, si, pi, -1, &tb[0][0][0], 2, 0, &hp, x0) == SLAM_ERR_INVALID);
+            std::memcpy(xb, xh, sizeof xb);
+            xb[2][1] = v;
+            EXPECT(ev(4, 2, 2, m, si, pi, -1, t, 2, &xb[0][0], tof, 3, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "x: entry 5") != nullptr);
+            std::memcpy(x0b, x0h, sizeof x0b);
+            x0b[1][2][1] = v;
+            EXPECT(mn(4, 2, 2, m, si, pi, -1, t, 2, 0, &hp, &x0b[0][0][0]) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "x0[11]") != nullptr);
+        }
+        {  // three terms on one entry
+            static double m3[3][16][2] = {{{0}}};
+            m3[0][9][0] = m3[1][9][0] = m3[2][9][0] = 1.0;
+            const int32_t s3[3] = {0, 1, 0}, p3[3] = {-1, -1, 1};
+            EXPECT(ev(4, 2, 3, &m3[0][0][0], s3, p3, -1, t, 2, x, tof, 3, 0) == SLAM_ERR_UNSUPPORTED);
+            EXPECT(std::strstr(slam_last_error(), "more than two contributions") != nullptr);
+        }
+        for (int32_t kind : {SLAM_COST_MAKHLIN, SLAM_COST_MUTUAL_INFO, SLAM_COST_MUTUAL_INFO_SQUARE, 5, -1}) {
+            EXPECT(ev(4, 2, 2, m, si, pi, -1, t, 2, x, tof, 3, kind) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "cost kind") != nullptr);
+            EXPECT(mn(4, 2, 2, m, si, pi, -1, t, 2, kind, &hp, x0) == SLAM_ERR_INVALID);
+        }
+        EXPECT(ev(4, 2, 2, m, si, pi, -1, nullptr, 2, x, tof, 3, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 2, 2, m, si, pi, -1, t, 0, x, tof, 3, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 2, 2, m, si, pi, -1, t, 2, nullptr, tof, 3, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 2, 2, m, si, pi, -1, t, 2, x, nullptr, 3, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 2, 2, m, si, pi, -1, t, 2, x, tof, 0, 0) == SLAM_ERR_INVALID);
+        EXPECT(mn(4, 2, 2, m, si, pi, -1, t, 2, 0, nullptr, x0) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "params is NULL") != nullptr);
+        EXPECT(mn(4, 2, 2, m, si, pi, -1, t, 2, 0, &hp, nullptr) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "x0 is required") != nullptr);
+    }
     EXPECT(slam_set_cost(nullptr, 0) == SLAM_ERR_INVALID);
     EXPECT(slam_synchronize(nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_get_stats(nullptr, &st) == SLAM_ERR_INVALID);
