@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := slam_decomposition_amd/csrc
-UNITS := slam_hip slam_v2_host slam_smush_host slam_geometry slam_analytic slam_q3_host slam_ham_host slam_comm
+UNITS := slam_hip slam_v2_host slam_smush_host slam_geometry slam_analytic slam_q3_host slam_ham_host slam_hams_host slam_comm
 OBJS  := $(UNITS:%=build/%.o)
 OUT   := slam_decomposition_amd/lib/libslamhip.so
 # -amdgpu-mfma-vgpr-form: the metric update's MFMAs (h_update_mfma) accumulate in VGPRs, where the metric lives, also in the kernels

@@ -966,6 +966,30 @@ int slam_ham_minimize(slam_ctx* ctx, int32_t dim, int32_t n_params, int32_t n_te
                       double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals, double* item_x, double* kernel_ms);
 
 /*
+ * Time-sliced Hamiltonian templates (csrc/slam_hams.hpp; the reference's ConversionGainSmush / ConversionGainSmush1QPhase,
+ * src/slam/hamiltonian.py:114-182): a piecewise-constant pulse of n_slices slices of equal length,
+ *   U(x) = U_S ... U_2 U_1,   U_s = exp(-i (t / S) H_s(x)),   H_s(x) = sum_k c_{s,k} M_k + h.c.,
+ *   c_{s,k} = x[s_index[s][k]] exp(i x[phi_index[s][k]])   (phi_index[s][k] = -1: phase 0),   t = x[t_index] (t_index = -1: t = 1);
+ * slice 0 acts first.  The term matrices are shared by the slices; a parameter may feed one slice, several or all of them.
+ * slam_hams_eval and slam_hams_minimize are slam_ham_eval and slam_ham_minimize -- arguments, checks before the context, outputs,
+ * status codes, ordered early exit and reduction over the restarts -- with
+ *   n_slices    in 1 .. SLAM_HAMS_MAX_SLICES (0 and below: SLAM_ERR_INVALID; above: SLAM_ERR_UNSUPPORTED)
+ *   s_index     int32[n_slices][n_terms]       in 0 .. n_params - 1
+ *   phi_index   int32[n_slices][n_terms]       in -1 .. n_params - 1
+ * and one difference in what a slice's Hamiltonian may hold: the two halves (M and its adjoint) of a phase-free term on a DIAGONAL entry
+ * count as one contribution of weight 2 Re M[r][r], so that two number operators may share an entry; the limit of two contributions
+ * per entry holds per slice.  n_slices = 1 computes what the slam_ham_* pair computes.
+ */
+#define SLAM_HAMS_MAX_SLICES 8
+int slam_hams_eval(slam_ctx* ctx, int32_t dim, int32_t n_params, int32_t n_terms, int32_t n_slices, const double* matrices, const int32_t* s_index,
+                   const int32_t* phi_index, int32_t t_index, const double* targets, int64_t n_targets, const double* x, const int32_t* target_of,
+                   int64_t M, int32_t cost_kind, double* loss, double* grad, double* unitary);
+int slam_hams_minimize(slam_ctx* ctx, int32_t dim, int32_t n_params, int32_t n_terms, int32_t n_slices, const double* matrices,
+                       const int32_t* s_index, const int32_t* phi_index, int32_t t_index, const double* targets, int64_t n_targets, int32_t cost_kind,
+                       const slam_opt_params* params, double exit_loss, const double* x0, double* best_loss, double* best_x, int32_t* best_restart,
+                       double* item_loss, int32_t* item_iters, int32_t* item_status, int32_t* item_evals, double* item_x, double* kernel_ms);
+
+/*
  * Multi-GPU: one process per GPU, RCCL over xGMI, reached through this ABI (no torch, no MPI).  The path shards by
  * target, every rank keeps all restarts of its targets, so the only exchange is the FINAL min-all-reduce of the
  * best-loss vector -- the running minimum of TemplateOptimizer._run (src/slam/optimizer.py:281-284) taken over the
@@ -1046,7 +1070,8 @@ const char* slam_version(void);
  *      later: slam_q3_eval and slam_q3_minimize (new symbols only);
  *      later: slam_q3m_eval and slam_q3m_minimize (new symbols only);
  *      later: slam_q3s_eval and slam_q3s_minimize (new symbols only);
- *      later: slam_ham_eval and slam_ham_minimize (new symbols only).
+ *      later: slam_ham_eval and slam_ham_minimize (new symbols only);
+ *      later: slam_hams_eval and slam_hams_minimize (new symbols only).
  * The Python binding refuses a library whose revision differs from the one it was written for. */
 #define SLAM_ABI_VERSION 7
 int slam_abi_version(void);

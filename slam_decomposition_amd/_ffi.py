@@ -119,6 +119,8 @@ EXPORTED_SYMBOLS = (
     "slam_q3s_minimize",
     "slam_ham_eval",
     "slam_ham_minimize",
+    "slam_hams_eval",
+    "slam_hams_minimize",
     "slam_set_cost",
     "slam_synchronize",
     "slam_host_alloc",
@@ -336,6 +338,10 @@ def load_library() -> C.CDLL:
         ham = [P, C.c_int32, C.c_int32, C.c_int32, P, P, P, C.c_int32, P, C.c_int64]
         lib.slam_ham_eval.argtypes = ham + [P, P, C.c_int64, C.c_int32, P, P, P]
         lib.slam_ham_minimize.argtypes = ham + [C.c_int32, C.POINTER(OptParams), C.c_double] + [P] * 10
+    if hasattr(lib, "slam_hams_eval"):
+        hams = [P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P, C.c_int32, P, C.c_int64]
+        lib.slam_hams_eval.argtypes = hams + [P, P, C.c_int64, C.c_int32, P, P, P]
+        lib.slam_hams_minimize.argtypes = hams + [C.c_int32, C.POINTER(OptParams), C.c_double] + [P] * 10
     lib.slam_set_cost.argtypes = [P, C.c_int]
     lib.slam_synchronize.argtypes = [P]
     if hasattr(lib, "slam_host_alloc"):
@@ -1312,19 +1318,34 @@ class Context:
         m = np.ascontiguousarray(np.asarray(terms["matrices"], dtype=np.complex128))
         if m.ndim != 3 or m.shape[1:] != (d, d):
             raise ValueError(f"terms['matrices'] must have shape [K, {d}, {d}]")
-        si = np.ascontiguousarray(terms["s_index"], dtype=np.int32).reshape(-1)
-        pi = np.ascontiguousarray(terms["phi_index"], dtype=np.int32).reshape(-1)
-        if len(si) != len(m) or len(pi) != len(m):
-            raise ValueError("terms: one s_index and one phi_index per matrix")
+        slices = terms.get("n_slices")  # None: one exponential (slam_ham_*); S: S time slices (slam_hams_*), index arrays [S, K]
+        si = np.ascontiguousarray(terms["s_index"], dtype=np.int32)
+        pi = np.ascontiguousarray(terms["phi_index"], dtype=np.int32)
+        if slices is None:
+            si, pi = si.reshape(-1), pi.reshape(-1)
+        if si.shape != pi.shape or si.shape != ((len(m),) if slices is None else (int(slices), len(m))):
+            raise ValueError("terms: one s_index and one phi_index per matrix" + ("" if slices is None else " and slice"))
         t = np.ascontiguousarray(np.asarray(targets, dtype=np.complex128))
         if t.ndim != 3 or t.shape[1:] != (d, d):
             raise ValueError(f"expected targets of shape [N, {d}, {d}], got {t.shape}")
-        head = (d, n, len(m), _ptr(m.view(np.float64)), _ptr(si), _ptr(pi), int(terms["t_index"]))
+        head = (d, n, len(m)) + (() if slices is None else (int(slices),)) + (_ptr(m.view(np.float64)), _ptr(si), _ptr(pi), int(terms["t_index"]))
         return head, (m, si, pi), t.view(np.float64).reshape(t.shape + (2,)), d, n
 
     def ham_eval(self, terms, targets, x, target_of=None, cost_kind: int = 0, want_grad=True, want_unitary=False):
         """``slam_ham_eval``: loss [M], gradient [M, n] (or None) and unitary complex128 [M, dim, dim] (or None) of M parameter rows of
         the Hamiltonian described by ``terms`` (``hamiltonian.Hamiltonian.device_terms()``), item m against ``targets[target_of[m]]``."""
+        if "n_slices" in terms:
+            raise ValueError("a time-sliced description goes to hams_eval")
+        return self._ham_eval(self._lib.slam_ham_eval, terms, targets, x, target_of, cost_kind, want_grad, want_unitary)
+
+    def hams_eval(self, terms, targets, x, target_of=None, cost_kind: int = 0, want_grad=True, want_unitary=False):
+        """``slam_hams_eval``: ``ham_eval`` for a time-sliced description (``hamiltonian.TimeSliced.device_terms()``: ``"n_slices"`` and
+        index arrays [S, K])."""
+        if "n_slices" not in terms:
+            raise ValueError("hams_eval takes a time-sliced description (terms['n_slices'])")
+        return self._ham_eval(self._lib.slam_hams_eval, terms, targets, x, target_of, cost_kind, want_grad, want_unitary)
+
+    def _ham_eval(self, call, terms, targets, x, target_of, cost_kind, want_grad, want_unitary):
         head, keep, t, d, n = self._ham_description(terms, targets)
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.ndim != 2 or x.shape[1] != n:
@@ -1336,13 +1357,23 @@ class Context:
         loss = np.empty(M, dtype=np.float64)
         grad = np.empty((M, n), dtype=np.float64) if want_grad else None
         w = np.empty((M, d, d, 2), dtype=np.float64) if want_unitary else None
-        _check(self._lib.slam_ham_eval(self._h, *head, _ptr(t), t.shape[0], _ptr(x), _ptr(tof), M, int(cost_kind), _ptr(loss), _ptr(grad),
-                                       _ptr(w)))
+        _check(call(self._h, *head, _ptr(t), t.shape[0], _ptr(x), _ptr(tof), M, int(cost_kind), _ptr(loss), _ptr(grad), _ptr(w)))
         return loss, grad, (None if w is None else w.view(np.complex128).reshape(M, d, d))
 
     def ham_minimize(self, terms, targets, params: OptParams, exit_loss: float, x0, cost_kind: int = 0) -> dict:
         """``slam_ham_minimize``: one stage over all targets x ``params.restarts`` from the start points ``x0`` [N, R, n]; the keys of
         ``q3_minimize``."""
+        if "n_slices" in terms:
+            raise ValueError("a time-sliced description goes to hams_minimize")
+        return self._ham_minimize(self._lib.slam_ham_minimize, terms, targets, params, exit_loss, x0, cost_kind)
+
+    def hams_minimize(self, terms, targets, params: OptParams, exit_loss: float, x0, cost_kind: int = 0) -> dict:
+        """``slam_hams_minimize``: ``ham_minimize`` for a time-sliced description."""
+        if "n_slices" not in terms:
+            raise ValueError("hams_minimize takes a time-sliced description (terms['n_slices'])")
+        return self._ham_minimize(self._lib.slam_hams_minimize, terms, targets, params, exit_loss, x0, cost_kind)
+
+    def _ham_minimize(self, call, terms, targets, params, exit_loss, x0, cost_kind):
         head, keep, t, d, n = self._ham_description(terms, targets)
         N, R = t.shape[0], int(params.restarts)
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
@@ -1353,8 +1384,8 @@ class Context:
                "item_iters": np.empty((N, R), dtype=np.int32), "item_status": np.empty((N, R), dtype=np.int32),
                "item_evals": np.empty((N, R), dtype=np.int32), "item_x": np.empty((N, R, n), dtype=np.float64)}
         ms = np.zeros(1, dtype=np.float64)
-        _check(self._lib.slam_ham_minimize(self._h, *head, _ptr(t), N, int(cost_kind), C.byref(params), float(exit_loss), _ptr(x0),
-                                           *[_ptr(a) for a in out.values()], _ptr(ms)))
+        _check(call(self._h, *head, _ptr(t), N, int(cost_kind), C.byref(params), float(exit_loss), _ptr(x0), *[_ptr(a) for a in out.values()],
+                    _ptr(ms)))
         out["kernel_ms"] = float(ms[0])
         return out
 

@@ -453,7 +453,9 @@ class MixedOrderBasisCircuitTemplate(CircuitTemplate):
 class HamiltonianTemplate(VariationalTemplate):
     """``HamiltonianTemplate(h)`` (basis.py:24-48): no circuit -- the parameters are the arguments of ``h.construct_U`` (drive strengths,
     phases, possibly the time) and the template's unitary is ``h.construct_U(*Xk)`` = exp(-i t H).  ``h`` is a
-    ``hamiltonian.Hamiltonian`` with a device description; ``TemplateOptimizer`` fits it on the GPU (csrc/slam_ham.hpp), every restart
+    ``hamiltonian.Hamiltonian`` with a device description -- also a piecewise-constant pulse, ``hamiltonian.TimeSliced`` or
+    ``ConversionGainSmush(n_slices=N)``, whose parameters are the flat ones --; ``TemplateOptimizer`` fits it on the GPU (csrc/slam_ham.hpp,
+    csrc/slam_hams.hpp), every restart
     from a start point drawn uniformly in [``start_low``, ``start_high``) -- scalars or per-parameter arrays; the reference's
     ``np.random.random`` is the default [0, 1)."""
 
@@ -479,7 +481,8 @@ class HamiltonianTemplate(VariationalTemplate):
         return range(1, 2)  # only need to build once, in lieu of a circuit template
 
     def eval(self, Xk):
-        return np.asarray(self.h.construct_U(*Xk))
+        flat = getattr(self.h, "construct_U_flat", None)  # (the time-sliced classes keep the reference's construct_U with drive vectors)
+        return np.asarray(flat(*Xk) if flat is not None else self.h.construct_U(*Xk))
 
     def parameter_guess(self, t=1):
         return np.random.uniform(self.start_low, self.start_high)

@@ -18,6 +18,7 @@
 //      any eigenbasis of a degenerate eigenvalue.
 // The 8x8 products go through three LDS matrices of 1 KB in the areas the q3 kernels use for their trig and gate tables; the LDS of a
 // wavefront stays kQ3LdsBytes.  The optimizer is slam_q3_minimize.inc around eval_ham; start points always come from the host (x0).
+// This header holds __device__ functions only (slam_hams.hpp uses them too); the two kernels are in slam_ham_kernels.hpp.
 //
 // Reference behaviour: HamiltonianTemplate src/slam/basis.py:24-48, src/slam/hamiltonian.py; BasicCost / SquareCost
 // src/slam/cost_function.py:140-145,169-173.
@@ -160,6 +161,65 @@ __device__ __forceinline__ double ham_sinc(double u, double sin_u) {
     return small ? p : sin_u / (small ? 1.0 : u);
 }
 
+// BasicCost / SquareCost of z = Tr(T^+ U) / d, and sigma = sr + i sim with d loss = Re(sigma dz)
+__device__ __forceinline__ double ham_cost(double zr, double zi, int dim, int cost_kind, double& sr, double& sim) {
+    const double az2 = fma(zr, zr, zi * zi);
+    const double rat = (az2 > 1e-300) ? fast_rsqrt(az2) : 0.0;
+    const double basic = 1.0 - az2 * rat;   // BasicCost, cost_function.py:140-145
+    const bool sq = (cost_kind == 1);       // SquareCost = d / (d + 1) (2 L - L^2) of BasicCost L (cost_function.py:169-173)
+    const double dd = dim == 4 ? 0.8 : 8.0 / 9.0;
+    const double c0 = sq ? 2.0 * dd : 1.0, c1 = sq ? -dd : 0.0;
+    const double fout = basic * fma(c1, basic, c0);
+    // sigma = -(d loss / d basic) conj(z) / |z|
+    const double dl = fma(2.0 * c1, basic, c0) * rat;
+    sr = -dl * zr;
+    sim = dl * zi;
+    return fout;
+}
+
+// The lane's entry of H from its two contributions q = 0, 1: packed indices iw, weights w2[q], parameters xs.  D_q = e^{+-i phi_q} w_q is
+// kept: dH[r][c] / ds_q = D_q, dH[r][c] / dphi_q = +-i s_q D_q
+struct HamEntry {
+    int si[2], pi[2];
+    double dr[2], di[2], sv[2], sgn[2];
+};
+template <bool HUGE_ARGS>
+__device__ __forceinline__ void ham_entry(uint32_t iw, const double2* w2, const double* xs, const double2* tbl, HamEntry& e, double& ar, double& ai) {
+    ar = 0.0;
+    ai = 0.0;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const uint32_t f = iw >> (16 * q);
+        e.si[q] = (int)(f & 63u) - 1;
+        e.pi[q] = (int)((f >> 6) & 63u) - 1;
+        e.sgn[q] = ((f >> 12) & 1u) ? -1.0 : 1.0;
+        const double2 w = w2[q];
+        e.sv[q] = e.si[q] >= 0 ? xs[e.si[q] >= 0 ? e.si[q] : 0] : 0.0;
+        const double ph = e.pi[q] >= 0 ? xs[e.pi[q] >= 0 ? e.pi[q] : 0] : 0.0;
+        double s, co;
+        if constexpr (HUGE_ARGS) sincos_any(ph, tbl, s, co);
+        else sincos_tbl(ph, tbl, s, co);
+        s *= e.sgn[q];
+        e.dr[q] = fma(co, w.x, -(s * w.y));
+        e.di[q] = fma(co, w.y, s * w.x);
+        ar = fma(e.sv[q], e.dr[q], ar);
+        ai = fma(e.sv[q], e.di[q], ai);
+    }
+}
+// d/ds_q and d/dphi_q of Re(kappa H[r][c]) for the lane's two contributions, kappa = kar + i kai
+__device__ __forceinline__ void ham_entry_grad(const HamEntry& e, double kar, double kai, double (&gstr)[2], double (&gphi)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        gstr[q] = fma(kar, e.dr[q], -(kai * e.di[q]));
+        gphi[q] = -(e.sgn[q] * e.sv[q]) * fma(kar, e.di[q], kai * e.dr[q]);
+    }
+}
+// what of them goes to parameter j
+__device__ __forceinline__ void ham_entry_share(const HamEntry& e, const double (&gstr)[2], const double (&gphi)[2], int j, double& v) {
+    v = (e.si[0] == j ? gstr[0] : 0.0) + (e.pi[0] == j ? gphi[0] : 0.0);
+    v += (e.si[1] == j ? gstr[1] : 0.0) + (e.pi[1] == j ? gphi[1] : 0.0);
+}
+
 // the entry lists into LDS (once per launch); the caller fences
 __device__ __forceinline__ void ham_prologue(double* lds, const HamDesc& h) {
     const int lane = threadIdx.x;
@@ -192,28 +252,11 @@ __device__ __forceinline__ double eval_ham(double* lds, double tre, double tim, 
         if constexpr (HUGE_ARGS) sincos_any(arg, tbl, s, co);
         else sincos_tbl(arg, tbl, s, co);
     };
-    // ---- 1. the lane's entry of H; D_q = e^{+-i phi_q} w_q is kept: dH[r][c] / ds_q = D_q, dH[r][c] / dphi_q = +-i s_q D_q
-    const uint32_t iw = reinterpret_cast<const uint32_t*>(lds + kHamOffIdx)[lane];
-    int si[2], pi[2];
-    double dr[2], di[2], sv[2], sgn[2];
-    double ar = 0.0, ai = 0.0;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const uint32_t f = iw >> (16 * q);
-        si[q] = (int)(f & 63u) - 1;
-        pi[q] = (int)((f >> 6) & 63u) - 1;
-        sgn[q] = ((f >> 12) & 1u) ? -1.0 : 1.0;
-        const double2 w = reinterpret_cast<const double2*>(lds + kHamOffW)[2 * lane + q];
-        sv[q] = si[q] >= 0 ? xs[si[q] >= 0 ? si[q] : 0] : 0.0;
-        const double ph = pi[q] >= 0 ? xs[pi[q] >= 0 ? pi[q] : 0] : 0.0;
-        double s, co;
-        sc(ph, s, co);
-        s *= sgn[q];
-        dr[q] = fma(co, w.x, -(s * w.y));
-        di[q] = fma(co, w.y, s * w.x);
-        ar = fma(sv[q], dr[q], ar);
-        ai = fma(sv[q], di[q], ai);
-    }
+    // ---- 1. the lane's entry of H
+    HamEntry en;
+    double ar, ai;
+    ham_entry<HUGE_ARGS>(reinterpret_cast<const uint32_t*>(lds + kHamOffIdx)[lane], reinterpret_cast<const double2*>(lds + kHamOffW) + 2 * lane, xs,
+                         tbl, en, ar, ai);
     const double t = t_index >= 0 ? xs[t_index >= 0 ? t_index : 0] : 1.0;
     // ---- 2. parallel Jacobi
     double vr = (r == c) ? 1.0 : 0.0, vi = 0.0;
@@ -253,16 +296,8 @@ __device__ __forceinline__ double eval_ham(double* lds, double tre, double tim, 
     const bool diag = r == c;
     const double zr = wave_sum(diag ? qr : 0.0) * inv_d, zi = wave_sum(diag ? qi : 0.0) * inv_d;
     const double ur = wave_sum(diag ? lr * qr : 0.0) * inv_d, ui = wave_sum(diag ? lr * qi : 0.0) * inv_d;  // dz/dt = -i (ur + i ui)
-    const double az2 = fma(zr, zr, zi * zi);
-    const double rat = (az2 > 1e-300) ? fast_rsqrt(az2) : 0.0;
-    const double basic = 1.0 - az2 * rat;   // BasicCost, cost_function.py:140-145
-    const bool sq = (cost_kind == 1);       // SquareCost = d / (d + 1) (2 L - L^2) of BasicCost L (cost_function.py:169-173)
-    const double dd = dim == 4 ? 0.8 : 8.0 / 9.0;
-    const double c0 = sq ? 2.0 * dd : 1.0, c1 = sq ? -dd : 0.0;
-    const double fout = basic * fma(c1, basic, c0);
-    // d loss = Re(sigma dz), sigma = -(d loss / d basic) conj(z) / |z|
-    const double dl = fma(2.0 * c1, basic, c0) * rat;
-    const double sr = -dl * zr, sim = dl * zi;
+    double sr, sim;
+    const double fout = ham_cost(zr, zi, dim, cost_kind, sr, sim);
     if constexpr (WANT_U) {
         double2* ev = reinterpret_cast<double2*>(lds + kHamOffE);
         if (diag) ev[r] = make_double2(fr, fi);
@@ -293,17 +328,13 @@ __device__ __forceinline__ double eval_ham(double* lds, double tre, double tim, 
     const double mr = t * inv_d * sim, mi = -(t * inv_d * sr);
     const double kar = fma(mr, kr, -(mi * ki)), kai = fma(mr, ki, mi * kr);
     double gstr[2], gphi[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        gstr[q] = fma(kar, dr[q], -(kai * di[q]));
-        gphi[q] = -(sgn[q] * sv[q]) * fma(kar, di[q], kai * dr[q]);
-    }
+    ham_entry_grad(en, kar, kai, gstr, gphi);
     const double gt = fma(sr, ui, sim * ur);  // Re(sigma (-i)(ur + i ui))
     double mine = 0.0;
 #pragma unroll 1
     for (int j = 0; j < n; ++j) {
-        double v = (si[0] == j ? gstr[0] : 0.0) + (pi[0] == j ? gphi[0] : 0.0);
-        v += (si[1] == j ? gstr[1] : 0.0) + (pi[1] == j ? gphi[1] : 0.0);
+        double v;
+        ham_entry_share(en, gstr, gphi, j, v);
         double tot = wave_sum(v);
         if (j == t_index) tot += gt;
         if (lane == j) mine = tot;
@@ -311,47 +342,6 @@ __device__ __forceinline__ double eval_ham(double* lds, double tre, double tim, 
     if (lane < n) gs[lane] = mine;
     lds_fence();
     return fout;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// slam_ham_eval: one item per wavefront, grid-stride
-// ---------------------------------------------------------------------------------------------------------------------------
-// (two wavefronts per SIMD: with the unitary wanted and the any-argument sincos path the evaluation does not fit 128 registers)
-__global__ void __launch_bounds__(kWave, 2) eval_ham_kernel(HamEvalArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int lane = threadIdx.x;
-    const int n = a.h.n;
-    ham_prologue(lds, a.h);
-    const int ent = ((lane & 7) * 8 + (lane >> 3)) * 2;  // entry (r, c) of a row-major 8x8
-    for (int64_t m = blockIdx.x; m < a.n_items; m += gridDim.x) {
-#pragma unroll
-        for (int s = 0; s < kQ3Slots; ++s) {
-            const int i = 2 * lane + s;
-            lds[kQ3OffX + i] = i < n ? a.x[m * n + i] : 0.0;
-        }
-        lds_fence();
-        const double2 t = q3_item_entry<false>(a.targets, (int64_t)a.target_of[m], lane, ent);
-        double wr = 0.0, wi = 0.0;
-        const double f = eval_ham<true, true>(lds, t.x, t.y, n, a.h.t_index, a.h.dim, a.cost_kind, wr, wi);
-        if (lane == 0) a.loss[m] = f;
-        if (a.grad && lane < n) a.grad[m * n + lane] = lds[kQ3OffG + lane];
-        if (a.unitary) *reinterpret_cast<double2*>(a.unitary + m * 128 + ent) = make_double2(wr, wi);
-        lds_fence();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// slam_ham_minimize: the optimizer body of the three-qubit templates around eval_ham
-// ---------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kWave, 3) minimize_ham_kernel(HamArgs args) {
-    constexpr bool STATE = false;
-#define Q3_MIN_SETUP const int n = args.h.n;
-#define Q3_MIN_PROLOGUE ham_prologue(lds, args.h);
-#define Q3_MIN_EVAL eval_ham<false, false>(lds, tre, tim, n, args.h.t_index, args.h.dim, args.cost_kind, wre, wim)
-#include "slam_q3_minimize.inc"
-#undef Q3_MIN_SETUP
-#undef Q3_MIN_PROLOGUE
-#undef Q3_MIN_EVAL
 }
 
 }  // namespace slamdev

@@ -1,6 +1,6 @@
 // slam_host.hpp -- what the host units of libslamhip.so share (internal: not installed, not part of the C ABI).
 // The units: slam_hip.hip (context, plain templates, the decompose family), slam_v2_host.hip, slam_smush_host.hip,
-// slam_geometry.hip, slam_analytic.hip, slam_q3_host.hip, slam_ham_host.hip and slam_comm.hip.  Every __global__ kernel is emitted by exactly one of them: a header that defines
+// slam_geometry.hip, slam_analytic.hip, slam_q3_host.hip, slam_ham_host.hip, slam_hams_host.hip and slam_comm.hip.  Every __global__ kernel is emitted by exactly one of them: a header that defines
 // kernels (slam_kernels.hpp, slam_long_kernels.hpp, slam_geometry_kernels.hpp, ...) is included by its owner alone, and the headers that
 // several units include (slam_weyl.hpp, slam_pd.hpp, slam_kak.hpp) hold __device__ functions only.  Where a unit needs another unit's
 // kernel it calls the enqueue_* function of the owner declared below.  Everything declared here has hidden visibility.

@@ -1,4 +1,4 @@
-// slam_q3_minimize.inc -- body of minimize_q3_kernel (slam_q3.hpp) and minimize_ham_kernel (slam_ham.hpp): the quasi-Newton iteration of
+// slam_q3_minimize.inc -- body of minimize_q3_kernel (slam_q3.hpp), minimize_ham_kernel (slam_ham_kernels.hpp) and minimize_hams_kernel (slam_hams.hpp): the quasi-Newton iteration of
 // slam_long_minimize.inc (its body, copied) for one wavefront per item and n <= 2 * 64 parameters, n possibly odd.  Included inside the
 // kernel with the constant STATE (and whatever its macros use) and three macros defined: Q3_MIN_SETUP declares n (and what the evaluation needs) from args
 // and k, Q3_MIN_PROLOGUE fills the wavefront's LDS once per launch, Q3_MIN_EVAL is the evaluation -- x from lds[kQ3OffX ..], the loss

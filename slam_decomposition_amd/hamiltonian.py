@@ -8,6 +8,10 @@ Every class has ``H(*args)`` (an ``ndarray``), a static ``construct_U(*args)`` =
 
 with M_k dense dim x dim matrices and all indices positions among ``construct_U``'s arguments.  Operators and basis order are those of
 ``gates.circulator_hamiltonian``: the raising operator is [[0, 0], [1, 0]] and mode a is the left Kronecker factor.
+
+Piecewise-constant pulses -- ``TimeSliced(h, n_slices, sliced=...)``, ``ConversionGainSmush(n_slices=N)`` and
+``ConversionGainSmush1QPhase(n_slices=N)`` -- are products of S slice exponentials exp(-i (t / S) H_s), slice 0 acting first; their
+``device_terms()`` carries ``"n_slices"`` and index arrays [S, K] (csrc/slam_hams.hpp), and ``slice_terms(s)`` is slice s alone.
 """
 from __future__ import annotations
 
@@ -19,6 +23,7 @@ from .gates import circulator_hamiltonian
 
 MAX_TERMS = 16   # SLAM_HAM_MAX_TERMS
 MAX_PARAMS = 32  # SLAM_HAM_MAX_PARAMS
+MAX_SLICES = 8   # SLAM_HAMS_MAX_SLICES
 
 _UP = np.array([[0, 0], [1, 0]], dtype=np.complex128)
 _ONE = np.eye(2, dtype=np.complex128)
@@ -99,7 +104,8 @@ class _TwoMode(Hamiltonian):
 
     def _term_matrices(self):
         A, B = _modes(2)
-        ops = {"conv": A @ B.conj().T, "gain": A @ B}
+        # (x_a, x_b: the single-qubit drives A + h.c., B + h.c.; z_a, z_b: A^+ A and B^+ B, halved because the description adds h.c.)
+        ops = {"conv": A @ B.conj().T, "gain": A @ B, "x_a": A, "x_b": B, "z_a": 0.5 * A.conj().T @ A, "z_b": 0.5 * B.conj().T @ B}
         return [ops[o] for o, _, _ in self._TERMS]
 
 
@@ -190,6 +196,136 @@ class DeltaConversionGainHamiltonian(_ThreeMode):
                                                                     c_ab, c_ac, c_bc)(1)
 
 
+# ---- piecewise-constant pulses: products of slice exponentials ----------------------------------------------------------------------
+class _Slices:
+    """How the flat parameters of an S-slice pulse map onto the arguments of one slice: ``names`` are the slice Hamiltonian's arguments
+    (strengths and phases, the time not among them), ``sliced`` those that get one flat parameter per slice.  Flat order: the shared
+    arguments in their order, then per sliced argument (in their order) its S copies ``name0 .. name{S-1}``, then the time."""
+
+    def __init__(self, names, sliced, n_slices, has_time):
+        if not (isinstance(n_slices, (int, np.integer)) and 1 <= int(n_slices) <= MAX_SLICES):
+            raise ValueError(f"n_slices must be an integer in 1 .. {MAX_SLICES} (got {n_slices!r})")
+        sliced = tuple(sliced)
+        for name in sliced:
+            if name not in names:
+                raise ValueError(f"{name!r} is not a strength or phase argument ({', '.join(names)})")
+        self.n_slices = S = int(n_slices)
+        shared = [a for a in names if a not in sliced]
+        per_slice = [a for a in names if a in sliced]
+        self.flat_names = tuple(shared + [f"{a}{s}" for a in per_slice for s in range(S)] + (["t"] if has_time else []))
+        if len(self.flat_names) > MAX_PARAMS:
+            raise ValueError(f"{len(self.flat_names)} parameters: the device takes at most {MAX_PARAMS}")
+        # position among the flat parameters of argument `a` in slice s
+        self.position = [{a: (shared.index(a) if a in shared else len(shared) + per_slice.index(a) * S + s) for a in names} for s in range(S)]
+        self.names = tuple(names)
+        self.t_index = len(self.flat_names) - 1 if has_time else -1
+
+    def slice_args(self, x, s):
+        return [float(x[self.position[s][a]]) for a in self.names]
+
+    def time(self, x):
+        return float(x[self.t_index]) if self.t_index >= 0 else 1.0
+
+    def terms(self, dim, matrices, term_names):
+        """``term_names``: per term (strength argument, phase argument or None)"""
+        return {
+            "dim": dim,
+            "n_params": len(self.flat_names),
+            "n_slices": self.n_slices,
+            "matrices": np.stack(matrices),
+            "s_index": np.array([[pos[sn] for sn, _ in term_names] for pos in self.position], dtype=np.int32),
+            "phi_index": np.array([[-1 if pn is None else pos[pn] for _, pn in term_names] for pos in self.position], dtype=np.int32),
+            "t_index": self.t_index,
+        }
+
+
+def slice_terms(terms: dict, s: int) -> dict:
+    """Slice s of a time-sliced description as a description of one exponential (for ``assemble``); its time is the whole pulse's."""
+    out = {k: v for k, v in terms.items() if k != "n_slices"}
+    out["s_index"], out["phi_index"] = terms["s_index"][s], terms["phi_index"][s]
+    return out
+
+
+class TimeSliced(Hamiltonian):
+    """``TimeSliced(h, n_slices, sliced=("g_ab", ...))``: the pulse U = U_S ... U_1, U_s = exp(-i (t / S) H_s), of any Hamiltonian ``h``
+    with a device description; the strength or phase arguments named in ``sliced`` take one value per slice (``g_ab0 .. g_ab{S-1}``), the
+    others are shared by the slices, and the time, if ``h`` has one, stays last.  With all slices equal it is ``h``."""
+
+    def __init__(self, h, n_slices, sliced=()):
+        base = h.device_terms()  # (NotImplementedError for the host-only Hamiltonians)
+        names = h.parameter_names
+        ti = base["t_index"]
+        args = [a for i, a in enumerate(names) if i != ti]
+        self.h = h
+        self.dim = int(base["dim"])
+        self._map = _Slices(args, sliced, n_slices, ti >= 0)
+        self.n_slices = self._map.n_slices
+        self._base = base
+        self._term_names = [(names[s], None if p < 0 else names[p]) for s, p in zip(base["s_index"], base["phi_index"])]
+        self._full = lambda a, t: a + [t] if ti >= 0 else a  # (the time is the last argument of every device Hamiltonian that has one)
+        assert ti in (-1, len(names) - 1)
+
+    def __repr__(self):
+        return f"TimeSliced({self.h!r}, {self.n_slices})"
+
+    @property
+    def parameter_names(self):
+        return self._map.flat_names
+
+    def device_terms(self) -> dict:
+        return self._map.terms(self.dim, self._base["matrices"], self._term_names)
+
+    def H(self, *x, s=0):
+        """H of slice s at the flat parameters (the time among them is ignored)"""
+        return assemble(self._base, np.asarray(self._full(self._map.slice_args(x, s), 0.0)))
+
+    def construct_U(self, *x):
+        S, t = self.n_slices, self._map.time(x)
+        total = np.eye(self.dim, dtype=np.complex128)
+        for s in range(S):
+            total = expm_hermitian(self.H(*x, s=s), t / S) @ total
+        return total
+
+    construct_U_flat = construct_U
+
+
+class _SlicedDrives:
+    """What ``ConversionGainSmush(n_slices=N)`` and ``ConversionGainSmush1QPhase(n_slices=N)`` add to the host-only classes: the flat
+    parameters (...scalars in the reference's order..., gx0 .. gx{N-1}, gy0 .. gy{N-1}, t), ``construct_U_flat`` and the device description.
+    Without ``n_slices`` nothing changes: ``construct_U`` takes the drive vectors and there is no device description."""
+
+    _HOST_ONLY = ""
+
+    def __init__(self, n_slices=None):
+        self.n_slices = None
+        if n_slices is not None:
+            args = tuple(signature(type(self).H).parameters)[1:]
+            self._map = _Slices(args, ("gx", "gy"), n_slices, True)
+            self.n_slices = self._map.n_slices
+
+    def __repr__(self):
+        return type(self).__name__ + ("" if self.n_slices is None else f"(n_slices={self.n_slices})")
+
+    @property
+    def parameter_names(self):
+        return super().parameter_names if self.n_slices is None else self._map.flat_names
+
+    def device_terms(self) -> dict:
+        if self.n_slices is None:
+            raise NotImplementedError(self._HOST_ONLY)
+        return self._map.terms(self.dim, self._term_matrices(), [(s, p) for _, s, p in self._TERMS])
+
+    def construct_U_flat(self, *x):
+        """``construct_U`` at the flat parameters"""
+        if self.n_slices is None:
+            raise NotImplementedError(self._HOST_ONLY)
+        N = self.n_slices
+        if len(x) != 2 * N + len(self._map.names) - 2 + 1:
+            raise ValueError(f"expected {len(self._map.flat_names)} parameters, got {len(x)}")
+        k = len(x) - 2 * N - 1
+        return type(self).construct_U(*x[:k], list(x[k:k + N]), list(x[k + N:k + 2 * N]), x[-1])
+
+
 # ---- host-only classes (import parity): no device description -----------------------------------------------------------------------
 class FSimHamiltonian(Hamiltonian):
     """H = g (s+ s- + s- s+) + g^2 / |eta| sz sz (hamiltonian.py:220-241, arXiv:1910.11333)."""
@@ -217,8 +353,12 @@ def _sliced_U(h_of_slice, gxvector, gyvector, t):
     return total
 
 
-class ConversionGainSmush(_TwoMode):
-    """Conversion / gain with single-qubit x drives that change from time slice to time slice (hamiltonian.py:114-144)."""
+class ConversionGainSmush(_SlicedDrives, _TwoMode):
+    """Conversion / gain with single-qubit x drives that change from time slice to time slice (hamiltonian.py:114-144).
+    ``ConversionGainSmush(n_slices=N)`` has a device description (see ``_SlicedDrives``)."""
+
+    _TERMS = (("x_a", "gx", None), ("x_b", "gy", None), ("conv", "gc", "phi_c"), ("gain", "gg", "phi_g"))
+    _HOST_ONLY = "ConversionGainSmush: a product of time slices, not one exp(-i t H) (see parallel_drive.py)"
 
     def H(self, phi_c, phi_g, gc, gg, gx, gy):
         A, B = _modes(2)
@@ -232,12 +372,13 @@ class ConversionGainSmush(_TwoMode):
         h = ConversionGainSmush()
         return _sliced_U(lambda gx, gy: h.H(phi_c, phi_g, gc, gg, gx, gy), gxvector, gyvector, t)
 
-    def device_terms(self):
-        raise NotImplementedError("ConversionGainSmush: a product of time slices, not one exp(-i t H) (see parallel_drive.py)")
 
-
-class ConversionGainSmush1QPhase(_TwoMode):
+class ConversionGainSmush1QPhase(_SlicedDrives, _TwoMode):
     """As ConversionGainSmush with phases on the single-qubit drives and z terms (hamiltonian.py:147-182)."""
+
+    _TERMS = (("x_a", "gx", "phi_a"), ("x_b", "gy", "phi_b"), ("conv", "gc", "phi_c"), ("gain", "gg", "phi_g"), ("z_a", "gz1", None),
+              ("z_b", "gz2", None))
+    _HOST_ONLY = "ConversionGainSmush1QPhase: a product of time slices, not one exp(-i t H) (see parallel_drive.py)"
 
     def H(self, phi_a, phi_b, phi_c, phi_g, gc, gg, gz1, gz2, gx, gy):
         A, B = _modes(2)
@@ -252,6 +393,3 @@ class ConversionGainSmush1QPhase(_TwoMode):
     def construct_U(phi_a, phi_b, phi_c, phi_g, gc, gg, gz1, gz2, gxvector, gyvector, t=1):
         h = ConversionGainSmush1QPhase()
         return _sliced_U(lambda gx, gy: h.H(phi_a, phi_b, phi_c, phi_g, gc, gg, gz1, gz2, gx, gy), gxvector, gyvector, t)
-
-    def device_terms(self):
-        raise NotImplementedError("ConversionGainSmush1QPhase: a product of time slices, not one exp(-i t H) (see parallel_drive.py)")

@@ -965,7 +965,9 @@ class TemplateOptimizer:
         prm = self._opt_params()
         x0 = self.basis.start_points(self.seed, n, int(prm.restarts))
         ctx = runtime.get_context(self.devices[0])
-        out = ctx.ham_minimize(self.basis.device_terms, targets, prm, self.success_threshold, x0, cost_kind=self._cost_kind)
+        # (a piecewise-constant pulse -- a description with "n_slices" -- goes to the time-sliced stage, slam_hams_minimize)
+        minimize = ctx.hams_minimize if "n_slices" in self.basis.device_terms else ctx.ham_minimize
+        out = minimize(self.basis.device_terms, targets, prm, self.success_threshold, x0, cost_kind=self._cost_kind)
         self.last_ham_stage = out
         self.span_best_losses = {1: np.array(out["best_loss"], dtype=np.float64)}
         stats = {"kernel_ms": out["kernel_ms"], "kernel_launches": 1, "evals": [0] * (_ffi.MAX_SPAN_EVAL + 1),

@@ -12,7 +12,8 @@ SAN="-fsanitize=address,undefined -fno-gpu-sanitize -fno-omit-frame-pointer -g -
 $HIPCC --offload-arch=gfx950 -std=c++17 -fPIC -shared $SAN -shared-libsan -Wno-unused-function \
     -o build/asan/libslamhip_asan.so slam_decomposition_amd/csrc/slam_hip.hip slam_decomposition_amd/csrc/slam_v2_host.hip \
     slam_decomposition_amd/csrc/slam_smush_host.hip slam_decomposition_amd/csrc/slam_geometry.hip slam_decomposition_amd/csrc/slam_analytic.hip \
-    slam_decomposition_amd/csrc/slam_q3_host.hip slam_decomposition_amd/csrc/slam_ham_host.hip slam_decomposition_amd/csrc/slam_comm.hip -ldl
+    slam_decomposition_amd/csrc/slam_q3_host.hip slam_decomposition_amd/csrc/slam_ham_host.hip slam_decomposition_amd/csrc/slam_hams_host.hip \
+    slam_decomposition_amd/csrc/slam_comm.hip -ldl
 $HIPCC -std=c++17 $SAN -shared-libsan -x c++ tools/asan_host_driver.cpp -o build/asan/driver -Lbuild/asan -lslamhip_asan -Wl,-rpath,'$ORIGIN' -lpthread
 RT=$(dirname "$($HIPCC -print-file-name=libclang_rt.asan-x86_64.so 2>/dev/null || true)")
 [ -d "$RT" ] || RT=$(dirname "$(find "$(dirname "$HIPCC")/../lib/llvm" -name 'libclang_rt.asan-x86_64.so' | head -1)")

@@ -550,6 +550,60 @@ int main() {
         EXPECT(mn(4, 2, 2, m, si, pi, -1, t, 2, 0, &hp, nullptr) == SLAM_ERR_INVALID);
         EXPECT(std::strstr(slam_last_error(), "x0 is required") != nullptr);
     }
+    {  // slam_hams_eval, slam_hams_minimize: the per-slice index rows and entry lists, the diagonal merge, everything before the context
+        static double mats[4][16][2] = {{{0}}}, tg[2][16][2] = {{{0}}}, xh[3][4] = {{0}}, x0h[2][3][4] = {{{0}}}, lossh[3], gradh[12], uh[3][16][2];
+        mats[0][2 * 4 + 1][0] = 1.0;
+        mats[1][3 * 4 + 0][0] = 1.0;
+        mats[2][0][0] = mats[2][1 * 4 + 1][0] = 0.5;  // two diagonal terms that share entry (0, 0)
+        mats[3][0][0] = mats[3][2 * 4 + 2][0] = 0.5;
+        const double* m = &mats[0][0][0];
+        const double* t = &tg[0][0][0];
+        constexpr int S = SLAM_HAMS_MAX_SLICES;
+        int32_t si[S][4], pi[S][4];
+        for (int s = 0; s < S; ++s)
+            for (int k = 0; k < 4; ++k) {
+                si[s][k] = (k + s) % 4;
+                pi[s][k] = k < 2 ? (s % 2 ? 3 : -1) : -1;
+            }
+        const int32_t tof[3] = {0, 1, 0};
+        slam_opt_params hp = prm;
+        hp.restarts = 3;
+        hp.maxiter = 10;
+        auto ev = [&](int32_t n, int32_t k, int32_t slices, const int32_t* s, const int32_t* p, int32_t ti, int32_t cost) {
+            return slam_hams_eval(nullptr, 4, n, k, slices, m, s, p, ti, t, 2, &xh[0][0], tof, 3, cost, lossh, gradh, &uh[0][0][0]);
+        };
+        auto mn = [&](int32_t n, int32_t k, int32_t slices, const int32_t* s, const int32_t* p, int32_t ti, int32_t cost, const double* xx0) {
+            return slam_hams_minimize(nullptr, 4, n, k, slices, m, s, p, ti, t, 2, cost, &hp, 1e-10, xx0, d, gradh, i32, d, i32, i32, i32, nullptr, nullptr);
+        };
+        for (int32_t slices = 1; slices <= S; ++slices) {  // good descriptions: the context is looked at last
+            EXPECT(ev(4, 4, slices, &si[0][0], &pi[0][0], 3, SLAM_COST_SQUARE) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+            EXPECT(mn(4, 4, slices, &si[0][0], &pi[0][0], -1, SLAM_COST_BASIC, &x0h[0][0][0]) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+        }
+        EXPECT(ev(4, 4, 0, &si[0][0], &pi[0][0], -1, 0) == SLAM_ERR_INVALID);
+        EXPECT(ev(4, 4, S + 1, &si[0][0], &pi[0][0], -1, 0) == SLAM_ERR_UNSUPPORTED);
+        EXPECT(std::strstr(slam_last_error(), "n_slices") != nullptr);
+        EXPECT(mn(4, 4, -3, &si[0][0], &pi[0][0], -1, 0, &x0h[0][0][0]) == SLAM_ERR_INVALID);
+        {  // an index out of range in the last slice only; a diagonal term on a phase is not merged
+            int32_t sb[S][4], pb[S][4];
+            std::memcpy(sb, si, sizeof sb);
+            std::memcpy(pb, pi, sizeof pb);
+            sb[S - 1][3] = 4;
+            EXPECT(ev(4, 4, S, &sb[0][0], &pi[0][0], -1, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "slice 7: s_index[3]") != nullptr);
+            EXPECT(ev(4, 4, S - 1, &sb[0][0], &pi[0][0], -1, 0) == SLAM_ERR_INVALID);
+            EXPECT(std::strstr(slam_last_error(), "ctx is NULL") != nullptr);
+            pb[2][2] = pb[2][3] = 0;
+            EXPECT(mn(4, 4, S, &si[0][0], &pb[0][0], -1, 0, &x0h[0][0][0]) == SLAM_ERR_UNSUPPORTED);
+            EXPECT(std::strstr(slam_last_error(), "slice 2: entry (0, 0)") != nullptr);
+        }
+        EXPECT(ev(4, 4, 2, &si[0][0], &pi[0][0], -1, SLAM_COST_MAKHLIN) == SLAM_ERR_INVALID);
+        x0h[1][2][3] = std::numeric_limits<double>::infinity();
+        EXPECT(mn(4, 4, 2, &si[0][0], &pi[0][0], -1, 0, &x0h[0][0][0]) == SLAM_ERR_INVALID);
+        EXPECT(std::strstr(slam_last_error(), "x0[23]") != nullptr);
+        EXPECT(mn(4, 4, 2, &si[0][0], &pi[0][0], -1, 0, nullptr) == SLAM_ERR_INVALID);
+    }
     EXPECT(slam_set_cost(nullptr, 0) == SLAM_ERR_INVALID);
     EXPECT(slam_synchronize(nullptr) == SLAM_ERR_INVALID);
     EXPECT(slam_get_stats(nullptr, &st) == SLAM_ERR_INVALID);
